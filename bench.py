@@ -15,8 +15,12 @@ One "step" = one pass of the whole hot path (PE -> RoI gather -> query generator
 samples.  Every stream has its OWN frames and rotates through `--rotate` distinct frame sets (feature maps, 2-D boxes) from step to
 step; on the two-frame (T) workloads every sample of every step also has its own img_metas (ego motion, time stamps), so the
 calibration tables are rebuilt on the host and uploaded inside the timed loop.  Inputs are resident in HBM before the timed region.
-Extra legs after the timed region (same process, reported beside `value`): the round-1 protocol (every stream replays the same
-frames), one sample per launch on 4 streams, and one sample on one stream with a synchronisation per frame (latency).
+A plain run sets up, warms up, times the K steps and prints the headline (`metric`, `value`, `unit`, `ms_per_step`, `dtype`, `config`).
+`--full` adds everything else after the timed region (same process unless noted, reported beside `value`): the round-1 protocol (every
+stream replays the same frames), one sample per launch on 4 streams, one sample on one stream with a synchronisation per frame
+(latency), the other mode, the integer parity against the reference golden, per-stage timings and rooflines, the decoder alone, the
+CPU baseline, the other workloads and the one-rank RCCL leg (sub-processes of this script).
+`--dump-outputs DIR` writes the decoded detections of the last timed step as DIR/{boxes,scores,labels,count}.npy (float32).
 Prints ONE JSON line.
 """
 import argparse
@@ -233,6 +237,30 @@ def ws_rows(out):
     return int(out['ws']['x'].shape[0])
 
 
+def dump_outputs(out, path, max_bytes=64 << 20):
+    """--dump-outputs: what the last timed step handed back, i.e. the decoded detections of every sample of the step (the wire rows the
+    decode kernels wrote, [samples, max_num * 11 + 1]: per ranked entry 9 box values, score, label; then the count; rows past the count are
+    zero), unpacked into DIR/boxes.npy [n, max_num, 9], scores.npy / labels.npy [n, max_num] and count.npy [n], all float32.  Above
+    ``max_bytes`` a fixed, seeded sample of the samples is written, with their indices in sample_index.npy (float64)."""
+    rows = out.reshape(-1, out.shape[-1]).float().cpu().numpy()
+    n, width = rows.shape
+    max_num = (width - 1) // 11
+    if rows.nbytes > max_bytes:
+        keep = (max_bytes - 8 * n) // (width * 4)
+        idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        rows = rows[idx]
+    else:
+        idx = None
+    det = rows[:, :-1].reshape(rows.shape[0], max_num, 11)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, 'boxes.npy'), np.ascontiguousarray(det[..., :9]))
+    np.save(os.path.join(path, 'scores.npy'), np.ascontiguousarray(det[..., 9]))
+    np.save(os.path.join(path, 'labels.npy'), np.ascontiguousarray(det[..., 10]))
+    np.save(os.path.join(path, 'count.npy'), np.ascontiguousarray(rows[:, -1]))
+    if idx is not None:
+        np.save(os.path.join(path, 'sample_index.npy'), idx.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -271,6 +299,9 @@ def main():
     ap.add_argument('--fuse-xattn', type=int, default=None, help='1 / 0: force the one-launch cross attention (csrc/xattn_fused.hip) on / off (engine default: on for the S path)')
     ap.add_argument('--force-collective', action='store_true', help='one rank: initialise the process group (nccl = RCCL) anyway and run the per-step all-gather of decoded boxes')
     ap.add_argument('--no-collective-leg', action='store_true', help='skip the one-rank RCCL leg (a sub-process of this script with --force-collective)')
+    ap.add_argument('--full', action='store_true', help='after the timed steps, run every other leg (extra legs, parity, stage timings / rooflines, decoder, '
+                    'CPU baseline, other workloads, RCCL leg, long run, collective check; the --no-* / --brief options select among them); off: the headline only')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR', help='write the decoded detections of the last timed step as DIR/<name>.npy (float32)')
     args = ap.parse_args()
     if args.force_collective:
         os.environ['MV2D_FORCE_COLLECTIVE'] = '1'
@@ -420,9 +451,10 @@ def main():
     for _ in range(args.warmup):
         step()
     barrier()
+    out_last = None
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        out_last = step()
     barrier()
     elapsed = time.perf_counter() - t0
     if world > 1:
@@ -431,6 +463,45 @@ def main():
         elapsed = float(t.item())
     samples = world * args.inflight * G * B * args.steps
     value = samples / elapsed
+    if args.dump_outputs and rank == 0 and out_last is not None:
+        dump_outputs(out_last, args.dump_outputs)
+    del out_last
+
+    headline = {
+        'metric': 'multi-view samples/sec (6-cam frames) through the MV2D RoI-head hot path',
+        'value': round(value, 2), 'unit': 'samples/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'setup_steps': args.prime,
+        'ms_per_step': round(elapsed / args.steps * 1e3, 4), 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
+        'dtype': (('f16 (ONE rounding of the key side: opt-in key16 mode) / f16x3 split precision (query side)' if args.key16 else
+                   'f16x3: every operand an fp16 hi + lo pair, three MFMAs per product, fp32 accumulation (fp32-class, index-exact route; the lo halves of the key / value rows are STORED as e4m3 bytes)')), 'data': 'synthetic',
+        'route': 'key16_mode_opt_in' if args.key16 else 'index_exact',
+        'timed_seconds': round(elapsed, 3),
+        'config': {'workload': f'{args.workload}: MV2D-{kind} head, {len(metas)} views {metas[0]["img_shape"][1]}x{metas[0]["img_shape"][0]}' +
+                               (f', corr_topk={args.corr_topk}' if args.corr_topk else '') + (f', forced n_c={args.force_nc}' if args.force_nc else ''),
+                   'frames_per_step_per_gpu': args.inflight * G * B, 'global_batch': world * args.inflight * G * B,
+                   'streams_per_gpu': args.inflight, 'launch_sequences_per_stream_and_step': G, 'samples_per_launch': B,
+                   'feature_map_memory': 'contiguous NCHW' if args.nchw_input else 'channels_last (position-major rows, as mv2d_amd.plugin.neck writes them; logical NCHW)', 'pe_sine_branch': 'folded into a per-(weights, geometry) table, FLOPs not counted',
+                   'parallelism': f'dp{world}', 'hipgraph': use_graph},
+    }
+
+    def finish(line):
+        # RCCL writes its version banner through C stdio (block-buffered on a pipe, so it would come out at process exit, after the JSON
+        # line): every rank flushes it now, the barrier orders that before rank 0 prints, and the JSON line stays the last line of stdout
+        import ctypes
+        sys.stdout.flush()
+        try:
+            ctypes.CDLL(None).fflush(None)
+        except Exception:
+            pass
+        if dist.is_initialized():
+            dist.barrier()
+            dist.destroy_process_group()
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+
+    if not args.full:
+        return finish(headline)
+
+    # ---------------- --full: everything below is reported beside the headline
     # the contract's K steps may be a very short region (20 steps = 0.08 s): time a second, longer loop of the same step so that an
     # external sampler sees the GPU busy; both are reported, `value` stays the K-step number
     long_run = None
@@ -790,14 +861,14 @@ def main():
         for wl_, b_ in (('cfg2_s_nc6', 16), ('cfg3_t', 16), ('cfg5_t', 4)):
             try:
                 r = subprocess.run([sys.executable, os.path.abspath(__file__), '--workload', wl_, '--batch', str(b_), '--steps', '100', '--warmup', '10', '--rounds', '1',
-                                    '--brief'], cwd=ROOT, capture_output=True, text=True, timeout=240)
+                                    '--brief', '--full'], cwd=ROOT, capture_output=True, text=True, timeout=240)
                 ls_ = [l for l in r.stdout.splitlines() if l.startswith('{')]
                 d_ = json.loads(ls_[-1])
                 other[wl_] = {k: d_.get(k) for k in ('value', 'unit', 'route', 'ms_per_step', 'steps', 'config', 'decoder_ms_per_iter', 'decoder_ms_per_launch', 'roofline',
                                                      'index_mismatches')}
                 # ... and the same loop in the opt-in key16 mode
                 r = subprocess.run([sys.executable, os.path.abspath(__file__), '--workload', wl_, '--batch', str(b_), '--steps', '60', '--warmup', '10', '--rounds', '1',
-                                    '--brief', '--key16'], cwd=ROOT, capture_output=True, text=True, timeout=240)
+                                    '--brief', '--key16', '--full'], cwd=ROOT, capture_output=True, text=True, timeout=240)
                 ls_ = [l for l in r.stdout.splitlines() if l.startswith('{')]
                 d2_ = json.loads(ls_[-1])
                 other[wl_]['samples_s_key16_mode_opt_in'] = d2_.get('value')
@@ -813,7 +884,8 @@ def main():
         import subprocess
         try:
             r = subprocess.run([sys.executable, os.path.abspath(__file__), '--workload', args.workload, '--batch', str(B), '--inflight', str(args.inflight),
-                                '--rotate', str(args.rotate), '--rounds', str(G), '--steps', str(max(40, args.steps)), '--warmup', '5', '--brief', '--force-collective', '--no-parity-leg'],
+                                '--rotate', str(args.rotate), '--rounds', str(G), '--steps', str(max(40, args.steps)), '--warmup', '5', '--brief', '--force-collective', '--no-parity-leg',
+                                '--full'],
                                cwd=ROOT, capture_output=True, text=True, timeout=300)
             ls_ = [l for l in r.stdout.splitlines() if l.startswith('{')]
             d_ = json.loads(ls_[-1])
@@ -841,21 +913,12 @@ def main():
         except Exception:      # noqa: BLE001
             pass
 
+    line = None
     if rank == 0:
+        headline['config']['workload'] = (f'{args.workload}: MV2D-{kind} head, {len(metas)} views {metas[0]["img_shape"][1]}x{metas[0]["img_shape"][0]}, '
+                                          f'R={R} queries, S={S} key positions, nnz={nnz} allowed (q,k) pairs = {nnz / max(R, 1):.1f} keys per query' + (f' (totals of the {B} samples of a launch)' if B > 1 else '') + (f', corr_topk={args.corr_topk}' if args.corr_topk else '') + (f', forced n_c={args.force_nc}' if args.force_nc else ''))
         line = {
-            'metric': 'multi-view samples/sec (6-cam frames) through the MV2D RoI-head hot path',
-            'value': round(value, 2), 'unit': 'samples/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'setup_steps': args.prime,
-            'ms_per_step': round(elapsed / args.steps * 1e3, 4), 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
-            'dtype': (('f16 (ONE rounding of the key side: opt-in key16 mode) / f16x3 split precision (query side)' if args.key16 else
-                       'f16x3: every operand an fp16 hi + lo pair, three MFMAs per product, fp32 accumulation (fp32-class, index-exact route; the lo halves of the key / value rows are STORED as e4m3 bytes)')), 'data': 'synthetic',
-            'route': 'key16_mode_opt_in' if args.key16 else 'index_exact',
-            'timed_seconds': round(elapsed, 3),
-            'config': {'workload': f'{args.workload}: MV2D-{kind} head, {len(metas)} views {metas[0]["img_shape"][1]}x{metas[0]["img_shape"][0]}, '
-                                   f'R={R} queries, S={S} key positions, nnz={nnz} allowed (q,k) pairs = {nnz / max(R, 1):.1f} keys per query' + (f' (totals of the {B} samples of a launch)' if B > 1 else '') + (f', corr_topk={args.corr_topk}' if args.corr_topk else '') + (f', forced n_c={args.force_nc}' if args.force_nc else ''),
-                       'frames_per_step_per_gpu': args.inflight * G * B, 'global_batch': world * args.inflight * G * B,
-                       'streams_per_gpu': args.inflight, 'launch_sequences_per_stream_and_step': G, 'samples_per_launch': B,
-                       'feature_map_memory': 'contiguous NCHW' if args.nchw_input else 'channels_last (position-major rows, as mv2d_amd.plugin.neck writes them; logical NCHW)', 'pe_sine_branch': 'folded into a per-(weights, geometry) table, FLOPs not counted',
-                       'parallelism': f'dp{world}', 'hipgraph': use_graph},
+            **headline,
             'decoder_ms_per_iter': round(decoder_ms / B, 4), 'decoder_ms_per_launch': round(decoder_ms, 4),
             'decoder_ms_per_iter_batch1': round(decoder_ms_b1, 4) if decoder_ms_b1 is not None else (round(decoder_ms, 4) if B == 1 else None),
             'long_run': long_run, 'ranked_index_mismatches_vs_reference': parity, 'other_workloads': other,
@@ -866,19 +929,7 @@ def main():
             'cpu_baseline': cpu, 'cpu_baseline_all_cores': cpu2,
             **extra,
         }
-    # RCCL writes its version banner through C stdio (block-buffered on a pipe, so it would come out at process exit, after the JSON
-    # line): every rank flushes it now, the barrier orders that before rank 0 prints, and the JSON line stays the last line of stdout
-    import ctypes
-    sys.stdout.flush()
-    try:
-        ctypes.CDLL(None).fflush(None)
-    except Exception:
-        pass
-    if dist.is_initialized():
-        dist.barrier()
-        dist.destroy_process_group()
-    if rank == 0:
-        print(json.dumps(line), flush=True)
+    finish(line)
 
 
 if __name__ == '__main__':

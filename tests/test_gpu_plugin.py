@@ -401,7 +401,7 @@ def test_bench_two_ranks_rccl_when_two_gpus_are_visible():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_PORT')}
     r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '10', '--warmup', '3', '--prime', '5', '--brief',
-                        '--no-parity-leg'], cwd=root, env=env, capture_output=True, text=True, timeout=900)
+                        '--no-parity-leg', '--full'], cwd=root, env=env, capture_output=True, text=True, timeout=900)
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
     assert r.returncode == 0 and lines, (r.returncode, r.stdout[-500:], r.stderr[-2000:])
     d = json.loads(lines[-1])

@@ -2,7 +2,7 @@
 # round 6: the whole GPU suite + the bench line in the driver's call shape
 O=gpurun_out/r06f; mkdir -p $O
 timeout 2400 python -m pytest tests -m gpu -q -x 2>&1 | tail -15 > $O/gpu_tests.txt; cat $O/gpu_tests.txt
-timeout 1200 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/driver_shape.json 2> $O/bench.err; tail -c 400 $O/bench.err
+timeout 1200 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/driver_shape.json 2> $O/bench.err; tail -c 400 $O/bench.err
 python - <<'PY'
 import json
 d = json.loads([l for l in open('gpurun_out/r06f/driver_shape.json') if l.startswith('{')][-1])

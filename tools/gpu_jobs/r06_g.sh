@@ -1,8 +1,8 @@
 #!/bin/bash
 O=gpurun_out/r06g; mkdir -p $O
-timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --no-other-workloads --no-cpu-baseline --no-collective-leg > $O/a.json 2> $O/bench.err; tail -c 300 $O/bench.err
-timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --brief --nchw-input > $O/b.json 2>> $O/bench.err
-timeout 600 python bench.py --gpus 1 --steps 120 --warmup 5 --brief --rounds 1 > $O/c.json 2>> $O/bench.err
+timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-other-workloads --no-cpu-baseline --no-collective-leg > $O/a.json 2> $O/bench.err; tail -c 300 $O/bench.err
+timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 --brief --nchw-input > $O/b.json 2>> $O/bench.err
+timeout 600 python bench.py --full --gpus 1 --steps 120 --warmup 5 --brief --rounds 1 > $O/c.json 2>> $O/bench.err
 python - <<'PY'
 import json
 for f in 'abc':

@@ -1,7 +1,7 @@
 # the two bench JSONs of tools/r06_evidence.sh step 1 again, now that profiles/ holds the kernel trace and the counters of THIS library
 O=gpurun_out/r06; mkdir -p $O
-timeout 1500 python bench.py > $O/default_bench_cfg2s.json 2> $O/bench.err
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/driver_shape_bench_cfg2s.json 2>> $O/bench.err
+timeout 1500 python bench.py --full > $O/default_bench_cfg2s.json 2> $O/bench.err
+timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/driver_shape_bench_cfg2s.json 2>> $O/bench.err
 python - <<'PY'
 import json
 for f in ('default_bench_cfg2s', 'driver_shape_bench_cfg2s'):

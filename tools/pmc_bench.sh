@@ -15,8 +15,5 @@ for c in "${PASSES[@]}"; do
   rm -rf $R/gpurun_out/$OUT/raw
 done
 if [ "${STATS:-1}" = "1" ]; then
-  timeout 300 rocprofv3 --kernel-trace --stats -d $R/gpurun_out/$OUT/stats -o s -- python $R/bench.py --steps 100 --no-cpu-baseline --no-extra-legs --no-other-workloads --no-collective-leg "$@" > $R/gpurun_out/$OUT/bench_under_rocprof.json 2>/dev/null
-  python $R/tools/rocpd_stats.py $(find $R/gpurun_out/$OUT/stats -name "s_results.db" | head -1) > $R/gpurun_out/$OUT/kernel_stats.txt 2>&1
-  rm -rf $R/gpurun_out/$OUT/stats
-  head -30 $R/gpurun_out/$OUT/kernel_stats.txt
+  HEAD=30 bash $R/tools/prof_stats.sh $OUT --full --no-extra-legs --no-collective-leg "$@"
 fi

@@ -5,18 +5,18 @@ mkdir -p $O
 # 0. fp16 MFMA keeps subnormal inputs (the hi + lo key rows rely on it)
 timeout 60 mv2d_amd/lib/f16_mfma_probe > $O/f16_mfma_probe.txt 2>&1
 # 1. the default bench line (CPU baseline leg, index-exact leg, one-rank RCCL leg, mismatch counts, other workloads) and the driver's call shape
-timeout 900 python bench.py --steps 100 > $O/default_bench_cfg2s.json 2> $O/bench.err
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/driver_shape_bench_cfg2s.json 2>> $O/bench.err
+timeout 900 python bench.py --full --steps 100 > $O/default_bench_cfg2s.json 2> $O/bench.err
+timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/driver_shape_bench_cfg2s.json 2>> $O/bench.err
 # 2. rocprofv3 kernel summary of the same default command (extra legs off) + PMC passes of the eager single-stream bench per workload
-HEAD=5 tools/prof_stats.sh r04/stats_default --no-extra-legs --no-parity-leg --no-collective-leg > /dev/null 2>&1
+HEAD=5 tools/prof_stats.sh r04/stats_default --full --no-extra-legs --no-parity-leg --no-collective-leg > /dev/null 2>&1
 mv $O/stats_default/kernel_stats.txt $O/default_bench_cfg2s_kernel_stats.txt; mv $O/stats_default/bench_under_rocprof.json $O/default_bench_cfg2s_under_rocprof.json; rmdir $O/stats_default
 L2=1 STATS=0 bash tools/pmc_bench.sh r04/pmc_cfg2s > /dev/null 2>&1
 L2=1 STATS=0 bash tools/pmc_bench.sh r04/pmc_cfg2s_nc6 --workload cfg2_s_nc6 > /dev/null 2>&1
 L2=1 STATS=0 bash tools/pmc_bench.sh r04/pmc_cfg3t --workload cfg3_t --batch 16 > /dev/null 2>&1
 L2=1 STATS=0 bash tools/pmc_bench.sh r04/pmc_cfg5t --workload cfg5_t --batch 4 > /dev/null 2>&1
 # 3. the one-rank RCCL leg under the kernel trace: the all-gather kernel beside the frame kernels
-HEAD=40 tools/prof_cmd.sh r04/prof_rccl python bench.py --brief --force-collective --steps 60 --warmup 10 --no-parity-leg > /dev/null 2>&1
-timeout 300 python bench.py --brief --force-collective --steps 200 --warmup 10 --no-parity-leg > $O/bench_cfg2s_one_rank_rccl.json 2>> $O/bench.err
+HEAD=40 tools/prof_cmd.sh r04/prof_rccl python bench.py --full --brief --force-collective --steps 60 --warmup 10 --no-parity-leg > /dev/null 2>&1
+timeout 300 python bench.py --full --brief --force-collective --steps 200 --warmup 10 --no-parity-leg > $O/bench_cfg2s_one_rank_rccl.json 2>> $O/bench.err
 # 4. per-kernel tables of one stream replaying 16-sample frames: default / index-exact route, S and T path; one sample per launch
 for w in "default_cfg2s --batch 16" "exact_cfg2s --exact --batch 16" "default_cfg3t --workload cfg3_t --batch 16" "exact_cfg3t --exact --workload cfg3_t --batch 16" \
          "default_cfg5t --workload cfg5_t --batch 4" "default_cfg2s_batch1 --batch 1"; do

@@ -3,12 +3,12 @@
 O=gpurun_out/r06
 mkdir -p $O
 # 1. the default bench line (index-exact route; CPU baseline legs, key16-mode leg, one-rank RCCL leg, mismatch counts, other workloads) and the driver's call shape
-timeout 1500 python bench.py > $O/default_bench_cfg2s.json 2> $O/bench.err
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/driver_shape_bench_cfg2s.json 2>> $O/bench.err
+timeout 1500 python bench.py --full > $O/default_bench_cfg2s.json 2> $O/bench.err
+timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/driver_shape_bench_cfg2s.json 2>> $O/bench.err
 # 1b. a sustained run: 640 steps of 384 frames (~29 s of timed steps) -- clocks and throughput under a long load
-timeout 900 python bench.py --steps 640 --warmup 20 --brief --no-parity-leg 2>> $O/bench.err | tail -n 1 > $O/soak_bench_cfg2s.json
+timeout 900 python bench.py --full --steps 640 --warmup 20 --brief --no-parity-leg 2>> $O/bench.err | tail -n 1 > $O/soak_bench_cfg2s.json
 # 2. rocprofv3 kernel summary of the default command (extra legs off) + PMC passes of the eager single-stream bench per workload
-HEAD=5 tools/prof_stats.sh r06/stats_default --steps 40 --no-extra-legs --no-parity-leg --no-collective-leg > /dev/null 2>&1
+HEAD=5 tools/prof_stats.sh r06/stats_default --full --steps 40 --no-extra-legs --no-parity-leg --no-collective-leg > /dev/null 2>&1
 mv $O/stats_default/kernel_stats.txt $O/default_bench_cfg2s_kernel_stats.txt; mv $O/stats_default/bench_under_rocprof.json $O/default_bench_cfg2s_under_rocprof.json; rmdir $O/stats_default
 L2=1 STATS=0 bash tools/pmc_bench.sh r06/pmc_cfg2s --rounds 1 > /dev/null 2>&1
 STATS=0 bash tools/pmc_bench.sh r06/pmc_cfg2s_nc6 --rounds 1 --workload cfg2_s_nc6 > /dev/null 2>&1
@@ -17,8 +17,8 @@ STATS=0 bash tools/pmc_bench.sh r06/pmc_cfg5t --rounds 1 --workload cfg5_t --bat
 STATS=0 bash tools/pmc_bench.sh r06/pmc_cfg2s_key16 --rounds 1 --key16 > /dev/null 2>&1
 STATS=0 bash tools/pmc_bench.sh r06/pmc_cfg2s_nchw --rounds 1 --nchw-input > /dev/null 2>&1
 # 3. the one-rank RCCL leg under the kernel trace
-HEAD=40 tools/prof_cmd.sh r06/prof_rccl python bench.py --brief --force-collective --steps 20 --warmup 5 --no-parity-leg > /dev/null 2>&1
-timeout 300 python bench.py --brief --force-collective --steps 40 --warmup 5 --no-parity-leg > $O/bench_cfg2s_one_rank_rccl.json 2>> $O/bench.err
+HEAD=40 tools/prof_cmd.sh r06/prof_rccl python bench.py --full --brief --force-collective --steps 20 --warmup 5 --no-parity-leg > /dev/null 2>&1
+timeout 300 python bench.py --full --brief --force-collective --steps 40 --warmup 5 --no-parity-leg > $O/bench_cfg2s_one_rank_rccl.json 2>> $O/bench.err
 # 4. per-kernel tables of one stream replaying 16-sample frames: index-exact route (S, T), the opt-in key16 mode, one sample per launch, the two opt-in round-6 kernels
 for w in "exact_cfg2s --batch 16" "key16_cfg2s --key16 --batch 16" "exact_cfg3t --workload cfg3_t --batch 16" "exact_cfg5t --workload cfg5_t --batch 4" \
          "exact_cfg2s_nc6 --workload cfg2_s_nc6 --batch 16" "exact_cfg2s_batch1 --batch 1" "optin_group_xattn_cfg3t --workload cfg3_t --batch 16 --group 1" \
@@ -30,7 +30,7 @@ done
 # 5. the round-6 experiments: launch order / shared-tile cross attention, the two shapes of the PE kernel, queries per block of the one-launch attention
 for w in cfg3_t cfg5_t cfg2_s_nc6; do timeout 600 python tools/microbench_cluster_order.py $w 2>&1 | grep -v Warn | tail -9; done > $O/cluster_order_and_shared_tiles.txt
 (python tools/pe_time.py 250000 1; python tools/pe_time.py 100000 0) 2>&1 | grep rows > $O/pe_kernel_shapes.txt
-for qb in 8 4; do MV2D_XF_QB=$qb timeout 600 python bench.py --steps 20 --warmup 5 --brief --no-parity-leg 2>/dev/null | python -c "import sys,json; d=json.loads([l for l in sys.stdin if l.startswith(chr(123))][-1]); print('xattn_fused queries per block = $qb: cfg2_s', d['value'], 'samples/s, kernel', d['roofline'].get('launch_ms_idle_gpu'), 'ms per launch (idle GPU)')"; done > $O/xattn_fused_queries_per_block.txt
+for qb in 8 4; do MV2D_XF_QB=$qb timeout 600 python bench.py --full --steps 20 --warmup 5 --brief --no-parity-leg 2>/dev/null | python -c "import sys,json; d=json.loads([l for l in sys.stdin if l.startswith(chr(123))][-1]); print('xattn_fused queries per block = $qb: cfg2_s', d['value'], 'samples/s, kernel', d['roofline'].get('launch_ms_idle_gpu'), 'ms per launch (idle GPU)')"; done > $O/xattn_fused_queries_per_block.txt
 bash tools/pmc_group.sh cfg3_t 16 > /dev/null 2>&1; cp gpurun_out/pmcgroup_cfg3_t/summary.txt $O/pmc_xattn_group_cfg3t.txt
 # 6. which key-side rounding costs how many ranks (query side in fp16 pairs)
 python tools/ablate_exact.py 2>/dev/null > $O/ablate_exact.txt

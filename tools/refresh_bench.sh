@@ -1,7 +1,10 @@
-mkdir -p gpurun_out/r2
-timeout 280 python bench.py --steps 100 > gpurun_out/r2/bench_default.json 2> gpurun_out/r2/bench_default.err
-timeout 200 python bench.py --steps 100 --workload cfg3_t --no-cpu-baseline > gpurun_out/r2/bench_cfg3_t.json 2>> gpurun_out/r2/bench_default.err
-timeout 200 python bench.py --steps 100 --workload cfg5_t --batch 2 --no-cpu-baseline > gpurun_out/r2/bench_cfg5_t.json 2>> gpurun_out/r2/bench_default.err
-timeout 200 python bench.py --steps 100 --batch 1 --no-cpu-baseline > gpurun_out/r2/bench_batch1.json 2>> gpurun_out/r2/bench_default.err
-timeout 200 python bench.py --steps 100 --batch 1 --inflight 1 --no-cpu-baseline > gpurun_out/r2/bench_single.json 2>> gpurun_out/r2/bench_default.err
-tail -c 600 gpurun_out/r2/bench_default.err
+# The default bench line (with the CPU baseline), the two T-path workloads and the one-sample-per-call shapes.
+# usage (on the GPU box): bash tools/refresh_bench.sh <outdir>
+O=${1:?usage: bash tools/refresh_bench.sh <outdir>}
+mkdir -p $O
+timeout 280 python bench.py --full --steps 100 > $O/bench_default.json 2> $O/bench_default.err
+timeout 200 python bench.py --full --steps 100 --workload cfg3_t --no-cpu-baseline > $O/bench_cfg3_t.json 2>> $O/bench_default.err
+timeout 200 python bench.py --full --steps 100 --workload cfg5_t --batch 2 --no-cpu-baseline > $O/bench_cfg5_t.json 2>> $O/bench_default.err
+timeout 200 python bench.py --full --steps 100 --batch 1 --no-cpu-baseline > $O/bench_batch1.json 2>> $O/bench_default.err
+timeout 200 python bench.py --full --steps 100 --batch 1 --inflight 1 --no-cpu-baseline > $O/bench_single.json 2>> $O/bench_default.err
+tail -c 600 $O/bench_default.err
