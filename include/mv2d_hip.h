@@ -211,6 +211,11 @@ int mv2d_split_rows_key16(const float* a, const float* b, void* hi, void* lo, in
  * mv2d_pack_wfrag_bf16 copies. */
 int mv2d_heads_fused_x3(const float* outs, const void* const* cls_w, const void* const* reg_w, const float* ref, float* cls, float* reg,
                         int M, int L, float eps, const float* pc_range, float dt, const float* dt_rows, void* stream);
+/* The same launch for 1 <= num_classes <= 64 classes: cls_w w6 [L,num_classes,256], b6 [L,num_classes], out cls [L,M,num_classes] (reg stays
+ * [L,M,10]).  The class output layer takes ceil(num_classes / 16) 16-column tiles, run by the waves that are idle behind the last 256x256
+ * linear at one tile.  mv2d_heads_fused_x3 is this entry with num_classes = 10; the fp32 mv2d_heads_fused above stays 10-class only. */
+int mv2d_heads_fused_x3_nc(const float* outs, const void* const* cls_w, const void* const* reg_w, const float* ref, float* cls, float* reg,
+                           int M, int L, int num_classes, float eps, const float* pc_range, float dt, const float* dt_rows, void* stream);
 
 /* Fused FFN partial sums (mmcv FFN 256 -> hidden -> 256 of the decoder layer, configs/mv2d/exp/*:78-79):
  * slabs[s] = relu(X . W1[64s:64s+64]^T + b1[64s:64s+64]) . W2[:, 64s:64s+64]^T  for the hidden/64 slices s, exact fp32.
@@ -498,6 +503,8 @@ int mv2d_pe_inputs(const int* s2pos, const int* S_dev, int S_max, const float* f
 
 /* NMSFreeCoder.decode_single + get_bboxes (CB/coders/nms_free_coder.py:49-102, CB/util.py:60-87,
  * RH/bbox_heads/cross_attention_head.py:357-377): top-k over R*num_classes logits, denormalise, centre-range filter.
+ * rows (of the largest sample) * num_classes <= 65536: up to 16384 candidates the keys are held in LDS, above that a second kernel
+ * recomputes them from cls on every radix pass (same results, bit for bit).
  * out: boxes [<=max_num,9], scores, labels (int64), bbox_index (int64), *count_out.
  * A batch (grp_start != NULL): one top-k per sample, outputs [n_samples][max_num], count_out [n_samples], bbox_index relative to
  * the sample's first row; max_grp_rows = rows of the largest sample.

@@ -78,21 +78,28 @@ def _common(with_cp):
     )
 
 
-def roi_head_cfg_s():
-    """CFG-S:40-121 (MV2D-S single frame)."""
+def _set_num_classes(d, num_classes):
+    # the reference config key, set in both places it appears (head and coder); 10 = nuScenes
+    d['bbox_head']['num_classes'] = num_classes
+    d['bbox_head']['bbox_coder']['num_classes'] = num_classes
+    return d
+
+
+def roi_head_cfg_s(num_classes=10):
+    """CFG-S:40-121 (MV2D-S single frame); ``num_classes`` sets ``bbox_head.num_classes`` and ``bbox_head.bbox_coder.num_classes``."""
     d = dict(type='MV2DSHead', use_denoise=False)
     d.update(_common(with_cp=False))
     d['box_correlation'] = dict(correlation_mode='topk_matched:1:0.0:0.0')
-    return copy.deepcopy(d)
+    return copy.deepcopy(_set_num_classes(d, num_classes))
 
 
-def roi_head_cfg_t():
-    """CFG-T:40-125 (MV2D-T two frames)."""
+def roi_head_cfg_t(num_classes=10):
+    """CFG-T:40-125 (MV2D-T two frames); ``num_classes`` as in ``roi_head_cfg_s``."""
     d = dict(type='MV2DTHead', use_denoise=True, neg_bbox_loss=True,
              denoise_noise_scale=1.25, denoise_split=0.6)
     d.update(_common(with_cp=True))
     d['box_correlation'] = dict(expand_stride=2, correlation_mode='topk_matched:20:0.0:0.0')
-    return copy.deepcopy(d)
+    return copy.deepcopy(_set_num_classes(d, num_classes))
 
 
 TEST_CFG_RCNN = dict(score_thr=0.0, nms=dict(nms_thr=1.0, use_rotate_nms=True), max_per_scene=300)  # CFG-T:154-158

@@ -988,84 +988,28 @@ __global__ __launch_bounds__(256) void pe_inputs_kernel(const int* __restrict__ 
 
 // ------------------------------------------------------------------------------------------------
 // a21: NMS-free decode (CB/coders/nms_free_coder.py:49-102, CB/util.py:60-87,
-//      cross_attention_head.py:372): single block, bitonic sort of (logit, index) in LDS.
+//      cross_attention_head.py:372): single block, radix select of (logit, index) keys + ranking of the survivors.
 //      Order: logit descending, lower flat index first among equals.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(1024) void decode_topk_kernel(const float* __restrict__ cls, const float* __restrict__ reg, int R, int ncls, int max_num,
-                                                           int npow2, float r0, float r1, float r2, float r3, float r4, float r5,
-                                                           float* __restrict__ boxes, float* __restrict__ scores, long long* __restrict__ labels,
-                                                           long long* __restrict__ bbox_index, int* __restrict__ count_out,
-                                                           long long* __restrict__ topk_index_dbg, const int* __restrict__ grp_start,
-                                                           float* __restrict__ payload) {
-    // keys: 64-bit (monotone logit bits << 32 | ~index) -> all distinct, "larger" = higher logit, then LOWER index.
-    // 1) 8 rounds of 8-bit radix select find the K-th largest key; 2) the K survivors are ranked by counting
-    //    (K^2 compares spread over 1024 threads) — no full sort of the R*ncls candidates.
-    extern __shared__ unsigned long long keys[];               // [n] all keys, then [1024] survivors
-    __shared__ int hist[256];
-    __shared__ unsigned long long prefix_s;
-    __shared__ int want_s, nsel;
-    __shared__ int kept_off[1025];
-    // one block per sample of the batch: rows [grp_start[g], grp_start[g+1]), outputs [g][max_num] (bbox_index relative to the sample)
-    if (grp_start) {
-        const int g = blockIdx.x, gs = grp_start[g];
-        R = grp_start[g + 1] - gs;
-        cls += (long long)gs * ncls; reg += (long long)gs * 10;
-        boxes += (long long)g * max_num * 9; scores += (long long)g * max_num; labels += (long long)g * max_num;
-        bbox_index += (long long)g * max_num; count_out += g;
-        if (topk_index_dbg) topk_index_dbg += (long long)g * max_num;
-        if (payload) payload += (long long)g * ((long long)max_num * 11 + 1);
-    }
-    const int tid = threadIdx.x, n = R * ncls;
-    const int K = min(max_num, n);
-    unsigned long long* sel = keys + npow2;
-    for (int i = tid; i < n; i += 1024) {
-        unsigned int u = __float_as_uint(cls[i]);
-        u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);           // monotone float -> uint
-        keys[i] = ((unsigned long long)u << 32) | (unsigned int)(0xffffffffu - (unsigned int)i);
-    }
-    if (tid == 0) { prefix_s = 0ull; want_s = K; nsel = 0; }
-    __syncthreads();
-    // radix select over the 32 logit bits (4 rounds); the bin holding the K-th element is found by one wave with a
-    // suffix scan over 256 bins (4 bins per lane)
-    for (int shift = 56; shift >= 32; shift -= 8) {
-        if (tid < 256) hist[tid] = 0;
-        __syncthreads();
-        const unsigned long long prefix = prefix_s;
-        const unsigned long long mask_hi = shift == 56 ? 0ull : (~0ull << (shift + 8));
-        for (int i = tid; i < n; i += 1024) {
-            const unsigned long long k = keys[i];
-            if ((k & mask_hi) == prefix) atomicAdd(&hist[(int)((k >> shift) & 0xffull)], 1);
-        }
-        __syncthreads();
-        if (tid < 64) {
-            const int h0 = hist[4 * tid], h1 = hist[4 * tid + 1], h2 = hist[4 * tid + 2], h3 = hist[4 * tid + 3];
-            const int s4 = h0 + h1 + h2 + h3;
-            int suf = s4;                                   // inclusive suffix sum over lanes tid..63
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_down(suf, o, 64); if (tid + o < 64) suf += t; }
-            const int want = want_s;
-            const unsigned long long bal = __ballot(suf >= want);
-            const int hit = 63 - __clzll(bal);              // highest lane whose suffix still covers `want`
-            if (tid == hit) {
-                int w = want - (suf - s4);                  // still wanted inside this lane's 4 bins
-                int b = 4 * tid + 3;
-                const int hh[4] = {h0, h1, h2, h3};
-                for (int e = 3; e > 0; --e) { if (hh[e] >= w) break; w -= hh[e]; --b; }
-                prefix_s = prefix | ((unsigned long long)b << shift);
-                want_s = w;
-            }
-        }
-        __syncthreads();
-    }
-    const unsigned long long kth_hi = prefix_s;                   // upper 32 bits of the K-th largest key
-    for (int i = tid; i < n; i += 1024) {
-        const unsigned long long k = keys[i];
-        if ((k & 0xffffffff00000000ull) >= kth_hi) { const int slot = atomicAdd(&nsel, 1); if (slot < 1024) sel[slot] = k; }
-    }
-    __syncthreads();
+// key of candidate i: 64-bit (monotone logit bits << 32 | ~index) -> all distinct, "larger" = higher logit, then LOWER index
+__device__ __forceinline__ unsigned long long decode_key(const float* __restrict__ cls, int i) {
+    unsigned int u = __float_as_uint(cls[i]);
+    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);           // monotone float -> uint
+    return ((unsigned long long)u << 32) | (unsigned int)(0xffffffffu - (unsigned int)i);
+}
+
+// The part both variants share, from the ns survivors sel[0..ns) on (their keys' upper halves >= that of the K-th largest key):
+// rank by counting, gather + denormalise + centre-range filter, compaction of the kept entries, the optional payload row.
+// `sorted` receives the K ranked keys; it may be `sel` itself (a barrier separates the reads from the writes).
+__device__ __forceinline__ void decode_rank_emit(const unsigned long long* sel, unsigned long long* sorted, int ns, int K, int* hist, int* kept_off,
+                                                 const float* __restrict__ cls, const float* __restrict__ reg, int ncls, int max_num,
+                                                 float r0, float r1, float r2, float r3, float r4, float r5,
+                                                 float* __restrict__ boxes, float* __restrict__ scores, long long* __restrict__ labels,
+                                                 long long* __restrict__ bbox_index, int* __restrict__ count_out,
+                                                 long long* __restrict__ topk_index_dbg, float* __restrict__ payload) {
+    const int tid = threadIdx.x;
     // rank by counting among the survivors (K plus, rarely, a few equal-logit candidates; ties resolved by the low
     // 32 bits = lower index first); ranks >= K are dropped
-    const int ns = min(nsel, 1024);
     unsigned long long mine = 0ull;
     int rank = 1 << 30;
     if (tid < ns) {
@@ -1074,13 +1018,13 @@ __global__ __launch_bounds__(1024) void decode_topk_kernel(const float* __restri
         for (int j = 0; j < ns; ++j) rank += sel[j] > mine ? 1 : 0;
     }
     __syncthreads();
-    if (rank < K) keys[rank] = mine;                              // keys[0..K) now sorted descending
+    if (rank < K) sorted[rank] = mine;                            // sorted[0..K) now sorted descending
     __syncthreads();
     // ---- gather + denormalise + centre-range filter, kept entries keep their rank order
     int keep = 0;
     float bx[9]; float sc = 0.f; int idx = 0;
     if (tid < K) {
-        idx = (int)(0xffffffffu - (unsigned int)(keys[tid] & 0xffffffffull));
+        idx = (int)(0xffffffffu - (unsigned int)(sorted[tid] & 0xffffffffull));
         if (topk_index_dbg) topk_index_dbg[tid] = idx;
         const int q = idx / ncls;
         const float* bp = reg + (long long)q * 10;
@@ -1122,6 +1066,81 @@ __global__ __launch_bounds__(1024) void decode_topk_kernel(const float* __restri
         }
         if (tid == 0) payload[(long long)max_num * 11] = (float)*count_out;
     }
+}
+
+// STREAM = false: all R*ncls keys live in LDS (n <= 16384).  STREAM = true (n <= 65536): no key array -- every pass of the radix select
+// recomputes the keys from `cls` in global memory (L2-resident: 4 reads of at most 256 KB), only the <= 1024 survivors go to LDS.
+template <bool STREAM>
+__global__ __launch_bounds__(1024) void decode_topk_kernel(const float* __restrict__ cls, const float* __restrict__ reg, int R, int ncls, int max_num,
+                                                           int npow2, float r0, float r1, float r2, float r3, float r4, float r5,
+                                                           float* __restrict__ boxes, float* __restrict__ scores, long long* __restrict__ labels,
+                                                           long long* __restrict__ bbox_index, int* __restrict__ count_out,
+                                                           long long* __restrict__ topk_index_dbg, const int* __restrict__ grp_start,
+                                                           float* __restrict__ payload) {
+    // 1) 4 rounds of 8-bit radix select over the logit bits find the upper half of the K-th largest key; 2) the K survivors are ranked
+    //    by counting (K^2 compares spread over 1024 threads) — no full sort of the R*ncls candidates.
+    extern __shared__ unsigned long long keys[];               // LDS: [n] all keys, then [1024] survivors; STREAM: [1024] survivors
+    __shared__ int hist[256];
+    __shared__ unsigned long long prefix_s;
+    __shared__ int want_s, nsel;
+    __shared__ int kept_off[1025];
+    // one block per sample of the batch: rows [grp_start[g], grp_start[g+1]), outputs [g][max_num] (bbox_index relative to the sample)
+    if (grp_start) {
+        const int g = blockIdx.x, gs = grp_start[g];
+        R = grp_start[g + 1] - gs;
+        cls += (long long)gs * ncls; reg += (long long)gs * 10;
+        boxes += (long long)g * max_num * 9; scores += (long long)g * max_num; labels += (long long)g * max_num;
+        bbox_index += (long long)g * max_num; count_out += g;
+        if (topk_index_dbg) topk_index_dbg += (long long)g * max_num;
+        if (payload) payload += (long long)g * ((long long)max_num * 11 + 1);
+    }
+    const int tid = threadIdx.x, n = R * ncls;
+    const int K = min(max_num, n);
+    unsigned long long* sel = STREAM ? keys : keys + npow2;
+    if (!STREAM)
+        for (int i = tid; i < n; i += 1024) keys[i] = decode_key(cls, i);
+    if (tid == 0) { prefix_s = 0ull; want_s = K; nsel = 0; }
+    __syncthreads();
+    // radix select over the 32 logit bits (4 rounds); the bin holding the K-th element is found by one wave with a
+    // suffix scan over 256 bins (4 bins per lane)
+    for (int shift = 56; shift >= 32; shift -= 8) {
+        if (tid < 256) hist[tid] = 0;
+        __syncthreads();
+        const unsigned long long prefix = prefix_s;
+        const unsigned long long mask_hi = shift == 56 ? 0ull : (~0ull << (shift + 8));
+        for (int i = tid; i < n; i += 1024) {
+            const unsigned long long k = STREAM ? decode_key(cls, i) : keys[i];
+            if ((k & mask_hi) == prefix) atomicAdd(&hist[(int)((k >> shift) & 0xffull)], 1);
+        }
+        __syncthreads();
+        if (tid < 64) {
+            const int h0 = hist[4 * tid], h1 = hist[4 * tid + 1], h2 = hist[4 * tid + 2], h3 = hist[4 * tid + 3];
+            const int s4 = h0 + h1 + h2 + h3;
+            int suf = s4;                                   // inclusive suffix sum over lanes tid..63
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_down(suf, o, 64); if (tid + o < 64) suf += t; }
+            const int want = want_s;
+            const unsigned long long bal = __ballot(suf >= want);
+            const int hit = 63 - __clzll(bal);              // highest lane whose suffix still covers `want`
+            if (tid == hit) {
+                int w = want - (suf - s4);                  // still wanted inside this lane's 4 bins
+                int b = 4 * tid + 3;
+                const int hh[4] = {h0, h1, h2, h3};
+                for (int e = 3; e > 0; --e) { if (hh[e] >= w) break; w -= hh[e]; --b; }
+                prefix_s = prefix | ((unsigned long long)b << shift);
+                want_s = w;
+            }
+        }
+        __syncthreads();
+    }
+    const unsigned long long kth_hi = prefix_s;                   // upper 32 bits of the K-th largest key
+    for (int i = tid; i < n; i += 1024) {
+        const unsigned long long k = STREAM ? decode_key(cls, i) : keys[i];
+        if ((k & 0xffffffff00000000ull) >= kth_hi) { const int slot = atomicAdd(&nsel, 1); if (slot < 1024) sel[slot] = k; }
+    }
+    __syncthreads();
+    decode_rank_emit(sel, keys, min(nsel, 1024), K, hist, kept_off, cls, reg, ncls, max_num, r0, r1, r2, r3, r4, r5, boxes, scores, labels,
+                     bbox_index, count_out, topk_index_dbg, payload);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1431,19 +1450,28 @@ extern "C" int mv2d_decode_topk(const float* cls, const float* reg, int R, int n
     MV2D_CHECK_ARG(cls && reg && post_center_range && boxes && scores && labels && bbox_index && count_out, "mv2d_decode_topk: null pointer");
     MV2D_CHECK_ARG(max_num >= 1 && max_num <= 1024, "mv2d_decode_topk: max_num must be in [1, 1024]");
     MV2D_CHECK_ARG(!grp_start || (n_grp >= 1 && max_grp_rows >= 1 && max_grp_rows <= R), "mv2d_decode_topk: bad sample list");
-    const int n = (grp_start ? max_grp_rows : R) * num_classes;
-    MV2D_CHECK_ARG(n > 0 && n <= 16384, "mv2d_decode_topk: rows (of one sample) * num_classes must be in [1, 16384]");
-    int npow2 = 1024;
-    while (npow2 < n) npow2 <<= 1;
-    const size_t lds = (size_t)(npow2 + 1024) * 8;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute((const void*)decode_topk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (16384 + 1024) * 8);
-        attr_set = true;
+    const int rows = grp_start ? max_grp_rows : R;
+    MV2D_CHECK_ARG(rows >= 1 && num_classes >= 1 && (long long)rows * num_classes <= 65536,
+                   "mv2d_decode_topk: rows (of one sample) * num_classes must be in [1, 65536]");
+    const int n = rows * num_classes;
+    const hipStream_t st = (hipStream_t)stream;
+    if (n <= 16384) {                                            // every key in LDS
+        int npow2 = 1024;
+        while (npow2 < n) npow2 <<= 1;
+        const size_t lds = (size_t)(npow2 + 1024) * 8;
+        static bool attr_set = false;
+        if (!attr_set) {
+            hipFuncSetAttribute((const void*)decode_topk_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (16384 + 1024) * 8);
+            attr_set = true;
+        }
+        hipLaunchKernelGGL(decode_topk_kernel<false>, dim3(grp_start ? n_grp : 1), dim3(1024), lds, st, cls, reg, R, num_classes, max_num, npow2,
+                           post_center_range[0], post_center_range[1], post_center_range[2], post_center_range[3], post_center_range[4],
+                           post_center_range[5], boxes, scores, labels, bbox_index, count_out, topk_index_dbg, grp_start, payload);
+    } else {                                                     // keys recomputed from cls on every pass, survivors in LDS
+        hipLaunchKernelGGL(decode_topk_kernel<true>, dim3(grp_start ? n_grp : 1), dim3(1024), 1024 * 8, st, cls, reg, R, num_classes, max_num, 0,
+                           post_center_range[0], post_center_range[1], post_center_range[2], post_center_range[3], post_center_range[4],
+                           post_center_range[5], boxes, scores, labels, bbox_index, count_out, topk_index_dbg, grp_start, payload);
     }
-    hipLaunchKernelGGL(decode_topk_kernel, dim3(grp_start ? n_grp : 1), dim3(1024), lds, (hipStream_t)stream, cls, reg, R, num_classes, max_num, npow2,
-                       post_center_range[0], post_center_range[1], post_center_range[2], post_center_range[3], post_center_range[4],
-                       post_center_range[5], boxes, scores, labels, bbox_index, count_out, topk_index_dbg, grp_start, payload);
     MV2D_LAUNCH_CHECK();
     return MV2D_OK;
 }

@@ -1075,12 +1075,17 @@ struct HeadsX3Params {
     const float* r4; const float* rb4;
     const float* ref; float* cls; float* reg;
     int M, L; float eps; float pc0, pc1, pc2, pd0, pd1, pd2, dt; const float* dt_rows;
+    int NC;                       // classes: w6 [L,NC,256], b6 [L,NC], cls [L,M,NC]
 };
 
 // RT row tiles (16 rows each) per block share one load of the weight fragments: with many rows (a batch of samples) the kernel is
 // bound by the L2 -> CU traffic of the weights (0.5 MB per block), not by the matrix pipe.
-template <int RT>
+// CT = 16-column tiles of the class output layer (NC <= 16 CT): wave w finishes row tile w % RT and class tile w / RT, so the waves that
+// sit idle behind the last 256x256 linear at CT = 1 carry the extra class tiles (RT * CT <= 16: up to 64 classes at RT = 4).
+// NCF = the class count as a compile-time constant (the 10-class launch: the instruction stream of the 10-class-only kernel), 0 = p.NC.
+template <int RT, int CT, int NCF>
 __global__ __launch_bounds__(1024) void heads_fused_x3_kernel(HeadsX3Params p) {
+    static_assert(RT * CT <= 16, "one wave per (row tile, class tile)");
     __shared__ __attribute__((aligned(16))) unsigned char ah[RT * 16 * 512], al[RT * 16 * 512];
     __shared__ __attribute__((aligned(16))) float tb[RT * 16 * C];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fr = lane & 15, fg = lane >> 4;
@@ -1153,19 +1158,23 @@ __global__ __launch_bounds__(1024) void heads_fused_x3_kernel(HeadsX3Params p) {
         *reinterpret_cast<float4*>(trow + t * 16 * C) = make_float4(relu_f(v.x), relu_f(v.y), relu_f(v.z), relu_f(v.w));
     }
     __syncthreads();
-    if (wave >= RT) return;
-    const int m0 = mb + 16 * wave;                                      // wave t finishes row tile t
+    // the reg branch has one column tile (10 wide), the cls branch CT
+    if (wave >= (branch == 0 ? CT * RT : RT)) return;
+    const int rt = CT == 1 ? wave : wave % RT, ct = CT == 1 ? 0 : wave / RT;
+    const int m0 = mb + 16 * rt;                                        // wave w finishes row tile w % RT
     if (m0 >= p.M) return;
-    const float* tbt = tb + wave * 16 * C;
-    // ---- final Linear(256 -> 10): one 16x16 tile, weight rows >= 10 clamped and masked
-    const float* wlast = branch == 0 ? p.w6 + (long long)l * 10 * C : p.r4 + (long long)l * 10 * C;
-    const float* blast = branch == 0 ? p.b6 + l * 10 : p.rb4 + l * 10;
+    const float* tbt = tb + rt * 16 * C;
+    // ---- final Linear(256 -> NC | 10): 16x16 tile ct, weight rows >= NC clamped and masked
+    const int nout = branch == 0 ? (NCF ? NCF : p.NC) : 10;
+    const float* wlast = branch == 0 ? p.w6 + (long long)l * nout * C : p.r4 + (long long)l * 10 * C;
+    const float* blast = branch == 0 ? p.b6 + l * nout : p.rb4 + l * 10;
     float* outp = branch == 0 ? p.cls : p.reg;
+    const int n = 16 * ct + fr;                                         // this lane's output column
     Frag f;
-    load_w(f, wlast, C, fr, 10, fg);
+    load_w(f, wlast, C, n, nout, fg);
     const f32x4_t o = tile_mma(tbt, f, fr, fg);
-    if (fr >= 10) return;
-    const float b = blast[fr];
+    if (n >= nout) return;
+    const float b = blast[n];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int m = m0 + 4 * fg + r;
@@ -1184,7 +1193,7 @@ __global__ __launch_bounds__(1024) void heads_fused_x3_kernel(HeadsX3Params p) {
                 if (dt != 0.f) v = v / dt;
             }
         }
-        outp[((long long)l * p.M + m) * 10 + fr] = v;
+        outp[((long long)l * p.M + m) * nout + n] = v;
     }
 }
 
@@ -1320,11 +1329,13 @@ extern "C" int mv2d_heads_fused(const float* outs, const float* const* cls_w, co
     return MV2D_OK;
 }
 
-extern "C" int mv2d_heads_fused_x3(const float* outs, const void* const* cls_w, const void* const* reg_w, const float* ref, float* cls, float* reg,
-                                   int M, int L, float eps, const float* pc_range, float dt, const float* dt_rows, void* stream) {
+extern "C" int mv2d_heads_fused_x3_nc(const float* outs, const void* const* cls_w, const void* const* reg_w, const float* ref, float* cls,
+                                      float* reg, int M, int L, int num_classes, float eps, const float* pc_range, float dt, const float* dt_rows,
+                                      void* stream) {
     // cls_w: {w0_hi,w0_lo,b0,lnw1,lnb1,w3_hi,w3_lo,b3,lnw4,lnb4,w6,b6}; reg_w: {w0_hi,w0_lo,b0,w2_hi,w2_lo,b2,w4,b4} device pointers,
     // every tensor stacked over the L layers; the *_hi/_lo matrices are per-layer mv2d_split_bf16x2 + mv2d_pack_wfrag_bf16 copies
     MV2D_CHECK_ARG(outs && cls_w && reg_w && ref && cls && reg && pc_range && L > 0, "mv2d_heads_fused_x3: null pointer");
+    MV2D_CHECK_ARG(num_classes >= 1 && num_classes <= 64, "mv2d_heads_fused_x3: num_classes must be in [1, 64]");
     for (int i = 0; i < 12; ++i) MV2D_CHECK_ARG(cls_w[i] != nullptr, "mv2d_heads_fused_x3: null cls weight");
     for (int i = 0; i < 8; ++i) MV2D_CHECK_ARG(reg_w[i] != nullptr, "mv2d_heads_fused_x3: null reg weight");
     if (M == 0) return MV2D_OK;
@@ -1333,12 +1344,29 @@ extern "C" int mv2d_heads_fused_x3(const float* outs, const void* const* cls_w, 
                     (Fp)cls_w[9], (Fp)cls_w[10], (Fp)cls_w[11],
                     (U)reg_w[0], (U)reg_w[1], (Fp)reg_w[2], (U)reg_w[3], (U)reg_w[4], (Fp)reg_w[5], (Fp)reg_w[6], (Fp)reg_w[7],
                     ref, cls, reg, M, L, eps,
-                    pc_range[0], pc_range[1], pc_range[2], pc_range[3] - pc_range[0], pc_range[4] - pc_range[1], pc_range[5] - pc_range[2], dt, dt_rows};
-    if (M <= 512) hipLaunchKernelGGL(heads_fused_x3_kernel<1>, dim3(cdiv(M, 16), L, 2), dim3(1024), 0, (hipStream_t)stream, p);
-    else if (M <= 1024) hipLaunchKernelGGL(heads_fused_x3_kernel<2>, dim3(cdiv(M, 32), L, 2), dim3(1024), 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL(heads_fused_x3_kernel<4>, dim3(cdiv(M, 64), L, 2), dim3(1024), 0, (hipStream_t)stream, p);
+                    pc_range[0], pc_range[1], pc_range[2], pc_range[3] - pc_range[0], pc_range[4] - pc_range[1], pc_range[5] - pc_range[2], dt, dt_rows,
+                    num_classes};
+    const int ct = num_classes == 10 ? 0 : (num_classes + 15) / 16;    // class column tiles (0: the 10-class instance)
+    const hipStream_t st = (hipStream_t)stream;
+#define MV2D_HEADS_X3(RT)                                                                                                             \
+    switch (ct) {                                                                                                                     \
+        case 0: hipLaunchKernelGGL((heads_fused_x3_kernel<RT, 1, 10>), dim3(cdiv(M, 16 * RT), L, 2), dim3(1024), 0, st, p); break;    \
+        case 1: hipLaunchKernelGGL((heads_fused_x3_kernel<RT, 1, 0>), dim3(cdiv(M, 16 * RT), L, 2), dim3(1024), 0, st, p); break;     \
+        case 2: hipLaunchKernelGGL((heads_fused_x3_kernel<RT, 2, 0>), dim3(cdiv(M, 16 * RT), L, 2), dim3(1024), 0, st, p); break;     \
+        case 3: hipLaunchKernelGGL((heads_fused_x3_kernel<RT, 3, 0>), dim3(cdiv(M, 16 * RT), L, 2), dim3(1024), 0, st, p); break;     \
+        default: hipLaunchKernelGGL((heads_fused_x3_kernel<RT, 4, 0>), dim3(cdiv(M, 16 * RT), L, 2), dim3(1024), 0, st, p); break;    \
+    }
+    if (M <= 512) { MV2D_HEADS_X3(1) }
+    else if (M <= 1024) { MV2D_HEADS_X3(2) }
+    else { MV2D_HEADS_X3(4) }
+#undef MV2D_HEADS_X3
     MV2D_LAUNCH_CHECK();
     return MV2D_OK;
+}
+
+extern "C" int mv2d_heads_fused_x3(const float* outs, const void* const* cls_w, const void* const* reg_w, const float* ref, float* cls, float* reg,
+                                   int M, int L, float eps, const float* pc_range, float dt, const float* dt_rows, void* stream) {
+    return mv2d_heads_fused_x3_nc(outs, cls_w, reg_w, ref, cls, reg, M, L, 10, eps, pc_range, dt, dt_rows, stream);
 }
 
 extern "C" int mv2d_linear_x3_ex(const float* A, const float* A2, int n_split, int lda, const void* Whi, const void* Wlo, const float* bias,

@@ -52,7 +52,8 @@ class HeadEngine:
         self.expand = float(expand_stride if expand_stride is not None else (0 if kind == 'S' else 2))
         self.max_num = max_num
         self.num_classes = int(num_classes)
-        assert self.num_classes == 10, 'the fused prediction-branch kernels (mv2d_heads_fused*) are built for 10 classes'
+        if not 1 <= self.num_classes <= 64:       # the class output layer of mv2d_heads_fused_x3_nc: up to 4 column tiles of 16
+            raise ValueError(f'HeadEngine: num_classes must be in [1, 64], got {num_classes}')
         self.depth_num = depth_num
         self.stride = stride
         self.iou_thr, self.ratio = iou_thr, ratio
@@ -160,6 +161,9 @@ class HeadEngine:
     # ------------------------------------------------------------------------------------------ weights
     def load_state(self, sd):
         d, L = self.dev, self.L
+        nc = int(tuple(sd['bbox_head.cls_branches.0.6.weight'].shape)[0])
+        if nc != self.num_classes:
+            raise ValueError(f'HeadEngine: the state dict has {nc} classes (cls_branches.*.6.weight), num_classes={self.num_classes}')
         self._weights_version = getattr(self, '_weights_version', 0) + 1
         g = lambda k: _t(sd[k], d, F32)
         k16 = ops.pack_key16                                                             # fp32 [N,K] -> key16, fragment-major (key-side kernels)
@@ -262,12 +266,12 @@ class HeadEngine:
         (kernels index [*, R, *] tensors densely) plus its own hipGraph; staging buffers, calibration cache and the stream-order
         guard are shared by all R of a bucket."""
         Vg = V if Vg is None else Vg                     # views per sample; V = all views of the batch
-        key = (V, h, w, R, Vg)
+        key = (V, h, w, R, Vg, self.num_classes)
         ws = self._ws.get(key)
         if ws is not None:
             return ws
         cap = max(64, -(-R // 32) * 32)
-        bkey = (V, h, w, cap, Vg)
+        bkey = (V, h, w, cap, Vg, self.num_classes)
         base = self._ws_base.get(bkey)
         if base is None:
             store = []
@@ -392,7 +396,7 @@ class HeadEngine:
         ws['zero_rows'] = z((R, C))                              # never written
         ws['sa0_ctx'] = e((R, C))                                # rows of the layer-0 self-attention value bias (fold_sa0), filled per weights version
         ws['qkv'] = e((R, 3 * C)); ws['parts'] = e((2048 // 64, R, C)); ws['outs'] = e((L, R, C))
-        ws['cls'] = e((L, R, 10)); ws['reg'] = e((L, R, 10))
+        ws['cls'] = e((L, R, self.num_classes)); ws['reg'] = e((L, R, 10))
         ws['boxes'] = z((B, self.max_num, 9)); ws['scores'] = z((B, self.max_num))
         ws['labels'] = z((B, self.max_num), torch.int64); ws['bbox_index'] = z((B, self.max_num), torch.int64); ws['count'] = z(B, torch.int32)
         return ws
@@ -523,9 +527,13 @@ class HeadEngine:
         assert max(counts) <= 1024, 'at most 1024 RoIs per view (mv2d_box_correlation)'
         sc['max_per_view'] = max(counts)
         # top-k decode: the kernel sizes its candidate buffer by a power of two >= rows * classes; the launch gets the largest row count
-        # of that size class, so that frames with different RoI counts share the launch configuration (and the graph)
+        # of that size class, so that frames with different RoI counts share the launch configuration (and the graph).  Above 16384
+        # candidates per sample the decode streams its keys from cls (mv2d_decode_topk), up to 65536 = 1024 queries x 64 classes
+        n_max = max(grp[b + 1] - grp[b] for b in range(B)) * self.num_classes
+        if n_max > 65536:
+            raise ValueError(f'mv2d engine: {n_max} decode candidates in one sample (queries x num_classes), at most 65536')
         n_pow2 = 1024
-        while n_pow2 < max(grp[b + 1] - grp[b] for b in range(B)) * self.num_classes:
+        while n_pow2 < n_max:
             n_pow2 <<= 1
         sc['max_rows'] = min(n_pow2 // self.num_classes, cap)
         sc['cap'] = cap
@@ -846,10 +854,10 @@ class HeadEngine:
             # cross_attention_head.py:202-242 / RH/mv2d_head.py:170-194); cls / reg of the other layers are then not written
             ll = self.L - 1
             ops.heads_fused_x3(ws['outs'][ll:], self.cls_ptrs_x3_last, self.reg_ptrs_x3_last, ws['ref'], ws['cls'][ll:], ws['reg'][ll:], R, 1,
-                               self.pc_range_h, dt, dt_rows=dt_rows)
+                               self.pc_range_h, dt, dt_rows=dt_rows, num_classes=self.num_classes)
         else:
             ops.heads_fused_x3(ws['outs'], self.cls_ptrs_x3, self.reg_ptrs_x3, ws['ref'], ws['cls'], ws['reg'], R, self.L, self.pc_range_h, dt,
-                               dt_rows=dt_rows)
+                               dt_rows=dt_rows, num_classes=self.num_classes)
 
     def _result(self, ws, R, keep_stages=False, batch=False):
         sel = (lambda t: t) if batch else (lambda t: t[0])
@@ -879,7 +887,7 @@ class HeadEngine:
     def run_batch(self, feats, proposals_list, metas_list, keep_stages=False, use_graph=False, payload=None):
         """Several samples through ONE sequence of launches (the reference runs one sample per call): feats = list of [V,256,h,w]
         maps (or one stacked [B*V,256,h,w] tensor), proposals_list / metas_list = one entry per sample.  Outputs: cls / reg
-        [L,R_total,10] with the samples' queries concatenated (out['grp_start']), boxes [B,max_num,9], scores, labels, count [B]."""
+        [L,R_total,num_classes] / [L,R_total,10] with the samples' queries concatenated (out['grp_start']), boxes [B,max_num,9], scores, labels, count [B]."""
         return self._run(feats, proposals_list, metas_list, keep_stages, use_graph, batch=True, payload=payload)
 
     def _run(self, feats, proposals_list, metas_list, keep_stages, use_graph, batch, payload=None):
@@ -926,7 +934,7 @@ class HeadEngine:
             return dict(self._result(ws, R, keep_stages, batch), dt=sc['dt'])
         # the graph bakes in the input pointers (the producer's output buffers are static under graph replay) and the
         # frame scalars; anything else changing (RoI boxes, calibration tables, feature values) is data.
-        gkey = (ptrs, 0 if payload is None else payload.data_ptr(), sc['pad_h'], sc['pad_w'], sc['max_rows'], self._weights_version, self._stage_outputs, self.last_stage_heads,
+        gkey = (ptrs, 0 if payload is None else payload.data_ptr(), sc['pad_h'], sc['pad_w'], sc['max_rows'], self.num_classes, self._weights_version, self._stage_outputs, self.last_stage_heads,
                 self.xattn_waves, self.fuse_maps, self.fuse_xattn, self.group_xattn, self.lo8_rows, self.pe_at_positions, self.pe_rows_in_waves, self.fold_sa0, self.masked_transpose, self.keep_sine_rows, self.force_nc, self.q_order,
                 self.fork_qg, self.exact_skip, self.ablate_zero_lo, self.stop_before_decoder)   # load_state() re-allocates the weights; every route option of __init__ is in the key
         graphs = ws.setdefault('graphs', {})             # one graph per (input buffers, frame scalars): a producer that alternates between
@@ -961,7 +969,7 @@ class HeadEngine:
         over [denoising queries | the sample's queries] with the self-attention mask of ``prepare_for_dn`` evaluated in the kernel and the
         denoising rows attending to every key some RoI can see (RH/mv2d_t_head.py:90-98: ``cross_attn_mask.all(dim=0)``;
         RH/mv2d_s_head.py:158-171).  ``dn_ref`` [pad,3] normalised reference points of the denoising queries (``train.prepare_for_dn``),
-        ``dn_single`` rows per group.  Returns (all_cls [L,pad+R,10], all_reg [L,pad+R,10]); the denoising rows' velocities are not divided
+        ``dn_single`` rows per group.  Returns (all_cls [L,pad+R,num_classes], all_reg [L,pad+R,10]); the denoising rows' velocities are not divided
         by the frame time step (the reference splits them off before ``_bbox_forward`` does that, RH/mv2d_t_head.py:104-110,132-137).
         Without ``dn_ref`` the inference outputs of all layers are returned (use_denoise=False).  Forward only; synchronises."""
         ws, R = out['ws'], out['R']
@@ -1019,7 +1027,7 @@ class HeadEngine:
                    row_ptr=torch.cat([torch.arange(pad, device=d, dtype=torch.int32) * nk, row_ptr + pad * nk]),
                    col_idx=torch.cat([keys.repeat(pad), col]).contiguous(),
                    ref=torch.cat([dn_ref.to(F32), ws['ref'][:R]]).contiguous(), qpos=torch.cat([qdn, ws['qpos'][:R]]).contiguous(),
-                   zero_rows=torch.zeros(T, C, device=d), qkv=e(T, 3 * C), parts=e(2048 // 64, T, C), outs=e(L, T, C), cls=e(L, T, 10),
+                   zero_rows=torch.zeros(T, C, device=d), qkv=e(T, 3 * C), parts=e(2048 // 64, T, C), outs=e(L, T, C), cls=e(L, T, self.num_classes),
                    reg=e(L, T, 10), dt_rows=torch.cat([torch.zeros(pad, device=d), torch.full((R,), float(out.get('dt', 0.0)), device=d)]))
         for n in ('x', 'x1', 'x2', 'ctx', 'q'):
             tws[n] = e(T, C)

@@ -312,10 +312,18 @@ def split_rows(a, b=None, hi=None, lo=None, m_dev=None, M=None):
     return hi, lo
 
 
-def heads_fused_x3(outs, cls_ptrs, reg_ptrs, ref, cls, reg, M, L, pc_range_host, dt=0.0, eps=1e-5, dt_rows=None):
-    """heads_fused with the 256x256 linears in bf16x3; cls_ptrs / reg_ptrs as documented in include/mv2d_hip.h (pack_x3_stack)."""
-    check(_lib.load().mv2d_heads_fused_x3(_p(outs), cls_ptrs, reg_ptrs, _p(ref), _p(cls), _p(reg), M, L, float(eps),
-                                          pc_range_host.data_ptr(), float(dt), _p(dt_rows), _stream()), 'mv2d_heads_fused_x3')
+def heads_fused_x3(outs, cls_ptrs, reg_ptrs, ref, cls, reg, M, L, pc_range_host, dt=0.0, eps=1e-5, dt_rows=None, num_classes=10):
+    """heads_fused with the 256x256 linears in bf16x3; cls_ptrs / reg_ptrs as documented in include/mv2d_hip.h (pack_x3_stack).
+    num_classes (1..64): rows of the class output layer, cls [L,M,num_classes]; 10 runs the 10-class entry mv2d_heads_fused_x3."""
+    num_classes = int(num_classes)
+    if not 1 <= num_classes <= 64:
+        raise ValueError(f'heads_fused_x3: num_classes must be in [1, 64], got {num_classes}')
+    if num_classes == 10:
+        check(_lib.load().mv2d_heads_fused_x3(_p(outs), cls_ptrs, reg_ptrs, _p(ref), _p(cls), _p(reg), M, L, float(eps),
+                                              pc_range_host.data_ptr(), float(dt), _p(dt_rows), _stream()), 'mv2d_heads_fused_x3')
+    else:
+        check(_lib.load().mv2d_heads_fused_x3_nc(_p(outs), cls_ptrs, reg_ptrs, _p(ref), _p(cls), _p(reg), M, L, num_classes, float(eps),
+                                                 pc_range_host.data_ptr(), float(dt), _p(dt_rows), _stream()), 'mv2d_heads_fused_x3_nc')
 
 
 def pack_x3_stack(W):

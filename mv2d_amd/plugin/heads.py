@@ -34,8 +34,15 @@ class CrossAttentionBoxHead(nn.Module):
                                  pc_range=[-51.2, -51.2, -5.0, 51.2, 51.2, 3.0], max_num=100, num_classes=10),
                  sync_cls_avg_factor=False, train_cfg=None, test_cfg=None, **kwargs):
         super().__init__()
-        assert not use_reg_layer and not pre_embed and embed_dims == C and num_reg_fcs == 2 and num_classes == 10, \
+        assert not use_reg_layer and not pre_embed and embed_dims == C and num_reg_fcs == 2, \
             'kernel path implements the shipped head configuration'
+        # the class output layer of the fused prediction branches (mv2d_heads_fused_x3_nc) holds up to 4 column tiles of 16 classes
+        if not 1 <= int(num_classes) <= 64:
+            raise ValueError(f'CrossAttentionBoxHead: num_classes must be in [1, 64] (the fused heads kernel), got {num_classes}')
+        coder_nc = (bbox_coder or {}).get('num_classes', 10)
+        if int(coder_nc) != int(num_classes):
+            raise ValueError(f'CrossAttentionBoxHead: bbox_coder.num_classes={coder_nc} differs from num_classes={num_classes} '
+                             '(the decode would read the wrong labels)')
         self.loss_cls = build_loss(loss_cls)
         self.loss_bbox = build_loss(loss_bbox)
         self.transformer = build_transformer(transformer)
@@ -76,7 +83,7 @@ class CrossAttentionBoxHead(nn.Module):
 
     def forward(self, reference_points, x, masks, pos_embed, attn_mask=None, cross_attn_mask=None, force_fp32=False,
                 query_embeds=None, return_query_feats=False, **kwargs):
-        """reference_points [bs,Q,3], x / pos_embed [bs,n,c,h,w], masks [bs,n,h,w] -> (all_cls_scores, all_bbox_preds) [L,bs,Q,10].
+        """reference_points [bs,Q,3], x / pos_embed [bs,n,c,h,w], masks [bs,n,h,w] -> (all_cls_scores [L,bs,Q,num_classes], all_bbox_preds [L,bs,Q,10]).
         Stray kwargs (e.g. ``pe=(module, x, metas)`` of RH/mv2d_head.py:172) are accepted and ignored like in the reference."""
         assert not self.training, 'inference kernels only (SURVEY.md §8 f3)'
         if not self.pre_embed:
@@ -94,8 +101,9 @@ class CrossAttentionBoxHead(nn.Module):
         h2 = ops.row_ln(h1.view(L * M, C), ln=(st(1, 'weight'), st(1, 'bias')), relu=True, rows_per_group=M).view(L, M, C)
         h1 = ops.gemm_f32(h2, st(3, 'weight'), st(3, 'bias'), M=M, lda=C, ldc=C, **gk)
         h2 = ops.row_ln(h1.view(L * M, C), ln=(st(4, 'weight'), st(4, 'bias')), relu=True, rows_per_group=M).view(L, M, C)
-        cls = torch.empty((L, M, 10), device=dev)
-        ops.gemm_f32(h2, st(6, 'weight'), st(6, 'bias'), out=cls, M=M, lda=C, ldc=10, groups=L, a_gs=M * C, c_gs=M * 10)
+        NC = self.num_classes
+        cls = torch.empty((L, M, NC), device=dev)
+        ops.gemm_f32(h2, st(6, 'weight'), st(6, 'bias'), out=cls, M=M, lda=C, ldc=NC, groups=L, a_gs=M * C, c_gs=M * NC)
         self._cur = self.reg_branches
         r1 = ops.gemm_f32(od, st(0, 'weight'), st(0, 'bias'), act=1, M=M, lda=C, ldc=C, **gk)
         r2 = ops.gemm_f32(r1, st(2, 'weight'), st(2, 'bias'), act=1, M=M, lda=C, ldc=C, **gk)
@@ -103,7 +111,7 @@ class CrossAttentionBoxHead(nn.Module):
         ops.gemm_f32(r2, st(4, 'weight'), st(4, 'bias'), out=reg, M=M, lda=C, ldc=10, groups=L, a_gs=M * C, c_gs=M * 10)
         del self._cur
         ops.finalize_reg(reg, reference_points.reshape(M, 3).float().contiguous(), L, M, torch.tensor(self.pc_range, dtype=torch.float32), 0.0)
-        all_cls_scores, all_bbox_preds = cls.view(L, bs, Q, 10), reg.view(L, bs, Q, 10)
+        all_cls_scores, all_bbox_preds = cls.view(L, bs, Q, NC), reg.view(L, bs, Q, 10)
         if return_query_feats:
             return all_cls_scores, all_bbox_preds, outs_dec[-1]
         return all_cls_scores, all_bbox_preds

@@ -108,8 +108,9 @@ def _ln(g, n):
     return w, b
 
 
-def make_head_state(seed=0, num_layers=NUM_LAYERS):
+def make_head_state(seed=0, num_layers=NUM_LAYERS, num_classes=NUM_CLASSES):
     """OrderedDict[str, np.ndarray] with the reference ``roi_head.*`` state-dict key layout.
+    ``num_classes`` sizes the class output layers ``cls_branches.{l}.6`` (the default draws exactly the 10-class stream).
 
     Xavier-uniform matrices like PETRTransformer.init_weights
     (mmdet3d_plugin/models/utils/petr_transformer.py:65-71); biases / LayerNorm affine are small
@@ -147,9 +148,9 @@ def make_head_state(seed=0, num_layers=NUM_LAYERS):
         sd[p + '1.weight'], sd[p + '1.bias'] = _ln(g, C)
         sd[p + '3.weight'] = _xavier(g, (C, C)); sd[p + '3.bias'] = _bias(g, C)
         sd[p + '4.weight'], sd[p + '4.bias'] = _ln(g, C)
-        sd[p + '6.weight'] = _xavier(g, (NUM_CLASSES, C))
+        sd[p + '6.weight'] = _xavier(g, (num_classes, C))
         # bias_init_with_prob(0.01) (cross_attention_head.py:193-197) plus a per-class spread
-        sd[p + '6.bias'] = (np.full(NUM_CLASSES, -math.log((1 - 0.01) / 0.01), np.float32) + _bias(g, NUM_CLASSES, 0.5))
+        sd[p + '6.bias'] = (np.full(num_classes, -math.log((1 - 0.01) / 0.01), np.float32) + _bias(g, num_classes, 0.5))
     for l in range(num_layers):
         p = f'bbox_head.reg_branches.{l}.'
         sd[p + '0.weight'] = _xavier(g, (C, C)); sd[p + '0.bias'] = _bias(g, C)
