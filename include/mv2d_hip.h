@@ -141,6 +141,11 @@ int mv2d_qg_conv_pool(const void* roi_feat, const void* W, const float* bias, fl
  * key16 hi / lo copies of the [256, 2304] matrix (mv2d_f32_to_key16 + mv2d_pack_wfrag_bf16); products a_lo w_hi + a_hi w_lo + a_hi w_hi. */
 int mv2d_qg_conv_pool_x3(const void* roi_feat_hi, const void* roi_feat_lo, const void* W_hi, const void* W_lo, const float* bias, float* out,
                          int ld_out, int R, void* stream);
+/* Both for an s x s RoI, 1 <= roi_size <= 14 (RoI cells [R, s*s, 256], conv3x3 + ReLU + AvgPool2d(s)): s = 7 runs the two entries above;
+ * other sizes one block per RoI over chunks of 64 output cells. */
+int mv2d_qg_conv_pool_s(const void* roi_feat, const void* W, const float* bias, float* out, int ld_out, int R, int roi_size, void* stream);
+int mv2d_qg_conv_pool_x3_s(const void* roi_feat_hi, const void* roi_feat_lo, const void* W_hi, const void* W_lo, const float* bias, float* out,
+                           int ld_out, int R, int roi_size, void* stream);
 
 /* The same chain in split precision (bf16x3, ~1e-5 relative): Wo / Wq as bf16 hi/lo pairs (mv2d_split_bf16x2), each in the
  * fragment-major order of mv2d_pack_wfrag_bf16. */
@@ -439,6 +444,10 @@ int mv2d_roi_align(const float* map0, const float* map1, const float* rois, void
 int mv2d_roi_align_ex(const float* map0, const float* map1, const float* rois, void* out0, void* out1, float* out0_f32, float* out1_f32,
                       int R, int H, int W, int channels, float spatial_scale, int sampling_ratio, const int* map1_index, int out1_is_sum,
                       void* out0_lo, void* out1_lo, void* out0_lo8, void* out1_lo8, int* lo8_flag, void* stream);
+/* mv2d_roi_align_ex for roi_size x roi_size bins, 1 <= roi_size <= 14: every output [R, roi_size^2, 256]; mv2d_roi_align_ex is this entry with 7. */
+int mv2d_roi_align_s(const float* map0, const float* map1, const float* rois, void* out0, void* out1, float* out0_f32, float* out1_f32,
+                     int R, int H, int W, int channels, float spatial_scale, int sampling_ratio, const int* map1_index, int out1_is_sum,
+                     void* out0_lo, void* out1_lo, void* out0_lo8, void* out1_lo8, int* lo8_flag, int roi_size, void* stream);
 
 /* BoxCorrelation.epipolar_in_box, 'topk_matched:k:thr:ratio' (RH/utils/box_correlation.py:196-398).
  * V = views per sample; view_start[n_views+1]: first RoI of each view; trans [n_views,V,16] fp64 = lidar2img[b] @ inv(lidar2img[a])
@@ -483,6 +492,13 @@ int mv2d_csr_from_corr(const int* match, int* row_ptr, int* col_idx, int* nnz_ou
 int mv2d_roi_positions_csr(const float* rois, const unsigned char* pad_mask, unsigned char* roi_mask, int* rect, int* pos2s, int* s2pos,
                            int* S_out, int R, int V, int h, int w, float stride, float expand_stride, const int* match, int* row_ptr,
                            int* col_idx, int* nnz_out, int Vg, int topk, const int* grp_start, int n_samples, int* order, int* order_flags, void* stream);
+/* The two entries above for an s x s RoIAlign, 1 <= roi_size <= 14: rows r*s*s+cell, s*s consecutive cells per listed RoI, and (expand_stride < 0)
+ * the cells the taps of the s x s RoIAlign touch.  The entries above are these with roi_size = 7. */
+int mv2d_csr_from_corr_s(const int* match, int* row_ptr, int* col_idx, int* nnz_out, int R, int V, int topk, int roi_size, void* stream);
+int mv2d_roi_positions_csr_s(const float* rois, const unsigned char* pad_mask, unsigned char* roi_mask, int* rect, int* pos2s, int* s2pos,
+                             int* S_out, int R, int V, int h, int w, float stride, float expand_stride, const int* match, int* row_ptr,
+                             int* col_idx, int* nnz_out, int Vg, int topk, const int* grp_start, int n_samples, int* order, int* order_flags,
+                             int roi_size, void* stream);
 
 /* Frustum rows of the index-exact route's PE block alone: out [S, 3 depth_num] fp32 = float(inverse_sigmoid(normalised 3-D point of every depth bin)),
  * computed in fp64 like the reference (MU/pe.py:96-131) at the positions s2pos[0 .. *S_dev); position_range = 6 doubles on the HOST.  Replaces the
@@ -677,6 +693,9 @@ int mv2d_lsap_layers(const float* cost, int L, int R, int G, int* match, int thr
  * that the convolution is one product: x [R,49,256] -> cols [R*49, 2304], column order (tap = 3 ky + kx, channel); and its gradient. */
 int mv2d_im2col3x3(const float* x, float* cols, int R, void* stream);
 int mv2d_col2im3x3(const float* dcols, float* dx, int R, void* stream);
+/* The same pair for s x s cells, 1 <= roi_size <= 14: x [R, s*s, 256] <-> cols [R*s*s, 2304]; s = 7 runs the entries above. */
+int mv2d_im2col3x3_s(const float* x, float* cols, int R, int roi_size, void* stream);
+int mv2d_col2im3x3_s(const float* dcols, float* dx, int R, int roi_size, void* stream);
 
 /* center2lidar + normalisation of the reference points for training (RH/utils/query_generator.py:333-341, RH/mv2d_s_head.py:146-152):
  * c [R,3] = (u, v, depth), minv [R,16] -> ref [R,3] = ((minv (u d, v d, d, 1))[:3] - low) / range; the backward returns d c.  pc_range: 6 HOST floats. */
@@ -703,6 +722,9 @@ int mv2d_dense_attn_bwd_parts(const float* q, const float* k, const float* v, co
  * index (may be null): position -> row of a compacted map, negative = no row (as map1_index of the forward). */
 int mv2d_roi_align_bwd(const float* grad_out, const float* rois, float* grad_map, const int* index, int R, int H, int W, int channels,
                        float spatial_scale, int sampling_ratio, void* stream);
+/* The same for roi_size x roi_size bins (grad_out [R][roi_size^2][256]), 1 <= roi_size <= 14; mv2d_roi_align_bwd is this entry with 7. */
+int mv2d_roi_align_bwd_s(const float* grad_out, const float* rois, float* grad_map, const int* index, int R, int H, int W, int channels,
+                         float spatial_scale, int sampling_ratio, int roi_size, void* stream);
 
 #ifdef __cplusplus
 }

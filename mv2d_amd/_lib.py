@@ -46,6 +46,8 @@ SIGNATURES = {
     'mv2d_split_rows_key16': (I, [P, P, P, P, I, I, P, P]),
     'mv2d_qg_conv_pool': (I, [P, P, P, P, I, I, P]),
     'mv2d_qg_conv_pool_x3': (I, [P, P, P, P, P, P, I, I, P]),
+    'mv2d_qg_conv_pool_s': (I, [P, P, P, P, I, I, I, P]),
+    'mv2d_qg_conv_pool_x3_s': (I, [P, P, P, P, P, P, I, I, I, P]),
     'mv2d_pack_wfrag_bf16': (I, [P, P, I, I, P]),
     'mv2d_gemm_f32': (I, [P, P, I, P, P, I, I, I, I, I, I, I, F, F, P, I, I, LL, I, LL, LL, LL, LL, P]),
     'mv2d_attn_out_fused': (I, [P, P, P, P, P, P, P, P, P, P, F, P, I, F, P]),
@@ -100,12 +102,15 @@ SIGNATURES = {
     'mv2d_posemb3d': (I, [P, P, P, I, P]),
     'mv2d_roi_align': (I, [P, P, P, P, P, P, P, I, I, I, I, F, I, P, I, P]),
     'mv2d_roi_align_ex': (I, [P, P, P, P, P, P, P, I, I, I, I, F, I, P, I, P, P, P, P, P, P]),
+    'mv2d_roi_align_s': (I, [P, P, P, P, P, P, P, I, I, I, I, F, I, P, I, P, P, P, P, P, I, P]),
     'mv2d_box_correlation': (I, [P, P, P, P, P, P, I, I, I, I, I, I, I, F, F, F, I, P]),
     'mv2d_csr_workspace_bytes': (LL, [I, I, I, I]),
     'mv2d_mask_compact': (I, [P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, F, F, I, P]),
     'mv2d_roi_positions': (I, [P, P, P, P, P, P, P, I, I, I, I, F, F, P]),
     'mv2d_csr_from_corr': (I, [P, P, P, P, I, I, I, P]),
+    'mv2d_csr_from_corr_s': (I, [P, P, P, P, I, I, I, I, P]),
     'mv2d_roi_positions_csr': (I, [P, P, P, P, P, P, P, I, I, I, I, F, F, P, P, P, P, I, I, P, I, P, P, P]),
+    'mv2d_roi_positions_csr_s': (I, [P, P, P, P, P, P, P, I, I, I, I, F, F, P, P, P, P, I, I, P, I, P, P, I, P]),
     'mv2d_frame_geometry': (I, [P, P, P, P, P, I, P, F, F, F, P, P, P, P, P, I, I, I, I, I, I, I, F, F, F, I, P, LL, P]),
     'mv2d_pe_inputs': (I, [P, P, I, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, P, P]),
     'mv2d_pe_frustum_f32': (I, [P, P, I, P, P, P, P, P, I, I, I, I, P, P]),
@@ -113,6 +118,7 @@ SIGNATURES = {
     'mv2d_nms_bev': (I, [P, P, P, P, F, P, I, I, P]),
     'mv2d_pack_detections': (I, [P, P, P, P, P, I, I, I, P]),
     'mv2d_roi_align_bwd': (I, [P, P, P, P, I, I, I, I, F, I, P]),
+    'mv2d_roi_align_bwd_s': (I, [P, P, P, P, I, I, I, I, F, I, I, P]),
     'mv2d_colsum_scratch_rows': (I, [I]),
     'mv2d_colsum': (I, [P, LL, I, I, P, P, P]),
     'mv2d_gemm_f32x3_ws_bytes': (LL, [I, I, I]),
@@ -131,6 +137,8 @@ SIGNATURES = {
     'mv2d_box_code_bwd': (I, [P, P, P, P, P, I, I, I, F, P, P]),
     'mv2d_im2col3x3': (I, [P, P, I, P]),
     'mv2d_col2im3x3': (I, [P, P, I, P]),
+    'mv2d_im2col3x3_s': (I, [P, P, I, I, P]),
+    'mv2d_col2im3x3_s': (I, [P, P, I, I, P]),
     'mv2d_center2lidar_fwd': (I, [P, P, P, I, P, P]),
     'mv2d_center2lidar_bwd': (I, [P, P, P, P, I, P, P]),
     'mv2d_dense_attn_ws_bytes': (LL, [I, I, I]),

@@ -458,24 +458,31 @@ class DenseHeadsAttnFn(torch.autograd.Function):
 
 
 class Im2Col3x3Fn(torch.autograd.Function):
-    """x [R,49,256] (7 x 7 cells) -> the unfolded input [R*49, 2304] of a 3 x 3 convolution with padding 1, column order (tap, channel):
-    ``mv2d_im2col3x3`` / ``mv2d_col2im3x3`` -- one launch per direction."""
+    """x [R,s*s,256] (s x s cells, s = roi_size, default 7) -> the unfolded input [R*s*s, 2304] of a 3 x 3 convolution with padding 1, column
+    order (tap, channel): ``mv2d_im2col3x3`` / ``mv2d_col2im3x3`` (s = 7) or their ``_s`` entries -- one launch per direction."""
 
     @staticmethod
-    def forward(ctx, x):
+    def forward(ctx, x, roi_size=7):
         x = _rows3(x)
-        R = x.shape[0]
-        cols = torch.empty((R * 49, 2304), device=x.device, dtype=F32)
-        check(_lib.load().mv2d_im2col3x3(_p(x), _p(cols), R, _stream()), 'mv2d_im2col3x3')
-        ctx.R = R
+        R, s = x.shape[0], int(roi_size)
+        cols = torch.empty((R * s * s, 2304), device=x.device, dtype=F32)
+        if s == 7:
+            check(_lib.load().mv2d_im2col3x3(_p(x), _p(cols), R, _stream()), 'mv2d_im2col3x3')
+        else:
+            check(_lib.load().mv2d_im2col3x3_s(_p(x), _p(cols), R, s, _stream()), 'mv2d_im2col3x3_s')
+        ctx.R, ctx.s = R, s
         return cols
 
     @staticmethod
     def backward(ctx, g):
         g = _rows3(g)
-        dx = torch.empty((ctx.R, 49, 256), device=g.device, dtype=F32)
-        check(_lib.load().mv2d_col2im3x3(_p(g), _p(dx), ctx.R, _stream()), 'mv2d_col2im3x3')
-        return dx
+        s = ctx.s
+        dx = torch.empty((ctx.R, s * s, 256), device=g.device, dtype=F32)
+        if s == 7:
+            check(_lib.load().mv2d_col2im3x3(_p(g), _p(dx), ctx.R, _stream()), 'mv2d_col2im3x3')
+        else:
+            check(_lib.load().mv2d_col2im3x3_s(_p(g), _p(dx), ctx.R, s, _stream()), 'mv2d_col2im3x3_s')
+        return dx, None
 
 
 class Center2LidarFn(torch.autograd.Function):

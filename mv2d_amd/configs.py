@@ -85,21 +85,29 @@ def _set_num_classes(d, num_classes):
     return d
 
 
-def roi_head_cfg_s(num_classes=10):
-    """CFG-S:40-121 (MV2D-S single frame); ``num_classes`` sets ``bbox_head.num_classes`` and ``bbox_head.bbox_coder.num_classes``."""
+def _set_roi_size(d, roi_size):
+    # the experiment configs' top-level ``roi_size`` (CFG-T:7), set where it appears: the RoI extractor's RoIAlign and the query generator
+    d['bbox_roi_extractor']['roi_layer']['output_size'] = roi_size
+    d['query_generator']['roi_feat_size'] = roi_size
+    return d
+
+
+def roi_head_cfg_s(num_classes=10, roi_size=ROI_SIZE):
+    """CFG-S:40-121 (MV2D-S single frame); ``num_classes`` sets ``bbox_head.num_classes`` and ``bbox_head.bbox_coder.num_classes``,
+    ``roi_size`` sets ``bbox_roi_extractor.roi_layer.output_size`` and ``query_generator.roi_feat_size``."""
     d = dict(type='MV2DSHead', use_denoise=False)
     d.update(_common(with_cp=False))
     d['box_correlation'] = dict(correlation_mode='topk_matched:1:0.0:0.0')
-    return copy.deepcopy(_set_num_classes(d, num_classes))
+    return copy.deepcopy(_set_roi_size(_set_num_classes(d, num_classes), roi_size))
 
 
-def roi_head_cfg_t(num_classes=10):
-    """CFG-T:40-125 (MV2D-T two frames); ``num_classes`` as in ``roi_head_cfg_s``."""
+def roi_head_cfg_t(num_classes=10, roi_size=ROI_SIZE):
+    """CFG-T:40-125 (MV2D-T two frames); ``num_classes`` and ``roi_size`` as in ``roi_head_cfg_s``."""
     d = dict(type='MV2DTHead', use_denoise=True, neg_bbox_loss=True,
              denoise_noise_scale=1.25, denoise_split=0.6)
     d.update(_common(with_cp=True))
     d['box_correlation'] = dict(expand_stride=2, correlation_mode='topk_matched:20:0.0:0.0')
-    return copy.deepcopy(_set_num_classes(d, num_classes))
+    return copy.deepcopy(_set_roi_size(_set_num_classes(d, num_classes), roi_size))
 
 
 TEST_CFG_RCNN = dict(score_thr=0.0, nms=dict(nms_thr=1.0, use_rotate_nms=True), max_per_scene=300)  # CFG-T:154-158

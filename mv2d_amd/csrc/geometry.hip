@@ -148,18 +148,23 @@ __global__ __launch_bounds__(256) void posemb3d_kernel(const float* __restrict__
 //     One block per (RoI, bin row); every bilinear tap is a fully coalesced C*4-byte row read.
 //     maps: up to two [V*h*w, 256] fp32 maps (feature, PE) -> out key16 (fp16) [R, 49, 256] each (+ optional fp32)
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void roi_align_kernel(const float* __restrict__ map0, const float* __restrict__ map1, const float* __restrict__ rois,
-                                                        unsigned short* __restrict__ out0, unsigned short* __restrict__ out1,
-                                                        float* __restrict__ out0_f32, float* __restrict__ out1_f32, int H, int W,
-                                                        float spatial_scale, int sampling_ratio, const int* __restrict__ map1_index,
-                                                        int out1_is_sum, int R, unsigned short* __restrict__ out0_lo,
-                                                        unsigned short* __restrict__ out1_lo, unsigned char* __restrict__ out0_lo8,
-                                                        unsigned char* __restrict__ out1_lo8, int* __restrict__ lo8_flag) {
-    // one block per RoI and bin row; wave w takes the bins w, w + 4 of the row, lane l the channels 4l .. 4l+3: every
+// SB > 0: SB x SB bins as a compile-time constant (7: the shipped configuration); SB = 0: s_rt x s_rt bins, 1 <= s_rt <= 14 (any RoI size of the
+// configs).  The 7x7 kernel below keeps its own signature and instruction stream; roi_align_s_kernel is the runtime-size instance.
+template <int SB>
+__device__ __forceinline__ void roi_align_body(const float* __restrict__ map0, const float* __restrict__ map1, const float* __restrict__ rois,
+                                               unsigned short* __restrict__ out0, unsigned short* __restrict__ out1,
+                                               float* __restrict__ out0_f32, float* __restrict__ out1_f32, int H, int W,
+                                               float spatial_scale, int sampling_ratio, const int* __restrict__ map1_index,
+                                               int out1_is_sum, int R, unsigned short* __restrict__ out0_lo,
+                                               unsigned short* __restrict__ out1_lo, unsigned char* __restrict__ out0_lo8,
+                                               unsigned char* __restrict__ out1_lo8, int* __restrict__ lo8_flag, int s_rt) {
+    // one block per RoI and bin row; wave w takes the bins w, w + 4, ... of the row, lane l the channels 4l .. 4l+3: every
     // bilinear tap is one 16-byte load per lane (a full 1 KB row per wave), every output one 8-byte (key16) / 16-byte (fp32) store.
-    // XCD-aware block map (block b runs on XCD b % 8): the 7 bin rows of a RoI tap overlapping map rows, so they take consecutive slots
-    // of ONE XCD and share its L2 (a (R, 7) grid ran them R blocks apart).  Speed only; any map is correct.
-    const int slot = blockIdx.x >> 3, ph = slot % 7, r = (slot / 7) * 8 + (blockIdx.x & 7);
+    // XCD-aware block map (block b runs on XCD b % 8): the S bin rows of a RoI tap overlapping map rows, so they take consecutive slots
+    // of ONE XCD and share its L2 (a (R, S) grid ran them R blocks apart).  Speed only; any map is correct.
+    const int S = SB > 0 ? SB : s_rt;
+    const float Sf = (float)S;
+    const int slot = blockIdx.x >> 3, ph = slot % S, r = (slot / S) * 8 + (blockIdx.x & 7);
     if (r >= R) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = 4 * lane;
     const float* b = rois + r * 5;
@@ -167,9 +172,9 @@ __global__ __launch_bounds__(256) void roi_align_kernel(const float* __restrict_
     const float x1 = b[1] * spatial_scale - 0.5f, y1 = b[2] * spatial_scale - 0.5f;
     const float x2 = b[3] * spatial_scale - 0.5f, y2 = b[4] * spatial_scale - 0.5f;
     const float rw = x2 - x1, rh = y2 - y1;
-    const float bw = rw / 7.0f, bh = rh / 7.0f;
-    const int gh = sampling_ratio > 0 ? sampling_ratio : (int)ceilf(rh / 7.0f);
-    const int gw = sampling_ratio > 0 ? sampling_ratio : (int)ceilf(rw / 7.0f);
+    const float bw = rw / Sf, bh = rh / Sf;
+    const int gh = sampling_ratio > 0 ? sampling_ratio : (int)ceilf(rh / Sf);
+    const int gw = sampling_ratio > 0 ? sampling_ratio : (int)ceilf(rw / Sf);
     const float count = (float)max(gh * gw, 1);
     const long long vbase = (long long)v * H * W;
     const int nmaps = map1 ? 2 : 1;
@@ -178,7 +183,7 @@ __global__ __launch_bounds__(256) void roi_align_kernel(const float* __restrict_
         s.x += w1 * a.x + w2 * bq.x + w3 * cq.x + w4 * d.x; s.y += w1 * a.y + w2 * bq.y + w3 * cq.y + w4 * d.y;
         s.z += w1 * a.z + w2 * bq.z + w3 * cq.z + w4 * d.z; s.w += w1 * a.w + w2 * bq.w + w3 * cq.w + w4 * d.w;
     };
-    for (int pw = wave; pw < 7; pw += 4) {
+    for (int pw = wave; pw < S; pw += 4) {
         float4 s0 = make_float4(0.f, 0.f, 0.f, 0.f), s1 = s0;
         for (int iy = 0; iy < gh; ++iy) {
             const float yy = y1 + ph * bh + (iy + 0.5f) * bh / gh;
@@ -203,7 +208,7 @@ __global__ __launch_bounds__(256) void roi_align_kernel(const float* __restrict_
                 }
             }
         }
-        const long long o = ((long long)r * 49 + ph * 7 + pw) * C + c;
+        const long long o = ((long long)r * (S * S) + ph * S + pw) * C + c;
         s0 = make_float4(s0.x / count, s0.y / count, s0.z / count, s0.w / count);
         // key16 outputs (common.h: fp16 since round 4); out*_lo: the remainder x - key16(x) next to the value: the fp32-class hi + lo rows of the
         // index-exact route; out*_lo8 (round 6): the same remainder as 256-byte e4m3 rows (common.h "lo8": what the cross attention gathers)
@@ -232,21 +237,46 @@ __global__ __launch_bounds__(256) void roi_align_kernel(const float* __restrict_
     }
 }
 
+__global__ __launch_bounds__(256) void roi_align_kernel(const float* __restrict__ map0, const float* __restrict__ map1, const float* __restrict__ rois,
+                                                        unsigned short* __restrict__ out0, unsigned short* __restrict__ out1,
+                                                        float* __restrict__ out0_f32, float* __restrict__ out1_f32, int H, int W,
+                                                        float spatial_scale, int sampling_ratio, const int* __restrict__ map1_index,
+                                                        int out1_is_sum, int R, unsigned short* __restrict__ out0_lo,
+                                                        unsigned short* __restrict__ out1_lo, unsigned char* __restrict__ out0_lo8,
+                                                        unsigned char* __restrict__ out1_lo8, int* __restrict__ lo8_flag) {
+    roi_align_body<7>(map0, map1, rois, out0, out1, out0_f32, out1_f32, H, W, spatial_scale, sampling_ratio, map1_index, out1_is_sum, R, out0_lo,
+                      out1_lo, out0_lo8, out1_lo8, lo8_flag, 7);
+}
+
+__global__ __launch_bounds__(256) void roi_align_s_kernel(const float* __restrict__ map0, const float* __restrict__ map1, const float* __restrict__ rois,
+                                                          unsigned short* __restrict__ out0, unsigned short* __restrict__ out1,
+                                                          float* __restrict__ out0_f32, float* __restrict__ out1_f32, int H, int W,
+                                                          float spatial_scale, int sampling_ratio, const int* __restrict__ map1_index,
+                                                          int out1_is_sum, int R, unsigned short* __restrict__ out0_lo,
+                                                          unsigned short* __restrict__ out1_lo, unsigned char* __restrict__ out0_lo8,
+                                                          unsigned char* __restrict__ out1_lo8, int* __restrict__ lo8_flag, int s) {
+    roi_align_body<0>(map0, map1, rois, out0, out1, out0_f32, out1_f32, H, W, spatial_scale, sampling_ratio, map1_index, out1_is_sum, R, out0_lo,
+                      out1_lo, out0_lo8, out1_lo8, lo8_flag, s);
+}
+
 // Backward of roi_align_kernel w.r.t. one map (training): the gradient of every output bin is spread over the bilinear taps
 // of its samples with the forward's weights / count.  Same grid and loops as the forward; fp32 hardware atomics into the (zeroed) map
 // gradient, so the summation order — not the values' set — varies from run to run (mmcv's RoIAlign backward does the same).
 // index: optional position -> row of a compacted map (rows < 0 are skipped).
-__global__ __launch_bounds__(256) void roi_align_bwd_kernel(const float* __restrict__ gout, const float* __restrict__ rois, float* __restrict__ gmap,
-                                                            const int* __restrict__ index, int H, int W, float spatial_scale, int sampling_ratio) {
+template <int SB>
+__device__ __forceinline__ void roi_align_bwd_body(const float* __restrict__ gout, const float* __restrict__ rois, float* __restrict__ gmap,
+                                                   const int* __restrict__ index, int H, int W, float spatial_scale, int sampling_ratio, int s_rt) {
+    const int S = SB > 0 ? SB : s_rt;
+    const float Sf = (float)S;
     const int r = blockIdx.x, ph = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = 4 * lane;
     const float* b = rois + r * 5;
     const int v = (int)b[0];
     const float x1 = b[1] * spatial_scale - 0.5f, y1 = b[2] * spatial_scale - 0.5f;
     const float x2 = b[3] * spatial_scale - 0.5f, y2 = b[4] * spatial_scale - 0.5f;
     const float rw = x2 - x1, rh = y2 - y1;
-    const float bw = rw / 7.0f, bh = rh / 7.0f;
-    const int gh = sampling_ratio > 0 ? sampling_ratio : (int)ceilf(rh / 7.0f);
-    const int gw = sampling_ratio > 0 ? sampling_ratio : (int)ceilf(rw / 7.0f);
+    const float bw = rw / Sf, bh = rh / Sf;
+    const int gh = sampling_ratio > 0 ? sampling_ratio : (int)ceilf(rh / Sf);
+    const int gw = sampling_ratio > 0 ? sampling_ratio : (int)ceilf(rw / Sf);
     const float count = (float)max(gh * gw, 1);
     const long long vbase = (long long)v * H * W;
     auto add = [&](long long q, float wgt, const float4& g) {
@@ -258,8 +288,8 @@ __global__ __launch_bounds__(256) void roi_align_bwd_kernel(const float* __restr
         float* d = gmap + q * C + c;
         unsafeAtomicAdd(d, wgt * g.x); unsafeAtomicAdd(d + 1, wgt * g.y); unsafeAtomicAdd(d + 2, wgt * g.z); unsafeAtomicAdd(d + 3, wgt * g.w);
     };
-    for (int pw = wave; pw < 7; pw += 4) {
-        float4 g = *reinterpret_cast<const float4*>(gout + ((long long)r * 49 + ph * 7 + pw) * C + c);
+    for (int pw = wave; pw < S; pw += 4) {
+        float4 g = *reinterpret_cast<const float4*>(gout + ((long long)r * (S * S) + ph * S + pw) * C + c);
         g = make_float4(g.x / count, g.y / count, g.z / count, g.w / count);
         for (int iy = 0; iy < gh; ++iy) {
             const float yy = y1 + ph * bh + (iy + 0.5f) * bh / gh;
@@ -278,6 +308,16 @@ __global__ __launch_bounds__(256) void roi_align_bwd_kernel(const float* __restr
             }
         }
     }
+}
+
+__global__ __launch_bounds__(256) void roi_align_bwd_kernel(const float* __restrict__ gout, const float* __restrict__ rois, float* __restrict__ gmap,
+                                                            const int* __restrict__ index, int H, int W, float spatial_scale, int sampling_ratio) {
+    roi_align_bwd_body<7>(gout, rois, gmap, index, H, W, spatial_scale, sampling_ratio, 7);
+}
+
+__global__ __launch_bounds__(256) void roi_align_bwd_s_kernel(const float* __restrict__ gout, const float* __restrict__ rois, float* __restrict__ gmap,
+                                                              const int* __restrict__ index, int H, int W, float spatial_scale, int sampling_ratio, int s) {
+    roi_align_bwd_body<0>(gout, rois, gmap, index, H, W, spatial_scale, sampling_ratio, s);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -447,13 +487,17 @@ __device__ __forceinline__ void roi_cell_range(const float* rb, int h, int w, fl
 // and its right / lower neighbour, clamped like the kernel clamps them.  The list the PE block is evaluated on shrinks by ~1 cell per axis and
 // RoI against the "RoI expanded by one cell" rectangle it replaces (141 k -> ~110 k positions per 16 cfg2_s samples); every tap, also a
 // zero-weight one, is still listed, so the RoI-aligned rows are bitwise the same.
-__device__ __forceinline__ void roi_tap_range(const float* rb, int h, int w, float spatial_scale, int& y0, int& y1, int& x0, int& x1) {
+// SB > 0: SB bins per axis as a compile-time constant (7: the shipped configuration), SB = 0: s_rt bins (the taps of roi_align_s_kernel).
+template <int SB = 7>
+__device__ __forceinline__ void roi_tap_range(const float* rb, int h, int w, float spatial_scale, int& y0, int& y1, int& x0, int& x1, int s_rt = SB) {
+    const int S = SB > 0 ? SB : s_rt;
+    const float Sf = (float)S;
     auto axis = [&](float lo_px, float hi_px, int n, int& c0, int& c1) {
         const float a = lo_px * spatial_scale - 0.5f, b = hi_px * spatial_scale - 0.5f;
-        const float len = b - a, bin = len / 7.0f;
-        const int g = (int)ceilf(len / 7.0f);
+        const float len = b - a, bin = len / Sf;
+        const int g = (int)ceilf(len / Sf);
         if (g <= 0) { c0 = n; c1 = -1; return; }                           // (degenerate RoI: no sample point, count = 1, zero output)
-        const float first = a + 0 * bin + (0 + 0.5f) * bin / g, last = a + 6 * bin + ((g - 1) + 0.5f) * bin / g;
+        const float first = a + 0 * bin + (0 + 0.5f) * bin / g, last = a + (S - 1) * bin + ((g - 1) + 0.5f) * bin / g;
         if (last < -1.0f || first > (float)n) { c0 = n; c1 = -1; return; }    // every sample of the axis is skipped
         const int lo = min((int)fmaxf(first, 0.f), n - 1), hi = min((int)fmaxf(last, 0.f), n - 1);
         c0 = lo;
@@ -464,9 +508,34 @@ __device__ __forceinline__ void roi_tap_range(const float* rb, int h, int w, flo
     if (x1 < x0 || y1 < y0) { x0 = w; x1 = -1; y0 = h; y1 = -1; }
 }
 
-// rect[r] = (view, y0, y1, x0, x1) and roi_mask[P] |= own-view rect   (roi_mask pre-zeroed)
+// rect[r] = (view, y0, y1, x0, x1) and roi_mask[P] |= own-view rect   (roi_mask pre-zeroed); S path (expand < 0): the taps of an SB x SB
+// RoIAlign (SB = 0: s_rt x s_rt)
+template <int SB>
+__device__ __forceinline__ void csr_mark_body(const float* __restrict__ rois, int* __restrict__ rect, unsigned char* __restrict__ roi_mask,
+                                              int h, int w, float stride, float expand, int s_rt) {
+    const int r = blockIdx.x, lane = threadIdx.x;
+    __shared__ int sr[4];
+    const float* rb = rois + r * 5;
+    if (lane == 0) {
+        int y0, y1, x0, x1;
+        if (expand < 0.f) roi_tap_range<SB>(rb, h, w, 1.0f / stride, y0, y1, x0, x1, s_rt);      // S path: the RoIAlign tap cells
+        else roi_cell_range(rb, h, w, stride, expand, y0, y1, x0, x1);
+        sr[0] = y0; sr[1] = y1; sr[2] = x0; sr[3] = x1;
+        rect[r * 5 + 0] = (int)rb[0]; rect[r * 5 + 1] = y0; rect[r * 5 + 2] = y1; rect[r * 5 + 3] = x0; rect[r * 5 + 4] = x1;
+    }
+    __syncthreads();
+    const int v = (int)rb[0], y0 = sr[0], y1 = sr[1], x0 = sr[2], x1 = sr[3];
+    if (y1 < y0 || x1 < x0) return;
+    const int nw = x1 - x0 + 1, n = (y1 - y0 + 1) * nw;
+    for (int i = lane; i < n; i += 64) {
+        const int y = y0 + i / nw, x = x0 + i % nw;
+        roi_mask[((long long)v * h + y) * w + x] = 1;
+    }
+}
+
 __global__ __launch_bounds__(64) void csr_mark_kernel(const float* __restrict__ rois, int* __restrict__ rect, unsigned char* __restrict__ roi_mask,
                                                       int h, int w, float stride, float expand) {
+    // (csr_mark_body<7> spelled out: inlined through the template, hipcc schedules two independent instructions of this kernel differently)
     const int r = blockIdx.x, lane = threadIdx.x;
     __shared__ int sr[4];
     const float* rb = rois + r * 5;
@@ -485,6 +554,11 @@ __global__ __launch_bounds__(64) void csr_mark_kernel(const float* __restrict__ 
         const int y = y0 + i / nw, x = x0 + i % nw;
         roi_mask[((long long)v * h + y) * w + x] = 1;
     }
+}
+
+__global__ __launch_bounds__(64) void csr_mark_s_kernel(const float* __restrict__ rois, int* __restrict__ rect, unsigned char* __restrict__ roi_mask,
+                                                        int h, int w, float stride, float expand, int s) {
+    csr_mark_body<0>(rois, rect, roi_mask, h, w, stride, expand, s);
 }
 
 // pos2s[P] = index into the compacted key list or -1 (not in any RoI rect, or padding),
@@ -684,9 +758,12 @@ __global__ __launch_bounds__(256) void csr_fill_kernel(const unsigned int* __res
 // Blocks of CFC_ROWS rows (round 4; round 1-3: ONE block walked all rows, 56 us at 4800 rows): a block first counts the RoIs listed by all
 // earlier rows itself (a few KB of match entries, cheaper than a second launch or a look-back chain), scans its own rows, then every wave
 // writes whole rows -- lanes = consecutive entries, the RoI ids of the row compacted through 256 B of LDS.
+// NCB > 0: NCB cells per RoI as a compile-time constant (49: 7 x 7 bins), NCB = 0: nc_rt cells (s x s bins of the RoI size s).
 constexpr int CFC_ROWS = 256;
+template <int NCB = 49>
 __device__ __forceinline__ void csr_from_corr_block(int blk, const int* __restrict__ match, int* __restrict__ row_ptr, int* __restrict__ col_idx,
-                                                    int* __restrict__ nnz_out, int R, int nm /* V * topk */) {
+                                                    int* __restrict__ nnz_out, int R, int nm /* V * topk */, int nc_rt = NCB) {
+    const int NC = NCB > 0 ? NCB : nc_rt;
     __shared__ int wsum[16];
     __shared__ int before_s;
     __shared__ int rowoff[CFC_ROWS + 1];
@@ -715,17 +792,17 @@ __device__ __forceinline__ void csr_from_corr_block(int blk, const int* __restri
         int off = before_s + sc - n;
         for (int k = 0; k < wv; ++k) off += wsum[k];
         rowoff[tid] = off;
-        if (r_own < R) row_ptr[r_own] = off * 49;
-        if (r_own == R - 1) { row_ptr[R] = (off + n) * 49; *nnz_out = (off + n) * 49; }
+        if (r_own < R) row_ptr[r_own] = off * NC;
+        if (r_own == R - 1) { row_ptr[R] = (off + n) * NC; *nnz_out = (off + n) * NC; }
     }
     __syncthreads();
-    // ---- a wave per row: compact the row's RoI ids (slot 0 = the row itself), then write 49 consecutive cells per id
+    // ---- a wave per row: compact the row's RoI ids (slot 0 = the row itself), then write NC consecutive cells per id
     for (int q = wv; q < CFC_ROWS; q += 16) {
         const int r = base + q;
         if (r >= R) break;
         // list positions p = 0 (the row itself), 1 .. nm (its match entries), 64 at a time (one pass when nm < 64: the shipped 'topk_matched' lists;
         // 'all_matched' lists up to views x 128 RoIs, round 6)
-        int* out = col_idx + (long long)rowoff[q] * 49;
+        int* out = col_idx + (long long)rowoff[q] * NC;
         for (int p0 = 0; p0 <= nm; p0 += 64) {
             const int p = p0 + lane;
             int id = -1;
@@ -735,8 +812,8 @@ __device__ __forceinline__ void csr_from_corr_block(int blk, const int* __restri
             if (id >= 0) ids[wv][__popcll(bal & ((1ull << lane) - 1ull))] = id;
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_s_waitcnt(0xc07f);
-            const int cnt = __popcll(bal) * 49;
-            for (int e = lane; e < cnt; e += 64) { const int k = e / 49; out[e] = ids[wv][k] * 49 + (e - k * 49); }
+            const int cnt = __popcll(bal) * NC;
+            for (int e = lane; e < cnt; e += 64) { const int k = e / NC; out[e] = ids[wv][k] * NC + (e - k * NC); }
             out += cnt;
             __builtin_amdgcn_wave_barrier();
         }
@@ -746,6 +823,11 @@ __device__ __forceinline__ void csr_from_corr_block(int blk, const int* __restri
 __global__ __launch_bounds__(1024) void csr_from_corr_kernel(const int* __restrict__ match, int* __restrict__ row_ptr, int* __restrict__ col_idx,
                                                              int* __restrict__ nnz_out, int R, int nm) {
     csr_from_corr_block(blockIdx.x, match, row_ptr, col_idx, nnz_out, R, nm);
+}
+
+__global__ __launch_bounds__(1024) void csr_from_corr_s_kernel(const int* __restrict__ match, int* __restrict__ row_ptr, int* __restrict__ col_idx,
+                                                               int* __restrict__ nnz_out, int R, int nm, int cells) {
+    csr_from_corr_block<0>(blockIdx.x, match, row_ptr, col_idx, nnz_out, R, nm, cells);
 }
 
 // S path, launch order of the attention blocks (xattn_tile_kernel's `order`): the queries of a sample ranked by the SMALLEST RoI they list (own
@@ -808,6 +890,18 @@ __global__ __launch_bounds__(1024) void scan_and_csr_kernel(const unsigned char*
     const int b = blockIdx.x;
     if (b < nscan) csr_scan_positions_block(b, nscan, roi_mask, pad_mask, pos2s, s2pos, S_out, P);
     else if (b < nscan + ncsr) csr_from_corr_block(b - nscan, match, row_ptr, col_idx, nnz_out, R, nm);
+    else s_order_block((b - nscan - ncsr) / ord_chunks, (b - nscan - ncsr) % ord_chunks, match, grp_start, n_grp, R, nm, perm, order_flags);
+}
+
+// the same launch for s x s cells per RoI (csr_from_corr_block<0>; the scan and the order do not depend on the RoI size)
+__global__ __launch_bounds__(1024) void scan_and_csr_s_kernel(const unsigned char* __restrict__ roi_mask, const unsigned char* __restrict__ pad_mask,
+                                                              int* __restrict__ pos2s, int* __restrict__ s2pos, int* __restrict__ S_out, int P, int nscan,
+                                                              const int* __restrict__ match, int* __restrict__ row_ptr, int* __restrict__ col_idx,
+                                                              int* __restrict__ nnz_out, int R, int nm, int ncsr, const int* __restrict__ grp_start, int n_grp,
+                                                              int ord_chunks, int* __restrict__ perm, int* __restrict__ order_flags, int cells) {
+    const int b = blockIdx.x;
+    if (b < nscan) csr_scan_positions_block(b, nscan, roi_mask, pad_mask, pos2s, s2pos, S_out, P);
+    else if (b < nscan + ncsr) csr_from_corr_block<0>(b - nscan, match, row_ptr, col_idx, nnz_out, R, nm, cells);
     else s_order_block((b - nscan - ncsr) / ord_chunks, (b - nscan - ncsr) % ord_chunks, match, grp_start, n_grp, R, nm, perm, order_flags);
 }
 
@@ -1252,18 +1346,35 @@ extern "C" int mv2d_posemb3d(const float* ref, const float* dim_t, float* posemb
     return MV2D_OK;
 }
 
-extern "C" int mv2d_roi_align_ex(const float* map0, const float* map1, const float* rois, void* out0, void* out1, float* out0_f32,
-                                 float* out1_f32, int R, int H, int W, int channels, float spatial_scale, int sampling_ratio,
-                                 const int* map1_index, int out1_is_sum, void* out0_lo, void* out1_lo, void* out0_lo8, void* out1_lo8, int* lo8_flag, void* stream) {
+// RoI sizes of the size-taking entries: s x s bins, 1 <= s <= 14 (the S-path CSR, the conv + pool and the training kernels follow s)
+constexpr int ROI_SIZE_MAX = 14;
+
+extern "C" int mv2d_roi_align_s(const float* map0, const float* map1, const float* rois, void* out0, void* out1, float* out0_f32,
+                                float* out1_f32, int R, int H, int W, int channels, float spatial_scale, int sampling_ratio,
+                                const int* map1_index, int out1_is_sum, void* out0_lo, void* out1_lo, void* out0_lo8, void* out1_lo8, int* lo8_flag,
+                                int roi_size, void* stream) {
     MV2D_CHECK_ARG(map0 && rois && channels == C, "mv2d_roi_align: needs 256-channel position-major maps");
     MV2D_CHECK_ARG(out0 || out0_f32, "mv2d_roi_align: no output");
     MV2D_CHECK_ARG((!(out0_lo || out0_lo8) || out0) && (!(out1_lo || out1_lo8) || out1), "mv2d_roi_align_ex: a lo output needs its key16 (hi) output");
+    MV2D_CHECK_ARG(roi_size >= 1 && roi_size <= ROI_SIZE_MAX, "mv2d_roi_align_s: roi_size must be in [1, 14]");
     if (R == 0) return MV2D_OK;
-    hipLaunchKernelGGL(roi_align_kernel, dim3(56 * cdiv(R, 8)), dim3(256), 0, (hipStream_t)stream, map0, map1, rois, (unsigned short*)out0,
-                       (unsigned short*)out1, out0_f32, out1_f32, H, W, spatial_scale, sampling_ratio, map1_index, out1_is_sum, R,
-                       (unsigned short*)out0_lo, (unsigned short*)out1_lo, (unsigned char*)out0_lo8, (unsigned char*)out1_lo8, lo8_flag);
+    if (roi_size == 7)
+        hipLaunchKernelGGL(roi_align_kernel, dim3(56 * cdiv(R, 8)), dim3(256), 0, (hipStream_t)stream, map0, map1, rois, (unsigned short*)out0,
+                           (unsigned short*)out1, out0_f32, out1_f32, H, W, spatial_scale, sampling_ratio, map1_index, out1_is_sum, R,
+                           (unsigned short*)out0_lo, (unsigned short*)out1_lo, (unsigned char*)out0_lo8, (unsigned char*)out1_lo8, lo8_flag);
+    else
+        hipLaunchKernelGGL(roi_align_s_kernel, dim3(8 * roi_size * cdiv(R, 8)), dim3(256), 0, (hipStream_t)stream, map0, map1, rois, (unsigned short*)out0,
+                           (unsigned short*)out1, out0_f32, out1_f32, H, W, spatial_scale, sampling_ratio, map1_index, out1_is_sum, R,
+                           (unsigned short*)out0_lo, (unsigned short*)out1_lo, (unsigned char*)out0_lo8, (unsigned char*)out1_lo8, lo8_flag, roi_size);
     MV2D_LAUNCH_CHECK();
     return MV2D_OK;
+}
+
+extern "C" int mv2d_roi_align_ex(const float* map0, const float* map1, const float* rois, void* out0, void* out1, float* out0_f32,
+                                 float* out1_f32, int R, int H, int W, int channels, float spatial_scale, int sampling_ratio,
+                                 const int* map1_index, int out1_is_sum, void* out0_lo, void* out1_lo, void* out0_lo8, void* out1_lo8, int* lo8_flag, void* stream) {
+    return mv2d_roi_align_s(map0, map1, rois, out0, out1, out0_f32, out1_f32, R, H, W, channels, spatial_scale, sampling_ratio, map1_index, out1_is_sum,
+                            out0_lo, out1_lo, out0_lo8, out1_lo8, lo8_flag, 7, stream);
 }
 
 extern "C" int mv2d_roi_align(const float* map0, const float* map1, const float* rois, void* out0, void* out1, float* out0_f32,
@@ -1273,14 +1384,24 @@ extern "C" int mv2d_roi_align(const float* map0, const float* map1, const float*
                              out1_is_sum, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
-extern "C" int mv2d_roi_align_bwd(const float* grad_out, const float* rois, float* grad_map, const int* index, int R, int H, int W,
-                                  int channels, float spatial_scale, int sampling_ratio, void* stream) {
-    MV2D_CHECK_ARG(grad_out && rois && grad_map && channels == C, "mv2d_roi_align_bwd: needs fp32 [R,49,256] gradients and a 256-channel position-major map");
+extern "C" int mv2d_roi_align_bwd_s(const float* grad_out, const float* rois, float* grad_map, const int* index, int R, int H, int W,
+                                    int channels, float spatial_scale, int sampling_ratio, int roi_size, void* stream) {
+    MV2D_CHECK_ARG(grad_out && rois && grad_map && channels == C, "mv2d_roi_align_bwd: needs fp32 [R,s*s,256] gradients and a 256-channel position-major map");
+    MV2D_CHECK_ARG(roi_size >= 1 && roi_size <= ROI_SIZE_MAX, "mv2d_roi_align_bwd_s: roi_size must be in [1, 14]");
     if (R == 0) return MV2D_OK;
-    hipLaunchKernelGGL(roi_align_bwd_kernel, dim3(R, 7), dim3(256), 0, (hipStream_t)stream, grad_out, rois, grad_map, index, H, W, spatial_scale,
-                       sampling_ratio);
+    if (roi_size == 7)
+        hipLaunchKernelGGL(roi_align_bwd_kernel, dim3(R, 7), dim3(256), 0, (hipStream_t)stream, grad_out, rois, grad_map, index, H, W, spatial_scale,
+                           sampling_ratio);
+    else
+        hipLaunchKernelGGL(roi_align_bwd_s_kernel, dim3(R, roi_size), dim3(256), 0, (hipStream_t)stream, grad_out, rois, grad_map, index, H, W,
+                           spatial_scale, sampling_ratio, roi_size);
     MV2D_LAUNCH_CHECK();
     return MV2D_OK;
+}
+
+extern "C" int mv2d_roi_align_bwd(const float* grad_out, const float* rois, float* grad_map, const int* index, int R, int H, int W,
+                                  int channels, float spatial_scale, int sampling_ratio, void* stream) {
+    return mv2d_roi_align_bwd_s(grad_out, rois, grad_map, index, R, H, W, channels, spatial_scale, sampling_ratio, 7, stream);
 }
 
 extern "C" int mv2d_box_correlation(const float* rois, const int* view_start, const double* trans, const float* lin, const float* depths,
@@ -1363,29 +1484,53 @@ extern "C" int mv2d_roi_positions(const float* rois, const unsigned char* pad_ma
     return MV2D_OK;
 }
 
-extern "C" int mv2d_csr_from_corr(const int* match, int* row_ptr, int* col_idx, int* nnz_out, int R, int V, int topk, void* stream) {
+extern "C" int mv2d_csr_from_corr_s(const int* match, int* row_ptr, int* col_idx, int* nnz_out, int R, int V, int topk, int roi_size, void* stream) {
     MV2D_CHECK_ARG(match && row_ptr && col_idx && nnz_out && R > 0 && V * topk >= 0 && V * topk <= 4096, "mv2d_csr_from_corr: bad args (V * topk <= 4096)");
-    hipLaunchKernelGGL(csr_from_corr_kernel, dim3(cdiv(R, CFC_ROWS)), dim3(1024), 0, (hipStream_t)stream, match, row_ptr, col_idx, nnz_out, R, V * topk);
+    MV2D_CHECK_ARG(roi_size >= 1 && roi_size <= ROI_SIZE_MAX, "mv2d_csr_from_corr_s: roi_size must be in [1, 14]");
+    if (roi_size == 7)
+        hipLaunchKernelGGL(csr_from_corr_kernel, dim3(cdiv(R, CFC_ROWS)), dim3(1024), 0, (hipStream_t)stream, match, row_ptr, col_idx, nnz_out, R, V * topk);
+    else
+        hipLaunchKernelGGL(csr_from_corr_s_kernel, dim3(cdiv(R, CFC_ROWS)), dim3(1024), 0, (hipStream_t)stream, match, row_ptr, col_idx, nnz_out, R, V * topk,
+                           roi_size * roi_size);
     MV2D_LAUNCH_CHECK();
     return MV2D_OK;
 }
 
-// mv2d_roi_positions + mv2d_csr_from_corr (S path) in TWO launches instead of three: the mark kernel, then the position scan and the CSR side by side
-extern "C" int mv2d_roi_positions_csr(const float* rois, const unsigned char* pad_mask, unsigned char* roi_mask, int* rect, int* pos2s, int* s2pos,
-                                      int* S_out, int R, int V, int h, int w, float stride, float expand_stride, const int* match, int* row_ptr,
-                                      int* col_idx, int* nnz_out, int Vg, int topk, const int* grp_start, int n_samples, int* order, int* order_flags, void* stream) {
+extern "C" int mv2d_csr_from_corr(const int* match, int* row_ptr, int* col_idx, int* nnz_out, int R, int V, int topk, void* stream) {
+    return mv2d_csr_from_corr_s(match, row_ptr, col_idx, nnz_out, R, V, topk, 7, stream);
+}
+
+// mv2d_roi_positions + mv2d_csr_from_corr (S path) in TWO launches instead of three: the mark kernel, then the position scan and the CSR side by side.
+// roi_size s: the tap cells of an s x s RoIAlign (expand_stride < 0) and s * s cells per listed RoI in the CSR.
+extern "C" int mv2d_roi_positions_csr_s(const float* rois, const unsigned char* pad_mask, unsigned char* roi_mask, int* rect, int* pos2s, int* s2pos,
+                                        int* S_out, int R, int V, int h, int w, float stride, float expand_stride, const int* match, int* row_ptr,
+                                        int* col_idx, int* nnz_out, int Vg, int topk, const int* grp_start, int n_samples, int* order, int* order_flags,
+                                        int roi_size, void* stream) {
     MV2D_CHECK_ARG(!order || (grp_start && n_samples >= 1), "mv2d_roi_positions_csr: the block order needs the sample row ranges");
     MV2D_CHECK_ARG(rois && pad_mask && roi_mask && rect && pos2s && s2pos && S_out && R > 0, "mv2d_roi_positions_csr: bad args");
     MV2D_CHECK_ARG(match && row_ptr && col_idx && nnz_out && Vg * topk >= 0 && Vg * topk <= 4096, "mv2d_roi_positions_csr: bad CSR args (views per sample * topk <= 4096)");
+    MV2D_CHECK_ARG(roi_size >= 1 && roi_size <= ROI_SIZE_MAX, "mv2d_roi_positions_csr_s: roi_size must be in [1, 14]");
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(csr_mark_kernel, dim3(R), dim3(64), 0, st, rois, rect, roi_mask, h, w, stride, expand_stride);
     const int nscan = cdiv(V * h * w, SCAN_SEG), ncsr = cdiv(R, CFC_ROWS);
     const int ord_chunks = cdiv(R < SORD_MAX ? R : SORD_MAX, SORD_CHUNK), nord = order ? (n_samples + 1) * ord_chunks : 0;
-    hipLaunchKernelGGL(scan_and_csr_kernel, dim3(nscan + ncsr + nord), dim3(1024), 0, st, roi_mask, pad_mask, pos2s, s2pos, S_out, V * h * w, nscan,
-                       match, row_ptr, col_idx, nnz_out, R, Vg * topk, ncsr, grp_start, n_samples, ord_chunks, order, order_flags);
-
+    if (roi_size == 7) {
+        hipLaunchKernelGGL(csr_mark_kernel, dim3(R), dim3(64), 0, st, rois, rect, roi_mask, h, w, stride, expand_stride);
+        hipLaunchKernelGGL(scan_and_csr_kernel, dim3(nscan + ncsr + nord), dim3(1024), 0, st, roi_mask, pad_mask, pos2s, s2pos, S_out, V * h * w, nscan,
+                           match, row_ptr, col_idx, nnz_out, R, Vg * topk, ncsr, grp_start, n_samples, ord_chunks, order, order_flags);
+    } else {
+        hipLaunchKernelGGL(csr_mark_s_kernel, dim3(R), dim3(64), 0, st, rois, rect, roi_mask, h, w, stride, expand_stride, roi_size);
+        hipLaunchKernelGGL(scan_and_csr_s_kernel, dim3(nscan + ncsr + nord), dim3(1024), 0, st, roi_mask, pad_mask, pos2s, s2pos, S_out, V * h * w, nscan,
+                           match, row_ptr, col_idx, nnz_out, R, Vg * topk, ncsr, grp_start, n_samples, ord_chunks, order, order_flags, roi_size * roi_size);
+    }
     MV2D_LAUNCH_CHECK();
     return MV2D_OK;
+}
+
+extern "C" int mv2d_roi_positions_csr(const float* rois, const unsigned char* pad_mask, unsigned char* roi_mask, int* rect, int* pos2s, int* s2pos,
+                                      int* S_out, int R, int V, int h, int w, float stride, float expand_stride, const int* match, int* row_ptr,
+                                      int* col_idx, int* nnz_out, int Vg, int topk, const int* grp_start, int n_samples, int* order, int* order_flags, void* stream) {
+    return mv2d_roi_positions_csr_s(rois, pad_mask, roi_mask, rect, pos2s, s2pos, S_out, R, V, h, w, stride, expand_stride, match, row_ptr, col_idx, nnz_out,
+                                    Vg, topk, grp_start, n_samples, order, order_flags, 7, stream);
 }
 
 extern "C" int mv2d_pe_frustum_f32(const int* s2pos, const int* S_dev, int S_max, const double* img2lidar, const double* coords_w, const double* coords_h,

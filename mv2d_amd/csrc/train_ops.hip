@@ -243,6 +243,37 @@ __global__ __launch_bounds__(256) void col2im3x3_kernel(const float* __restrict_
     *reinterpret_cast<float4*>(dx + (long long)pos * 256 + c) = s;
 }
 
+// the same pair for s x s cells, 1 <= s <= 14 (the 7 x 7 kernels above stay the shipped instances)
+__global__ __launch_bounds__(256) void im2col3x3_s_kernel(const float* __restrict__ in, float* __restrict__ cols, int R, int s) {
+    const int S2 = s * s;
+    const int pos = blockIdx.x * 4 + (threadIdx.x >> 6), c = 4 * (threadIdx.x & 63);
+    if (pos >= R * S2) return;
+    const int r = pos / S2, p = pos % S2, y = p / s, x = p % s;
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap) {
+        const int yy = y + tap / 3 - 1, xx = x + tap % 3 - 1;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (yy >= 0 && yy < s && xx >= 0 && xx < s) v = *reinterpret_cast<const float4*>(in + ((long long)r * S2 + yy * s + xx) * 256 + c);
+        *reinterpret_cast<float4*>(cols + (long long)pos * 2304 + tap * 256 + c) = v;
+    }
+}
+__global__ __launch_bounds__(256) void col2im3x3_s_kernel(const float* __restrict__ dcols, float* __restrict__ dx, int R, int s) {
+    const int S2 = s * s;
+    const int pos = blockIdx.x * 4 + (threadIdx.x >> 6), c = 4 * (threadIdx.x & 63);
+    if (pos >= R * S2) return;
+    const int r = pos / S2, p = pos % S2, y = p / s, x = p % s;
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap) {
+        const int yy = y - tap / 3 + 1, xx = x - tap % 3 + 1;
+        if (yy >= 0 && yy < s && xx >= 0 && xx < s) {
+            const float4 v = *reinterpret_cast<const float4*>(dcols + ((long long)r * S2 + yy * s + xx) * 2304 + tap * 256 + c);
+            acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
+        }
+    }
+    *reinterpret_cast<float4*>(dx + (long long)pos * 256 + c) = acc;
+}
+
 }  // namespace
 
 // x [R, 49, 256] fp32 (7 x 7 cells, row-major) -> cols [R * 49, 2304]
@@ -323,6 +354,26 @@ extern "C" int mv2d_center2lidar_bwd(const float* g, const float* c, const float
     C2LRange rg;
     for (int k = 0; k < 3; ++k) { rg.lo[k] = pc_range[k]; rg.span[k] = pc_range[3 + k] - pc_range[k]; }
     hipLaunchKernelGGL(center2lidar_bwd_kernel, dim3(cdiv(R, 256)), dim3(256), 0, (hipStream_t)stream, g, c, minv, dc, R, rg);
+    MV2D_LAUNCH_CHECK();
+    return MV2D_OK;
+}
+
+// x [R, s * s, 256] fp32 (s x s cells, row-major) -> cols [R * s * s, 2304]; 1 <= s <= 14, s = 7 is mv2d_im2col3x3
+extern "C" int mv2d_im2col3x3_s(const float* x, float* cols, int R, int roi_size, void* stream) {
+    MV2D_CHECK_ARG(x && cols && R >= 0 && roi_size >= 1 && roi_size <= 14, "mv2d_im2col3x3_s: bad args (roi_size in [1, 14])");
+    if (roi_size == 7) return mv2d_im2col3x3(x, cols, R, stream);
+    if (R == 0) return MV2D_OK;
+    hipLaunchKernelGGL(im2col3x3_s_kernel, dim3(cdiv(R * roi_size * roi_size, 4)), dim3(256), 0, (hipStream_t)stream, x, cols, R, roi_size);
+    MV2D_LAUNCH_CHECK();
+    return MV2D_OK;
+}
+
+// gradient of mv2d_im2col3x3_s: dcols [R * s * s, 2304] -> dx [R, s * s, 256]
+extern "C" int mv2d_col2im3x3_s(const float* dcols, float* dx, int R, int roi_size, void* stream) {
+    MV2D_CHECK_ARG(dcols && dx && R >= 0 && roi_size >= 1 && roi_size <= 14, "mv2d_col2im3x3_s: bad args (roi_size in [1, 14])");
+    if (roi_size == 7) return mv2d_col2im3x3(dcols, dx, R, stream);
+    if (R == 0) return MV2D_OK;
+    hipLaunchKernelGGL(col2im3x3_s_kernel, dim3(cdiv(R * roi_size * roi_size, 4)), dim3(256), 0, (hipStream_t)stream, dcols, dx, R, roi_size);
     MV2D_LAUNCH_CHECK();
     return MV2D_OK;
 }

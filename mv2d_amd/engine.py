@@ -42,7 +42,7 @@ class HeadEngine:
     def __init__(self, state_dict, kind, device, num_views=6, topk=None, expand_stride=None, num_layers=L_DEFAULT,
                  max_num=300, pc_range=(-51.2, -51.2, -5.0, 51.2, 51.2, 3.0),
                  post_range=(-61.2, -61.2, -10.0, 61.2, 61.2, 10.0), depth_num=64, stride=16, col_cap_per_query=2048,
-                 iou_thr=0.0, ratio=0.0, masked_row='nan', exact=None, num_classes=10):
+                 iou_thr=0.0, ratio=0.0, masked_row='nan', exact=None, num_classes=10, roi_size=7):
         assert kind in ('S', 'T')
         self.kind = kind
         self.dev = torch.device(device)
@@ -54,6 +54,11 @@ class HeadEngine:
         self.num_classes = int(num_classes)
         if not 1 <= self.num_classes <= 64:       # the class output layer of mv2d_heads_fused_x3_nc: up to 4 column tiles of 16
             raise ValueError(f'HeadEngine: num_classes must be in [1, 64], got {num_classes}')
+        # RoIAlign output size s (square): s x s bins per RoI -> s * s RoI cells (query-generator conv input; the S path's keys per RoI)
+        self.roi_size = int(roi_size)
+        if self.roi_size != roi_size or not 1 <= self.roi_size <= 14:
+            raise ValueError(f'HeadEngine: roi_size must be an int in [1, 14], got {roi_size}')
+        self.cells = self.roi_size * self.roi_size
         self.depth_num = depth_num
         self.stride = stride
         self.iou_thr, self.ratio = iou_thr, ratio
@@ -266,12 +271,12 @@ class HeadEngine:
         (kernels index [*, R, *] tensors densely) plus its own hipGraph; staging buffers, calibration cache and the stream-order
         guard are shared by all R of a bucket."""
         Vg = V if Vg is None else Vg                     # views per sample; V = all views of the batch
-        key = (V, h, w, R, Vg, self.num_classes)
+        key = (V, h, w, R, Vg, self.num_classes, self.roi_size)
         ws = self._ws.get(key)
         if ws is not None:
             return ws
         cap = max(64, -(-R // 32) * 32)
-        bkey = (V, h, w, cap, Vg, self.num_classes)
+        bkey = (V, h, w, cap, Vg, self.num_classes, self.roi_size)
         base = self._ws_base.get(bkey)
         if base is None:
             store = []
@@ -331,9 +336,10 @@ class HeadEngine:
             ws['grp_start' + sfx] = buf[o2:o3]
             ws['dt_rows' + sfx] = buf[o3:].view(F32)
         K16 = self.K16
+        NC = self.cells                                  # RoI cells (s x s)
         ws['featcl'] = e((P, C))
         ws['enc'] = z((R, 1056)); ws['minv'] = e((R, 16))
-        ws['roi_feat'] = e((R, 49, C), K16)
+        ws['roi_feat'] = e((R, NC, C), K16)
         ws['enc1'] = e((R, 512)); ws['enc2'] = e((R, C)); ws['center'] = e((R, 3))
         ws['xyz'] = e((R, 3)); ws['ref'] = e((R, 3)); ws['posemb'] = e((R, 384)); ws['qe1'] = e((R, C)); ws['qpos'] = e((R, C))
         ws['match'] = e((R, Vg, self.topk), torch.int32)
@@ -354,9 +360,9 @@ class HeadEngine:
             ws['col_cap'] = R * self.col_cap_per_query
             ws['S_kv'] = P
         else:
-            ws['col_cap'] = R * (1 + Vg * self.topk) * 49
-            ws['S_kv'] = R * 49
-            ws['roi_sum'] = e((R, 49, C), K16)
+            ws['col_cap'] = R * (1 + Vg * self.topk) * NC
+            ws['S_kv'] = R * NC
+            ws['roi_sum'] = e((R, NC, C), K16)
         ws['q_order'] = alloc(R, torch.int32, zero=True) if self.q_order else None
         ws['col_idx'] = e(ws['col_cap'], torch.int32)
         # group tables of the shared-tile cross attention (csrc/xattn_group.hip): g_slot | g_cnt | g_ptr | g_len per group, the groups' union key lists
@@ -377,11 +383,11 @@ class HeadEngine:
             LO = torch.uint8 if lo8 else K16
             if self.kind == 'T':
                 ws['xk_lo'] = z((P, C), LO); ws['xv_lo'] = z((P, C), LO)
-                ws['roi_lo'] = e((R, 49, C), K16)                 # lo halves of the RoI cells (conv input)
+                ws['roi_lo'] = e((R, NC, C), K16)                 # lo halves of the RoI cells (conv input)
             else:
-                ws['xk_lo'] = z((R * 49, C), LO); ws['xv_lo'] = z((R * 49, C), LO)
+                ws['xk_lo'] = z((R * NC, C), LO); ws['xv_lo'] = z((R * NC, C), LO)
                 # S path: the value rows ARE the RoI cells (key16 lo rows: one array for both; lo8 rows: the split-precision conv, when it runs, reads its own key16 lo cells)
-                ws['roi_lo'] = e((R, 49, C), K16) if lo8 else ws['xv_lo'].view(R, 49, C)
+                ws['roi_lo'] = e((R, NC, C), K16) if lo8 else ws['xv_lo'].view(R, NC, C)
         ws['pe'] = e((P, C)); ws['Xk'] = e((P, C), K16)
         ws['pe_pos'] = z((P, C)) if (self.kind == 'S' and self.exact and self.pe_at_positions) else None      # never-listed rows stay 0 (they only ever meet weight 0)
         # cross attention in the raw key space: per-query operand Qt (key16 hi | lo rows of the 8 per-head maps), per-head context sums z
@@ -390,7 +396,7 @@ class HeadEngine:
         if self.kind == 'T':
             ws['xk_rows'], ws['xv_rows'] = ws['Xk'], ws['Xf_b']
         else:
-            ws['xk_rows'], ws['xv_rows'] = ws['roi_sum'].view(R * 49, C), ws['roi_feat'].view(R * 49, C)
+            ws['xk_rows'], ws['xv_rows'] = ws['roi_sum'].view(R * NC, C), ws['roi_feat'].view(R * NC, C)
         for n in ('x', 'x1', 'x2', 'ctx', 'q'):
             ws[n] = e((R, C))
         ws['zero_rows'] = z((R, C))                              # never written
@@ -581,7 +587,7 @@ class HeadEngine:
         # bytes: one launch (round 4; a one-sample frame is bound by its NUMBER of kernels)
         o.frame_geometry(rois, T['viewK'], T['viewE'], ws['enc'][:, 1024:], 1056, ws['minv'], ws['view_start'], T['trans'], self.const['lin'],
                          self.const['depths'], ws['match'], Vg, self.topk, sc['pad_h'], sc['pad_w'], sc['max_per_view'], iou_thr=self.iou_thr,
-                         ratio=self.ratio, zero=ws['zbuf'])
+                         ratio=self.ratio, zero=ws['zbuf'], roi_size=float(self.roi_size))
         tk('csr')
         # T path: the query-generator chain (RoIAlign -> conv -> fcs -> ref points -> query_pos) only needs the feature map and
         # the per-RoI cameras, the key chain (correlation -> key list -> PE -> K/V) only the boxes: run them on two streams
@@ -592,7 +598,7 @@ class HeadEngine:
                 side = ws['side_stream'] = torch.cuda.Stream(device=self.dev)
             side.wait_stream(main)
             with torch.cuda.stream(side):
-                o.roi_align(featcl, rois, h, w, out0=ws['roi_feat'], R=R)
+                o.roi_align(featcl, rois, h, w, out0=ws['roi_feat'], R=R, roi_size=self.roi_size)
                 self._enqueue_qg(ws, R)
         if self.kind == 'T':
             # a11/a12: key list + CSR, then a4 RoIAlign of the feature half only
@@ -608,7 +614,7 @@ class HeadEngine:
             if not forked:
                 tk('roi_align')
                 o.roi_align(featcl, rois, h, w, out0=ws['roi_feat'],
-                            out0_lo=ws.get('roi_lo') if (self.exact and 'conv' not in self.exact_skip) else None, R=R)
+                            out0_lo=ws.get('roi_lo') if (self.exact and 'conv' not in self.exact_skip) else None, R=R, roi_size=self.roi_size)
         else:
             if self.force_nc is not None:
                 # the synthetic rig barely correlates RoIs across views, so the S-path sweep over n_c
@@ -626,7 +632,8 @@ class HeadEngine:
             # the attention blocks (queries ranked by the smallest RoI they list)
             o.roi_positions_csr(rois, ws['zero_mask'], ws['roi_mask'], ws['rect'], ws['pos2s'], ws['s2pos'], ws['S_dev'], R, V, h, w, ws['match'],
                                 ws['row_ptr'], ws['col_idx'], ws['nnz'], Vg, self.topk, stride=self.stride, expand_stride=-1.0, grp_start=grp,
-                                order=ws.get('q_order') if self.q_order else None, order_flags=ws['qt_ctl'][1:] if self.q_order else None)
+                                order=ws.get('q_order') if self.q_order else None, order_flags=ws['qt_ctl'][1:] if self.q_order else None,
+                                roi_size=self.roi_size)
             if self._grouped(ws):
                 o.xattn_group_tables(ws['row_ptr'], ws['col_idx'], grp, R, ws['grp_tab'], order=ws.get('q_order') if self.q_order else None)
             if masked:
@@ -655,10 +662,11 @@ class HeadEngine:
             pe_map, pe_idx = (ws['pe_pos'], None) if at_pos else (ws['pe'], ws['pos2s'])
             if self.exact and self._lo8():
                 o.roi_align(featcl, rois, h, w, map1=pe_map, out0=ws['roi_feat'], out1=ws['roi_sum'], map1_index=pe_idx, out1_is_sum=True,
-                            out0_lo=ws.get('roi_lo') if 'conv' not in self.exact_skip else None, out0_lo8=ws['xv_lo'], out1_lo8=ws['xk_lo'], lo8_flag=ws['lo8_flag'], R=R)
+                            out0_lo=ws.get('roi_lo') if 'conv' not in self.exact_skip else None, out0_lo8=ws['xv_lo'], out1_lo8=ws['xk_lo'], lo8_flag=ws['lo8_flag'], R=R,
+                            roi_size=self.roi_size)
             else:
                 o.roi_align(featcl, rois, h, w, map1=pe_map, out0=ws['roi_feat'], out1=ws['roi_sum'], map1_index=pe_idx, out1_is_sum=True,
-                            out0_lo=ws['xv_lo'] if self.exact else None, out1_lo=ws['xk_lo'] if self.exact else None, R=R)
+                            out0_lo=ws['xv_lo'] if self.exact else None, out1_lo=ws['xk_lo'] if self.exact else None, R=R, roi_size=self.roi_size)
         if self.ablate_zero_lo and self.exact:
             if self._lo8():
                 raise ValueError('ablate_zero_lo works on key16 lo rows: set lo8_rows = False')
@@ -739,12 +747,12 @@ class HeadEngine:
     def _enqueue_qg(self, ws, R):
         """a6-a8, a13: QueryGenerator on the RoI features -> reference points -> query positional embedding."""
         o, W_, tk = ops, self.w, self._tick
-        # a6: QueryGenerator: conv3x3 + ReLU + AvgPool2d(7) fused, one block per RoI (index-exact route: in split precision on the hi + lo cells)
+        # a6: QueryGenerator: conv3x3 + ReLU + AvgPool2d(s) fused, one block per RoI (index-exact route: in split precision on the hi + lo cells)
         tk('qg_conv_gemm')
         if self.exact and 'conv' not in self.exact_skip:
-            o.qg_conv_pool_x3(ws['roi_feat'], ws['roi_lo'], W_['qg_conv_wx3'], W_['qg_conv_b'], ws['x2'], R=R)
+            o.qg_conv_pool_x3(ws['roi_feat'], ws['roi_lo'], W_['qg_conv_wx3'], W_['qg_conv_b'], ws['x2'], R=R, roi_size=self.roi_size)
         else:
-            o.qg_conv_pool(ws['roi_feat'], W_['qg_conv_wp'], W_['qg_conv_b'], ws['x2'], R=R)
+            o.qg_conv_pool(ws['roi_feat'], W_['qg_conv_wp'], W_['qg_conv_b'], ws['x2'], R=R, roi_size=self.roi_size)
         tk('qg_rest')
         o.linear_x3(ws['x2'], W_['qg_fc_wx'], W_['qg_fc_b'], N=1024, K=256, act=1, clamp=5e3, out=ws['enc'], ldc=1056, M=R)
         o.linear_x3(ws['enc'], W_['qg_e0_wx'], W_['qg_e0_b'], N=512, K=1056, act=1, out=ws['enc1'], M=R)
@@ -934,7 +942,7 @@ class HeadEngine:
             return dict(self._result(ws, R, keep_stages, batch), dt=sc['dt'])
         # the graph bakes in the input pointers (the producer's output buffers are static under graph replay) and the
         # frame scalars; anything else changing (RoI boxes, calibration tables, feature values) is data.
-        gkey = (ptrs, 0 if payload is None else payload.data_ptr(), sc['pad_h'], sc['pad_w'], sc['max_rows'], self.num_classes, self._weights_version, self._stage_outputs, self.last_stage_heads,
+        gkey = (ptrs, 0 if payload is None else payload.data_ptr(), sc['pad_h'], sc['pad_w'], sc['max_rows'], self.num_classes, self.roi_size, self._weights_version, self._stage_outputs, self.last_stage_heads,
                 self.xattn_waves, self.fuse_maps, self.fuse_xattn, self.group_xattn, self.lo8_rows, self.pe_at_positions, self.pe_rows_in_waves, self.fold_sa0, self.masked_transpose, self.keep_sine_rows, self.force_nc, self.q_order,
                 self.fork_qg, self.exact_skip, self.ablate_zero_lo, self.stop_before_decoder)   # load_state() re-allocates the weights; every route option of __init__ is in the key
         graphs = ws.setdefault('graphs', {})             # one graph per (input buffers, frame scalars): a producer that alternates between

@@ -481,21 +481,38 @@ def pack_wfrag(W):
     return Wp
 
 
-def qg_conv_pool(roi_feat, W, bias, out, R=None, ld_out=None):
-    """out[r] = avgpool7x7(relu(conv3x3(roi_feat[r]) + bias)); roi_feat [R,49,256] key16, W = pack_key16(conv weight [256,2304])."""
+def _roi_size(s):
+    s = int(s)
+    if not 1 <= s <= 14:
+        raise ValueError(f'roi_size must be in [1, 14], got {s}')
+    return s
+
+
+def qg_conv_pool(roi_feat, W, bias, out, R=None, ld_out=None, roi_size=7):
+    """out[r] = avgpool_s(relu(conv3x3(roi_feat[r]) + bias)); roi_feat [R,s*s,256] key16 (s = roi_size, 1..14), W = pack_key16(conv weight [256,2304])."""
     _req16(roi_feat, 'roi_feat'); _req16(W, 'W'); _req(bias, torch.float32, 'bias'); _req(out, torch.float32, 'out')
     R = roi_feat.shape[0] if R is None else R
-    check(_lib.load().mv2d_qg_conv_pool(_p(roi_feat), _p(W), _p(bias), _p(out), out.stride(0) if ld_out is None else ld_out, R, _stream()),
-          'mv2d_qg_conv_pool')
+    s = _roi_size(roi_size)
+    if s == 7:
+        check(_lib.load().mv2d_qg_conv_pool(_p(roi_feat), _p(W), _p(bias), _p(out), out.stride(0) if ld_out is None else ld_out, R, _stream()),
+              'mv2d_qg_conv_pool')
+    else:
+        check(_lib.load().mv2d_qg_conv_pool_s(_p(roi_feat), _p(W), _p(bias), _p(out), out.stride(0) if ld_out is None else ld_out, R, s, _stream()),
+              'mv2d_qg_conv_pool_s')
     return out
 
 
-def qg_conv_pool_x3(roi_hi, roi_lo, W_x3, bias, out, R=None, ld_out=None):
-    """qg_conv_pool in split precision: RoI cells as key16 hi + lo [R,49,256], W_x3 = pack_key16_x3(conv weight [256,2304])."""
+def qg_conv_pool_x3(roi_hi, roi_lo, W_x3, bias, out, R=None, ld_out=None, roi_size=7):
+    """qg_conv_pool in split precision: RoI cells as key16 hi + lo [R,s*s,256], W_x3 = pack_key16_x3(conv weight [256,2304])."""
     _req16(roi_hi, 'roi_hi'); _req16(roi_lo, 'roi_lo'); _req16(W_x3[0], 'W_hi'); _req16(W_x3[1], 'W_lo'); _req(bias, torch.float32, 'bias'); _req(out, torch.float32, 'out')
     R = roi_hi.shape[0] if R is None else R
-    check(_lib.load().mv2d_qg_conv_pool_x3(_p(roi_hi), _p(roi_lo), _p(W_x3[0]), _p(W_x3[1]), _p(bias), _p(out),
-                                           out.stride(0) if ld_out is None else ld_out, R, _stream()), 'mv2d_qg_conv_pool_x3')
+    s = _roi_size(roi_size)
+    if s == 7:
+        check(_lib.load().mv2d_qg_conv_pool_x3(_p(roi_hi), _p(roi_lo), _p(W_x3[0]), _p(W_x3[1]), _p(bias), _p(out),
+                                               out.stride(0) if ld_out is None else ld_out, R, _stream()), 'mv2d_qg_conv_pool_x3')
+    else:
+        check(_lib.load().mv2d_qg_conv_pool_x3_s(_p(roi_hi), _p(roi_lo), _p(W_x3[0]), _p(W_x3[1]), _p(bias), _p(out),
+                                                 out.stride(0) if ld_out is None else ld_out, R, s, _stream()), 'mv2d_qg_conv_pool_x3_s')
     return out
 
 
@@ -833,10 +850,19 @@ def posemb3d(ref, dim_t, out=None):
 
 
 def roi_align(map0, rois, H, W, *, map1=None, out0=None, out1=None, out0_f32=None, out1_f32=None, spatial_scale=1.0 / 16,
-              sampling_ratio=-1, map1_index=None, out1_is_sum=False, R=None, out0_lo=None, out1_lo=None, out0_lo8=None, out1_lo8=None, lo8_flag=None):
+              sampling_ratio=-1, map1_index=None, out1_is_sum=False, R=None, out0_lo=None, out1_lo=None, out0_lo8=None, out1_lo8=None, lo8_flag=None,
+              roi_size=7):
+    """roi_size s (1..14): s x s bins, every output [R, s*s, 256]; 7 runs the 7x7 entry mv2d_roi_align_ex."""
     _req(map0, torch.float32, 'map0'); _req(map1, torch.float32, 'map1'); _req(rois, torch.float32, 'rois')
     _req16(out0, 'out0'); _req16(out1, 'out1'); _req16(out0_lo, 'out0_lo'); _req16(out1_lo, 'out1_lo')
     _req(out0_lo8, torch.uint8, 'out0_lo8'); _req(out1_lo8, torch.uint8, 'out1_lo8'); _req(lo8_flag, torch.int32, 'lo8_flag')
+    s = _roi_size(roi_size)
+    if s != 7:
+        check(_lib.load().mv2d_roi_align_s(_p(map0), _p(map1), _p(rois), _p(out0), _p(out1), _p(out0_f32), _p(out1_f32),
+                                           rois.shape[0] if R is None else R, H, W, map0.shape[-1], spatial_scale, sampling_ratio,
+                                           _p(map1_index), 1 if out1_is_sum else 0, _p(out0_lo), _p(out1_lo), _p(out0_lo8), _p(out1_lo8), _p(lo8_flag), s,
+                                           _stream()), 'mv2d_roi_align_s')
+        return
     check(_lib.load().mv2d_roi_align_ex(_p(map0), _p(map1), _p(rois), _p(out0), _p(out1), _p(out0_f32), _p(out1_f32),
                                         rois.shape[0] if R is None else R, H, W, map0.shape[-1], spatial_scale, sampling_ratio,
                                         _p(map1_index), 1 if out1_is_sum else 0, _p(out0_lo), _p(out1_lo), _p(out0_lo8), _p(out1_lo8), _p(lo8_flag), _stream()),
@@ -882,16 +908,28 @@ def roi_positions(rois, pad_mask, roi_mask, rect, pos2s, s2pos, S_out, R, V, h, 
 
 
 def roi_positions_csr(rois, pad_mask, roi_mask, rect, pos2s, s2pos, S_out, R, V, h, w, match, row_ptr, col_idx, nnz_out, Vg, topk, stride=16.0,
-                      expand_stride=1.0, grp_start=None, order=None, order_flags=None):
-    """roi_positions + csr_from_corr (S path) in two launches; order (int32 [R]) + grp_start: also the launch order of the attention blocks."""
+                      expand_stride=1.0, grp_start=None, order=None, order_flags=None, roi_size=7):
+    """roi_positions + csr_from_corr (S path) in two launches; order (int32 [R]) + grp_start: also the launch order of the attention blocks.
+    roi_size s (1..14): s*s cells per listed RoI, and the tap cells of an s x s RoIAlign (expand_stride < 0)."""
     _req(order, torch.int32, 'order'); _req(grp_start, torch.int32, 'grp_start'); _req(order_flags, torch.int32, 'order_flags')
+    s = _roi_size(roi_size)
+    if s != 7:
+        check(_lib.load().mv2d_roi_positions_csr_s(_p(rois), _p(pad_mask), _p(roi_mask), _p(rect), _p(pos2s), _p(s2pos), _p(S_out), R, V, h, w, float(stride),
+                                                   float(expand_stride), _p(match), _p(row_ptr), _p(col_idx), _p(nnz_out), Vg, topk, _p(grp_start),
+                                                   grp_start.numel() - 1 if grp_start is not None else 0, _p(order), _p(order_flags), s, _stream()),
+              'mv2d_roi_positions_csr_s')
+        return
     check(_lib.load().mv2d_roi_positions_csr(_p(rois), _p(pad_mask), _p(roi_mask), _p(rect), _p(pos2s), _p(s2pos), _p(S_out), R, V, h, w, float(stride),
                                              float(expand_stride), _p(match), _p(row_ptr), _p(col_idx), _p(nnz_out), Vg, topk, _p(grp_start),
                                              grp_start.numel() - 1 if grp_start is not None else 0, _p(order), _p(order_flags), _stream()),
           'mv2d_roi_positions_csr')
 
 
-def csr_from_corr(match, row_ptr, col_idx, nnz_out, R, V, topk):
+def csr_from_corr(match, row_ptr, col_idx, nnz_out, R, V, topk, roi_size=7):
+    s = _roi_size(roi_size)
+    if s != 7:
+        check(_lib.load().mv2d_csr_from_corr_s(_p(match), _p(row_ptr), _p(col_idx), _p(nnz_out), R, V, topk, s, _stream()), 'mv2d_csr_from_corr_s')
+        return
     check(_lib.load().mv2d_csr_from_corr(_p(match), _p(row_ptr), _p(col_idx), _p(nnz_out), R, V, topk, _stream()),
           'mv2d_csr_from_corr')
 
@@ -951,32 +989,37 @@ def pack_detections(boxes, scores, labels, count, out, max_num=300):
 
 
 class RoIAlignRows(torch.autograd.Function):
-    """RoIAlign (mmcv semantics, 7x7, stride 16) of a position-major fp32 map [rows,256] -> [R,49,256] fp32, differentiable w.r.t. the
-    map (``mv2d_roi_align`` / ``mv2d_roi_align_bwd``).  ``index`` (int32 [V*H*W] or None): position -> row of a compacted map (the PE rows
-    of the S path); ``full`` is then any full-size map the kernel can read alongside (its output is discarded)."""
+    """RoIAlign (mmcv semantics, s x s bins with s = roi_size (default 7), stride 16) of a position-major fp32 map [rows,256] -> [R,s*s,256]
+    fp32, differentiable w.r.t. the map (``mv2d_roi_align`` / ``mv2d_roi_align_bwd`` and their ``_s`` entries).  ``index`` (int32 [V*H*W] or
+    None): position -> row of a compacted map (the PE rows of the S path); ``full`` is then any full-size map the kernel can read alongside
+    (its output is discarded)."""
 
     @staticmethod
-    def forward(ctx, rows, index, rois, H, W, full=None):
-        R = rois.shape[0]
-        out = torch.empty((R, 49, 256), device=rows.device, dtype=torch.float32)
+    def forward(ctx, rows, index, rois, H, W, full=None, roi_size=7):
+        R, s = rois.shape[0], _roi_size(roi_size)
+        out = torch.empty((R, s * s, 256), device=rows.device, dtype=torch.float32)
         rows_c = rows.contiguous()
         if index is None:
-            roi_align(rows_c, rois, H, W, out0_f32=out, R=R)
+            roi_align(rows_c, rois, H, W, out0_f32=out, R=R, roi_size=s)
         else:
             scratch = torch.empty_like(out)
-            roi_align(full.contiguous(), rois, H, W, map1=rows_c, out0_f32=scratch, out1_f32=out, map1_index=index, R=R)
+            roi_align(full.contiguous(), rois, H, W, map1=rows_c, out0_f32=scratch, out1_f32=out, map1_index=index, R=R, roi_size=s)
         ctx.save_for_backward(rois, index if index is not None else torch.empty(0, dtype=torch.int32, device=rows.device))
-        ctx.meta = (H, W, rows.shape[0], index is not None)
+        ctx.meta = (H, W, rows.shape[0], index is not None, s)
         return out
 
     @staticmethod
     def backward(ctx, gout):
         rois, index = ctx.saved_tensors
-        H, W, n, indexed = ctx.meta
+        H, W, n, indexed, s = ctx.meta
         gmap = torch.zeros((n, 256), device=gout.device, dtype=torch.float32)
-        check(_lib.load().mv2d_roi_align_bwd(_p(gout.contiguous().float()), _p(rois), _p(gmap), _p(index) if indexed else None, rois.shape[0], H, W,
-                                             256, 1.0 / 16, -1, _stream()), 'mv2d_roi_align_bwd')
-        return gmap, None, None, None, None, None
+        if s == 7:
+            check(_lib.load().mv2d_roi_align_bwd(_p(gout.contiguous().float()), _p(rois), _p(gmap), _p(index) if indexed else None, rois.shape[0], H, W,
+                                                 256, 1.0 / 16, -1, _stream()), 'mv2d_roi_align_bwd')
+        else:
+            check(_lib.load().mv2d_roi_align_bwd_s(_p(gout.contiguous().float()), _p(rois), _p(gmap), _p(index) if indexed else None, rois.shape[0], H, W,
+                                                   256, 1.0 / 16, -1, s, _stream()), 'mv2d_roi_align_bwd_s')
+        return gmap, None, None, None, None, None, None
 
 
 def match_cost(cls, box, gt, gt_labels, cls_weight=2.0, reg_weight=0.25, alpha=0.25, gamma=2.0):

@@ -17,7 +17,7 @@ import torch.nn as nn
 from .. import calib, ops
 from ..engine import HeadEngine
 from ..registry import HEADS, build_bbox_coder, build_head, build_loss, build_roi_extractor, build_transformer
-from .modules import BoxCorrelation, PE, QueryGenerator, _f, _rows
+from .modules import BoxCorrelation, PE, QueryGenerator, _f, _rows, roi_size_of
 
 C = 256
 
@@ -185,6 +185,12 @@ class MV2DHead(nn.Module):
         self.roi_size = bbox_roi_extractor['roi_layer']['output_size']
         if isinstance(self.roi_size, int):
             self.roi_size = [self.roi_size, self.roi_size]
+        # one square size s for the RoIAlign bins and the query generator's conv grid (the kernels take 1 <= s <= 14)
+        s_ext = roi_size_of(bbox_roi_extractor['roi_layer']['output_size'], 'bbox_roi_extractor.roi_layer.output_size')
+        s_qg = roi_size_of(query_generator.get('roi_feat_size', 7), 'query_generator.roi_feat_size')
+        if s_ext != s_qg:
+            raise ValueError(f'MV2DHead: roi_layer.output_size = {s_ext} and query_generator.roi_feat_size = {s_qg} must agree')
+        self.roi_cells = s_ext
         query_generator = dict(query_generator)
         query_generator.update(dict(loss_cls=self.bbox_head.loss_cls))
         self.query_generator = QueryGenerator(**query_generator)
@@ -225,7 +231,7 @@ class MV2DHead(nn.Module):
                                       expand_stride=bc.expand_stride, num_layers=self.bbox_head.num_pred, max_num=coder.max_num,
                                       pc_range=tuple(self.pc_range), post_range=tuple(coder.post_center_range),
                                       depth_num=self.position_encoding.depth_num, stride=self.strides[self.feat_lvl],
-                                      iou_thr=bc.iou_thr, ratio=bc.ratio, num_classes=self.bbox_head.num_classes,
+                                      iou_thr=bc.iou_thr, ratio=bc.ratio, num_classes=self.bbox_head.num_classes, roi_size=self.roi_cells,
                                       masked_row=(self.test_cfg or {}).get('masked_row', 'nan'),
                                       exact=(self.test_cfg or {}).get('index_exact', None))      # None: MV2D_EXACT decides
             if 'lo8_rows' in (self.test_cfg or {}):                              # test_cfg.lo8_rows=False: fp16 lo halves of the key / value rows (engine.py; default: e4m3 bytes)
@@ -276,7 +282,8 @@ class MV2DHead(nn.Module):
         V, _, h, w = feat.shape
         fm = feat.float().permute(0, 2, 3, 1).reshape(V * h * w, C)
         rois = ws['rois'][:R].clone()
-        bbox_feats = ops.RoIAlignRows.apply(fm, None, rois, h, w)                                   # [R,49,256]
+        s = self.roi_cells
+        bbox_feats = ops.RoIAlignRows.apply(fm, None, rois, h, w, None, s)                          # [R,s*s,256]
         # reference points with the gradient of the query generator (issued before the first host read-back below: the host keeps
         # launching while the engine's kernels run)
         ref = train.query_generator_autograd(self, bbox_feats, ws['enc'][:R, 1024:1040].clone(), ws['minv'][:R].clone())
@@ -297,9 +304,9 @@ class MV2DHead(nn.Module):
         if self.KIND == 'T':
             key_in, val_in = key_rows, val_rows
         else:
-            pe_aligned = ops.RoIAlignRows.apply(pe_rows, ws['pos2s'].clone(), rois, h, w, fm.detach())
-            val_in = bbox_feats.reshape(R * 49, C)
-            key_in = val_in + pe_aligned.reshape(R * 49, C)
+            pe_aligned = ops.RoIAlignRows.apply(pe_rows, ws['pos2s'].clone(), rois, h, w, fm.detach(), s)
+            val_in = bbox_feats.reshape(R * s * s, C)
+            key_in = val_in + pe_aligned.reshape(R * s * s, C)
         ref_const, pad, single, md, keys = ws['ref'][:R].clone(), 0, 1, None, None
         if getattr(self, 'use_denoise', False):
             padded, _, md = train.prepare_for_dn(ref_const, gt, labels, self.denoise_scalar, self.denoise_noise_scale, self.denoise_noise_trans,

@@ -40,11 +40,12 @@ class _Bf16Cache:
     def __init__(self):
         self._c = {}
 
-    def get(self, name, tensor):
+    def get(self, name, tensor, convert=None):
+        """convert (optional): fp32 parameter -> the cached copy (default: the bf16 copy)."""
         ver = (tensor.data_ptr(), tensor._version)
         hit = self._c.get(name)
         if hit is None or hit[0] != ver:
-            hit = (ver, ops.f32_to_bf16(_f(tensor)))
+            hit = (ver, (convert or ops.f32_to_bf16)(_f(tensor)))
             self._c[name] = hit
         return hit[1]
 
@@ -69,6 +70,21 @@ for _n in ('FocalLoss', 'L1Loss', 'CrossEntropyLoss', 'SmoothL1Loss'):
     LOSSES.register_module(name=_n, module=type(_n, (_LossStub,), {'type': _n}), force=True)
 
 
+ROI_SIZE_RANGE = (1, 14)          # square RoI sizes s the gfx950 kernels take (RoIAlign, conv + pool, S-path key lists)
+
+
+def roi_size_of(value, what='roi_size'):
+    """An RoI size as the configs write it (an int, or an equal pair) -> the int s; anything else raises ValueError naming the range."""
+    v = value
+    if isinstance(v, (tuple, list)):
+        if len(v) != 2 or v[0] != v[1]:
+            raise ValueError(f'{what}: only square RoI sizes s x s with {ROI_SIZE_RANGE[0]} <= s <= {ROI_SIZE_RANGE[1]} are supported, got {value!r}')
+        v = v[0]
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not ROI_SIZE_RANGE[0] <= int(v) <= ROI_SIZE_RANGE[1]:
+        raise ValueError(f'{what}: the RoI size must be an int (or an equal pair) in [{ROI_SIZE_RANGE[0]}, {ROI_SIZE_RANGE[1]}], got {value!r}')
+    return int(v)
+
+
 @ROI_EXTRACTORS.register_module()
 class SingleRoIExtractor(nn.Module):
     """mmdet SingleRoIExtractor + mmcv RoIAlign, single stride (CFG-T:49-53; call site RH/mv2d_head.py:114-115)."""
@@ -77,10 +93,10 @@ class SingleRoIExtractor(nn.Module):
         super().__init__()
         assert roi_layer['type'] == 'RoIAlign' and len(featmap_strides) == 1
         self.output_size = roi_layer['output_size']
+        self.roi_size = roi_size_of(self.output_size, 'roi_layer.output_size')
         self.sampling_ratio = roi_layer.get('sampling_ratio', 0)
         self.featmap_strides = featmap_strides
         self.out_channels = out_channels
-        assert self.output_size == 7, 'the gfx950 RoIAlign kernel is specialised for 7x7 bins'
 
     @property
     def num_inputs(self):
@@ -93,11 +109,12 @@ class SingleRoIExtractor(nn.Module):
         R = rois.shape[0]
         rois = rois.float().contiguous()
         maps = [ops.nchw_to_nhwc(x[:, i * C:(i + 1) * C].float().contiguous()) for i in range(Cn // C)]
-        outs = [torch.empty((R, 49, C), device=x.device, dtype=torch.float32) for _ in maps]
+        s = self.roi_size
+        outs = [torch.empty((R, s * s, C), device=x.device, dtype=torch.float32) for _ in maps]
         ops.roi_align(maps[0], rois, h, w, map1=maps[1] if len(maps) > 1 else None, out0_f32=outs[0],
                       out1_f32=outs[1] if len(maps) > 1 else None, spatial_scale=1.0 / self.featmap_strides[0],
-                      sampling_ratio=self.sampling_ratio)
-        return torch.cat([o.view(R, 7, 7, C).permute(0, 3, 1, 2) for o in outs], 1)
+                      sampling_ratio=self.sampling_ratio, roi_size=s)
+        return torch.cat([o.view(R, s, s, C).permute(0, 3, 1, 2) for o in outs], 1)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -627,7 +644,8 @@ class QueryGenerator(nn.Module):
                  norm_cfg=None, init_cfg=None, **kwargs):
         super().__init__()
         assert with_center and with_avg_pool and not (with_cls or with_size or with_heading or with_attr)
-        assert num_shared_convs == 1 and num_shared_fcs == 1 and in_channels == C and conv_out_channels == C and roi_feat_size == 7
+        assert num_shared_convs == 1 and num_shared_fcs == 1 and in_channels == C and conv_out_channels == C
+        self.roi_feat_size = roi_size_of(roi_feat_size, 'query_generator.roi_feat_size')
         assert all(kwargs.get(k, 0) == 0 for k in kwargs if k.startswith('num_')), 'branch convs/fcs are 0 in the shipped configs'
         fc = extra_encoding['feat_channels']
         assert extra_encoding['num_layers'] == 2 and len(extra_encoding['features']) == 1 and extra_encoding['features'][0]['in_channels'] == 16
@@ -640,19 +658,29 @@ class QueryGenerator(nn.Module):
         self._b = _Bf16Cache()
 
     def forward(self, x, intrinsics, extrinsics, extra_feats=dict()):
-        """x [R,256,7,7]; intrinsics/extrinsics [R,4,4] fp64 (per-RoI); extra_feats['intrinsic'] [R,16] -> (xyz [R,3], {})."""
+        """x [R,256,s,s] (s = roi_feat_size); intrinsics/extrinsics [R,4,4] fp64 (per-RoI); extra_feats['intrinsic'] [R,16] -> (xyz [R,3], {})."""
         assert not self.training
         dev = x.device
         R = x.shape[0]
-        xcl = ops.f32_to_bf16(x.float().flatten(2).transpose(1, 2).contiguous())           # [R,49,256]
+        s = self.roi_feat_size
+        if tuple(x.shape[2:]) != (s, s):
+            raise ValueError(f'QueryGenerator: RoI features of {tuple(x.shape[2:])} cells, roi_feat_size = {s}')
         conv = self.shared_convs[0].conv
-        wconv = self._b.get('conv', conv.weight.permute(0, 2, 3, 1).reshape(C, 9 * C))
-        co = ops.gemm_bf16(xcl, wconv, _f(conv.bias), conv3x3=True, act=1, out_dtype=torch.float32)
         K1 = self.fc_out_channels + 16
         Kp = (K1 + 31) // 32 * 32
         enc = torch.zeros((R, Kp), device=dev)
         pooled = torch.empty((R, C), device=dev)
-        ops.avgpool49(co, pooled, C, R)
+        if s == 7:
+            xcl = ops.f32_to_bf16(x.float().flatten(2).transpose(1, 2).contiguous())           # [R,49,256]
+            wconv = self._b.get('conv', conv.weight.permute(0, 2, 3, 1).reshape(C, 9 * C))
+            co = ops.gemm_bf16(xcl, wconv, _f(conv.bias), conv3x3=True, act=1, out_dtype=torch.float32)
+            ops.avgpool49(co, pooled, C, R)
+        else:
+            # other sizes: the engine's fused conv + ReLU + AvgPool2d(s) kernel (key16 cells, fragment-major key16 weights, packed once per
+            # version of the parameter) -- the precision of the engine's key16 route, not the bf16 GEMM of the 7x7 module path
+            xcl = ops.f32_to_key16(x.float().flatten(2).transpose(1, 2).contiguous())          # [R,s*s,256]
+            wp = self._b.get('conv_key16', conv.weight, lambda w: ops.pack_key16(w.permute(0, 2, 3, 1).reshape(C, 9 * C).contiguous()))
+            ops.qg_conv_pool(xcl, wp, _f(conv.bias).contiguous(), pooled, R=R, roi_size=s)
         fc = self.shared_fcs[0]
         ops.gemm_f32(pooled, _f(fc.weight), _f(fc.bias), act=1, clamp=5e3, out=enc, ldc=Kp)
         enc[:, self.fc_out_channels:K1] = extra_feats['intrinsic'].float().clamp(-5e3, 5e3)

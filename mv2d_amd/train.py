@@ -466,8 +466,8 @@ def allreduce_gradients(parameters, bucket_bytes=256 << 20, average=True, group=
 
 def query_generator_autograd(roi_head, roi_feat, intr_feat, minv):
     """``QueryGenerator.forward`` + ``center2lidar`` + the reference-point normalisation (RH/utils/query_generator.py:352-405,333-341;
-    RH/mv2d_s_head.py:146-152) as torch autograd over the module's own parameters, on the engine's RoIAlign output: roi_feat [R,49,256]
-    (bf16, cell-major 7x7), intr_feat [R,16] (scaled intrinsics), minv [R,16] = inverse(K_roi E^T) fp32.  Returns the normalised
+    RH/mv2d_s_head.py:146-152) as torch autograd over the module's own parameters, on the engine's RoIAlign output: roi_feat [R,s*s,256]
+    (bf16, cell-major s x s, s = the query generator's roi_feat_size), intr_feat [R,16] (scaled intrinsics), minv [R,16] = inverse(K_roi E^T) fp32.  Returns the normalised
     reference points [R,3], differentiable w.r.t. the query generator's parameters and w.r.t. roi_feat (``ops.RoIAlignRows`` carries the
     gradient on to the feature map)."""
     import torch.nn.functional as F
@@ -478,9 +478,10 @@ def query_generator_autograd(roi_head, roi_feat, intr_feat, minv):
     # conv3x3 (padding 1) as im2col + ONE product on the HIP GEMM, k order (tap, channel); the unfolding is one launch per direction (round 5)
     from .autograd_ops import Im2Col3x3Fn
     assert Cc == 256
-    cols = Im2Col3x3Fn.apply(roi_feat.float().reshape(R, 49, Cc))
+    s = getattr(qg, 'roi_feat_size', 7)                 # s x s cells (roi_feat [R,s*s,256])
+    cols = Im2Col3x3Fn.apply(roi_feat.float().reshape(R, s * s, Cc), s)
     conv = qg.shared_convs[0].conv
-    x = linear(cols, conv.weight.permute(0, 2, 3, 1).reshape(conv.weight.shape[0], 9 * Cc), conv.bias, 1).view(R, 49, -1).mean(1)   # ReLU, AvgPool2d(7)
+    x = linear(cols, conv.weight.permute(0, 2, 3, 1).reshape(conv.weight.shape[0], 9 * Cc), conv.bias, 1).view(R, s * s, -1).mean(1)   # ReLU, AvgPool2d(s)
     x = linear(x, qg.shared_fcs[0].weight, qg.shared_fcs[0].bias, 1)
     x = torch.cat([x, intr_feat.detach().float()], 1).clamp(min=-5e3, max=5e3)
     x = linear(x, qg.extra_enc[0].weight, qg.extra_enc[0].bias, 1)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Replay the head engine's hipGraph a few times on one stream (a profiling target for tools/prof_cmd.sh):
-    python tools/run_engine.py --workload cfg2_s --batch 8 --steps 20 [--exact] [--eager] [--num-classes N]"""
+    python tools/run_engine.py --workload cfg2_s --batch 8 --steps 20 [--exact] [--eager] [--num-classes N] [--roi-size S]"""
 import argparse
 import os
 import sys
@@ -22,11 +22,12 @@ ap.add_argument('--eager', action='store_true')
 ap.add_argument('--pe-v2', action='store_true', help='the opt-in second shape of the PE kernel (csrc/pe_x3b.hip) instead of csrc/pe_x3.hip')
 ap.add_argument('--group', type=int, default=None, help='1 / 0: force the shared-tile cross attention (csrc/xattn_group.hip) on / off; default: the engine chooses (T path: on)')
 ap.add_argument('--num-classes', type=int, default=10, help='class count of the head (synthetic weights of that many classes)')
+ap.add_argument('--roi-size', type=int, default=7, help='RoIAlign output size s (s x s bins, 1..14; the weights do not depend on it)')
 a = ap.parse_args()
 dev = torch.device('cuda:0')
 probs = [synthetic.make_problem(a.workload, seed=s) for s in range(a.batch)]
 eng = HeadEngine(synthetic.make_head_state(seed=0, num_classes=a.num_classes), probs[0]['kind'], dev, num_views=probs[0]['views_per_frame'],
-                 exact=not a.key16, num_classes=a.num_classes)
+                 exact=not a.key16, num_classes=a.num_classes, roi_size=a.roi_size)
 eng.fork_qg = False
 if a.pe_v2:
     eng.pe_rows_in_waves = True
@@ -44,4 +45,4 @@ for _ in range(a.steps):
     run()
 torch.cuda.synchronize()
 dt = (time.perf_counter() - t0) / a.steps
-print(f'{a.workload} batch {a.batch} num_classes {a.num_classes} route={"key16" if a.key16 else "index-exact"}: {dt * 1e3:.3f} ms per launch sequence, {a.batch / dt:.0f} samples/s on one stream')
+print(f'{a.workload} batch {a.batch} num_classes {a.num_classes} roi_size {a.roi_size} route={"key16" if a.key16 else "index-exact"}: {dt * 1e3:.3f} ms per launch sequence, {a.batch / dt:.0f} samples/s on one stream')
