@@ -106,6 +106,14 @@ int mv2d_pe_fused_tab2(const void* A1, const void* Xfb, const float* Xf32, const
                        const void* Wr, const float* br, const void* We, const float* be,
                        const float* sine_tab, int tab_period, float* pe, void* Xk, int shape, void* stream);
 
+/* mv2d_pe_fused_tab2 with the ELEMENT FORMAT of the feature map Xf32: map_fmt 0 = fp32, 1 = IEEE fp16, 2 = bf16 (the map_fmt of every *_fmt entry
+ * below).  A 16-bit element is widened to fp32 in registers -- exact -- and then meets the arithmetic of the fp32 kernel, so every output is bit for
+ * bit that of the fp32 entry fed the widened map; no fp32 image of the map exists.  mv2d_pe_fused_tab2 is this entry with map_fmt 0. */
+int mv2d_pe_fused_tab_fmt(const void* A1, const void* Xfb, const void* Xf32, const int* row_index, const int* m_dev, int M,
+                          const void* W1a, const float* b1a, const void* W1b, const float* b1b,
+                          const void* Wr, const float* br, const void* We, const float* be,
+                          const float* sine_tab, int tab_period, float* pe, void* Xk, int shape, int map_fmt, void* stream);
+
 /* The same block in SPLIT PRECISION on unrounded fp32 inputs (index-exact route; csrc/pe_x3.hip): every product a_hi w_hi + a_lo w_hi + a_hi w_lo on
  * bf16 MFMAs (2^-17 per operand), hidden layer split hi / lo in LDS.  A1 [M,192] fp32 (mv2d_pe_inputs' A_frustum_f32), Xmap = fp32 feature rows
  * [.,256] indexed by row_index[m] (or m when NULL); weights as bf16 hi / lo pairs (mv2d_split_bf16x2), each in the fragment-major order of
@@ -121,6 +129,13 @@ int mv2d_pe_fused_x3(const float* A1, const float* Xmap, const int* row_index, c
                      const void* Wr_hi, const void* Wr_lo, const float* br, const void* We_hi, const void* We_lo, const float* be,
                      const float* sine_tab, int tab_period, float* pe, void* Xk_hi, void* Xk_lo, void* Xv_hi, void* Xv_lo, int lo_fmt, int pe_at_index,
                      int* lo8_flag, void* stream);
+/* mv2d_pe_fused_x3 with the element format of the feature map Xmap (map_fmt: see mv2d_pe_fused_tab_fmt; 16-bit rows 8-byte aligned); mv2d_pe_fused_x3
+ * is this entry with map_fmt 0.  (mv2d_pe_fused_x3b below reads fp32 maps only.) */
+int mv2d_pe_fused_x3_fmt(const float* A1, const void* Xmap, const int* row_index, const int* m_dev, int M,
+                         const void* W1a_hi, const void* W1a_lo, const float* b1a, const void* W1b_hi, const void* W1b_lo, const float* b1b,
+                         const void* Wr_hi, const void* Wr_lo, const float* br, const void* We_hi, const void* We_lo, const float* be,
+                         const float* sine_tab, int tab_period, float* pe, void* Xk_hi, void* Xk_lo, void* Xv_hi, void* Xv_lo, int lo_fmt, int pe_at_index,
+                         int* lo8_flag, int map_fmt, void* stream);
 /* The same block on the second shape of the kernel (round 6, csrc/pe_x3b.hip): a wave owns 16 rows through both layers of each MLP, the hidden layer
  * stays in registers (no LDS image, no barrier between the layers), the weights go through a 4-deep LDS ring (LDS-DMA) shared by the 8 waves of a 128-row
  * block, two waves per SIMD.  Same operands EXCEPT that W1a and Wr (the first layers) are packed from the weight with its rows in the order
@@ -272,6 +287,11 @@ int mv2d_nchw_to_nhwc(const float* x, float* y, int V, int C, int HW, void* stre
 /* the same for the listed positions only: mask [V * HW] bytes (1 = some RoI's rectangle holds the position: mv2d_roi_positions* / mv2d_mask_compact's
  * roi_mask); unlisted rows of y are not written (HW, C multiples of 4; x, y 16-byte aligned) */
 int mv2d_nchw_to_nhwc_masked(const float* x, float* y, const unsigned char* mask, int V, int C, int HW, void* stream);
+/* Both with the element format of the map (map_fmt 0 = fp32, 1 = fp16, 2 = bf16; x and y share it): a 16-bit NCHW map becomes a 16-bit position-major
+ * map, 512 bytes per 256-channel row.  16-bit maps: 8-byte accesses (HW, C multiples of 4; x, y 8-byte aligned), otherwise -- unmasked form only --
+ * an element-wise tile kernel.  The fp32 entries above are these with map_fmt 0. */
+int mv2d_nchw_to_nhwc_fmt(const void* x, void* y, int V, int C, int HW, int map_fmt, void* stream);
+int mv2d_nchw_to_nhwc_masked_fmt(const void* x, void* y, const unsigned char* mask, int V, int C, int HW, int map_fmt, void* stream);
 
 /* "next" row f2 — the extra FPN level between the 2-D detector and the RoI head (mmdet FPN, start_level = end_level = 2, num_outs = 1:
  * configs/mv2d/exp/*:32-39, mmdet3d_plugin/models/detectors/mv2d.py:122-127): out = conv3x3(conv1x1(x) + b_lat) + b_fpn.
@@ -448,6 +468,11 @@ int mv2d_roi_align_ex(const float* map0, const float* map1, const float* rois, v
 int mv2d_roi_align_s(const float* map0, const float* map1, const float* rois, void* out0, void* out1, float* out0_f32, float* out1_f32,
                      int R, int H, int W, int channels, float spatial_scale, int sampling_ratio, const int* map1_index, int out1_is_sum,
                      void* out0_lo, void* out1_lo, void* out0_lo8, void* out1_lo8, int* lo8_flag, int roi_size, void* stream);
+/* mv2d_roi_align_s with the element format of map0, the feature map (map_fmt 0 = fp32, 1 = fp16, 2 = bf16: widened in registers, every output form
+ * bit for bit that of the fp32 entry on the widened map); map1, the PE map, stays fp32.  mv2d_roi_align_s is this entry with map_fmt 0. */
+int mv2d_roi_align_fmt(const void* map0, const float* map1, const float* rois, void* out0, void* out1, float* out0_f32, float* out1_f32,
+                       int R, int H, int W, int channels, float spatial_scale, int sampling_ratio, const int* map1_index, int out1_is_sum,
+                       void* out0_lo, void* out1_lo, void* out0_lo8, void* out1_lo8, int* lo8_flag, int roi_size, int map_fmt, void* stream);
 
 /* BoxCorrelation.epipolar_in_box, 'topk_matched:k:thr:ratio' (RH/utils/box_correlation.py:196-398).
  * V = views per sample; view_start[n_views+1]: first RoI of each view; trans [n_views,V,16] fp64 = lidar2img[b] @ inv(lidar2img[a])
@@ -516,6 +541,11 @@ int mv2d_pe_inputs(const int* s2pos, const int* S_dev, int S_max, const float* f
                    const double* coords_w, const double* coords_h, const double* coords_d, const float* embeds,
                    const float* dim_t, void* A_frustum, void* A_sine, void* Xf_k16, float* Xf_f32, float* A_frustum_f32,
                    float* A_sine_f32, int V, int h, int w, int depth_num, const double* position_range, void* stream);
+/* mv2d_pe_inputs with the element format of featcl (map_fmt 0 = fp32, 1 = fp16, 2 = bf16); Xf_f32, when given, receives the widened rows. */
+int mv2d_pe_inputs_fmt(const int* s2pos, const int* S_dev, int S_max, const void* featcl, const double* img2lidar,
+                       const double* coords_w, const double* coords_h, const double* coords_d, const float* embeds,
+                       const float* dim_t, void* A_frustum, void* A_sine, void* Xf_k16, float* Xf_f32, float* A_frustum_f32,
+                       float* A_sine_f32, int V, int h, int w, int depth_num, const double* position_range, int map_fmt, void* stream);
 
 /* NMSFreeCoder.decode_single + get_bboxes (CB/coders/nms_free_coder.py:49-102, CB/util.py:60-87,
  * RH/bbox_heads/cross_attention_head.py:357-377): top-k over R*num_classes logits, denormalise, centre-range filter.

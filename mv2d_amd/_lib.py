@@ -40,6 +40,8 @@ SIGNATURES = {
     'mv2d_pe_fused_tab': (I, [P, P, P, P, P, I] + [P] * 9 + [I, P, P, P]),
     'mv2d_pe_fused_tab2': (I, [P, P, P, P, P, I] + [P] * 9 + [I, P, P, I, P]),
     'mv2d_pe_fused_x3': (I, [P, P, P, P, I] + [P] * 13 + [I] + [P] * 5 + [I, I, P, P]),
+    'mv2d_pe_fused_tab_fmt': (I, [P, P, P, P, P, I] + [P] * 9 + [I, P, P, I, I, P]),
+    'mv2d_pe_fused_x3_fmt': (I, [P, P, P, P, I] + [P] * 13 + [I] + [P] * 5 + [I, I, P, I, P]),
     'mv2d_pe_fused_x3b': (I, [P, P, P, P, I] + [P] * 13 + [I] + [P] * 5 + [I, I, P, P]),
     'mv2d_key16_format': (I, []),
     'mv2d_f32_to_key16': (I, [P, P, P, LL, P]),
@@ -73,6 +75,8 @@ SIGNATURES = {
     'mv2d_f32_to_bf16': (I, [P, P, LL, P]),
     'mv2d_nchw_to_nhwc': (I, [P, P, I, I, I, P]),
     'mv2d_nchw_to_nhwc_masked': (I, [P, P, P, I, I, I, P]),
+    'mv2d_nchw_to_nhwc_fmt': (I, [P, P, I, I, I, I, P]),
+    'mv2d_nchw_to_nhwc_masked_fmt': (I, [P, P, P, I, I, I, I, P]),
     'mv2d_nchw_to_nhwc_bf16': (I, [P, P, I, I, I, P]),
     'mv2d_map_conv3x3': (I, [P, P, P, P, I, I, I, P]),
     'mv2d_self_attn_fwd': (I, [P, P, I, P, I, P]),
@@ -103,6 +107,7 @@ SIGNATURES = {
     'mv2d_roi_align': (I, [P, P, P, P, P, P, P, I, I, I, I, F, I, P, I, P]),
     'mv2d_roi_align_ex': (I, [P, P, P, P, P, P, P, I, I, I, I, F, I, P, I, P, P, P, P, P, P]),
     'mv2d_roi_align_s': (I, [P, P, P, P, P, P, P, I, I, I, I, F, I, P, I, P, P, P, P, P, I, P]),
+    'mv2d_roi_align_fmt': (I, [P, P, P, P, P, P, P, I, I, I, I, F, I, P, I, P, P, P, P, P, I, I, P]),
     'mv2d_box_correlation': (I, [P, P, P, P, P, P, I, I, I, I, I, I, I, F, F, F, I, P]),
     'mv2d_csr_workspace_bytes': (LL, [I, I, I, I]),
     'mv2d_mask_compact': (I, [P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, F, F, I, P]),
@@ -113,6 +118,7 @@ SIGNATURES = {
     'mv2d_roi_positions_csr_s': (I, [P, P, P, P, P, P, P, I, I, I, I, F, F, P, P, P, P, I, I, P, I, P, P, I, P]),
     'mv2d_frame_geometry': (I, [P, P, P, P, P, I, P, F, F, F, P, P, P, P, P, I, I, I, I, I, I, I, F, F, F, I, P, LL, P]),
     'mv2d_pe_inputs': (I, [P, P, I, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, P, P]),
+    'mv2d_pe_inputs_fmt': (I, [P, P, I, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, P, I, P]),
     'mv2d_pe_frustum_f32': (I, [P, P, I, P, P, P, P, P, I, I, I, I, P, P]),
     'mv2d_result_pack': (I, [P, P, P, P, F, I, P, P, P, P, I, I, P]),
     'mv2d_nms_bev': (I, [P, P, P, P, F, P, I, I, P]),

@@ -257,6 +257,52 @@ __device__ __forceinline__ void split_q16x4(const float4& v, uint2& hi, uint2& l
     split_q16x2(v.z, v.w, hi.y, lo.y);
 }
 
+// ------------------------------------------------------------------------------------------------------------------------------
+// Element formats of the stride-16 FEATURE MAP (the `map_fmt` argument of the *_fmt entries, include/mv2d_hip.h): 0 = fp32, 1 = IEEE fp16,
+// 2 = bf16.  A backbone under mixed precision hands the map over in 16 bits and the reference head widens it (`force_fp32` = x.float(), exact);
+// the kernels that read the position-major map are instantiated per element type and widen each element in registers, so their arithmetic --
+// and every result bit -- is that of the fp32 instance fed the widened map.  MapElem<MT>: raw4 = four consecutive elements as loaded (16 or
+// 8 bytes per lane), widen() = the exact conversion (v_cvt_f32_f16 keeps fp16 subnormals under the default kernel mode; bf16 is a shift).
+// For MT = float everything is the identity: the fp32 instances keep their instruction streams.
+// ------------------------------------------------------------------------------------------------------------------------------
+#define MV2D_MAP_F32 0
+#define MV2D_MAP_F16 1
+#define MV2D_MAP_BF16 2
+struct map_f16 { unsigned short u; };
+struct map_bf16 { unsigned short u; };
+template <class MT> struct MapElem;
+template <> struct MapElem<float> {
+    typedef float4 raw4;
+    static __device__ __forceinline__ const raw4& ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+    static __device__ __forceinline__ const float4& widen(const raw4& r) { return r; }      // (a reference: the uses read the loaded registers themselves)
+    static __device__ __forceinline__ float ld1(const float* p) { return *p; }
+};
+template <> struct MapElem<map_f16> {
+    typedef uint2 raw4;
+    static __device__ __forceinline__ raw4 ld4(const map_f16* p) { return *reinterpret_cast<const uint2*>(p); }
+    static __device__ __forceinline__ float4 widen(const raw4& r) {
+        typedef __attribute__((ext_vector_type(2))) _Float16 f16x2_cv;
+        const f16x2_cv a = __builtin_bit_cast(f16x2_cv, r.x), b = __builtin_bit_cast(f16x2_cv, r.y);
+        return make_float4((float)a[0], (float)a[1], (float)b[0], (float)b[1]);
+    }
+    static __device__ __forceinline__ float ld1(const map_f16* p) { return (float)__builtin_bit_cast(_Float16, p->u); }
+};
+template <> struct MapElem<map_bf16> {
+    typedef uint2 raw4;
+    static __device__ __forceinline__ raw4 ld4(const map_bf16* p) { return *reinterpret_cast<const uint2*>(p); }
+    static __device__ __forceinline__ float4 widen(const raw4& r) {
+        return make_float4(__uint_as_float(r.x << 16), __uint_as_float(r.x & 0xffff0000u), __uint_as_float(r.y << 16), __uint_as_float(r.y & 0xffff0000u));
+    }
+    static __device__ __forceinline__ float ld1(const map_bf16* p) { return bf16_to_f32(p->u); }
+};
+// host side: run `call` with MT bound to the element type of map_fmt (callers have checked 0 <= map_fmt <= 2)
+#define MV2D_MAP_DISPATCH(map_fmt, call)                                   \
+    do {                                                                   \
+        if ((map_fmt) == MV2D_MAP_F16) { typedef map_f16 MT; call; }       \
+        else if ((map_fmt) == MV2D_MAP_BF16) { typedef map_bf16 MT; call; } \
+        else { typedef float MT; call; }                                   \
+    } while (0)
+
 // ReLU that keeps NaN like torch.relu (fmaxf(NaN, 0) would return 0 and hide a poisoned row).  (An integer maximum with 0 on the bit pattern is one
 // instruction instead of two, but zeroes a NaN whose sign bit is set -- and the NaN rows of a fully masked query do carry it after the
 // LayerNorm: tests/test_gpu_golden.py::test_fully_masked_row_golden fails with it.  Round 4.)

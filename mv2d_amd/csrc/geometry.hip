@@ -149,9 +149,11 @@ __global__ __launch_bounds__(256) void posemb3d_kernel(const float* __restrict__
 //     maps: up to two [V*h*w, 256] fp32 maps (feature, PE) -> out key16 (fp16) [R, 49, 256] each (+ optional fp32)
 // ------------------------------------------------------------------------------------------------
 // SB > 0: SB x SB bins as a compile-time constant (7: the shipped configuration); SB = 0: s_rt x s_rt bins, 1 <= s_rt <= 14 (any RoI size of the
-// configs).  The 7x7 kernel below keeps its own signature and instruction stream; roi_align_s_kernel is the runtime-size instance.
-template <int SB>
-__device__ __forceinline__ void roi_align_body(const float* __restrict__ map0, const float* __restrict__ map1, const float* __restrict__ rois,
+// configs).  The 7x7 kernel below keeps its own signature and instruction stream (its fp32-map instance); roi_align_s_kernel is the runtime-size instance.
+// MT: element type of map0, the feature map (common.h MapElem: float, map_f16, map_bf16 -- widened in registers, same arithmetic); map1, the PE
+// map the engine produces itself, is always fp32.
+template <int SB, class MT>
+__device__ __forceinline__ void roi_align_body(const MT* __restrict__ map0, const float* __restrict__ map1, const float* __restrict__ rois,
                                                unsigned short* __restrict__ out0, unsigned short* __restrict__ out1,
                                                float* __restrict__ out0_f32, float* __restrict__ out1_f32, int H, int W,
                                                float spatial_scale, int sampling_ratio, const int* __restrict__ map1_index,
@@ -179,6 +181,7 @@ __device__ __forceinline__ void roi_align_body(const float* __restrict__ map0, c
     const long long vbase = (long long)v * H * W;
     const int nmaps = map1 ? 2 : 1;
     auto ld = [&](const float* m, long long q) { return *reinterpret_cast<const float4*>(m + q * C + c); };
+    auto ld0 = [&](long long q) { return MapElem<MT>::widen(MapElem<MT>::ld4(map0 + q * C + c)); };
     auto tap4 = [](float w1, const float4& a, float w2, const float4& bq, float w3, const float4& cq, float w4, const float4& d, float4& s) {
         s.x += w1 * a.x + w2 * bq.x + w3 * cq.x + w4 * d.x; s.y += w1 * a.y + w2 * bq.y + w3 * cq.y + w4 * d.y;
         s.z += w1 * a.z + w2 * bq.z + w3 * cq.z + w4 * d.z; s.w += w1 * a.w + w2 * bq.w + w3 * cq.w + w4 * d.w;
@@ -198,7 +201,7 @@ __device__ __forceinline__ void roi_align_body(const float* __restrict__ map0, c
                 const float w1 = hy * hx, w2 = hy * lx, w3 = ly * hx, w4 = ly * lx;
                 const long long q1 = vbase + (long long)yl * W + xl, q2 = vbase + (long long)yl * W + xh;
                 const long long q3 = vbase + (long long)yh * W + xl, q4 = vbase + (long long)yh * W + xh;
-                tap4(w1, ld(map0, q1), w2, ld(map0, q2), w3, ld(map0, q3), w4, ld(map0, q4), s0);
+                tap4(w1, ld0(q1), w2, ld0(q2), w3, ld0(q3), w4, ld0(q4), s0);
                 if (nmaps == 2) {
                     long long p1 = q1, p2 = q2, p3 = q3, p4 = q4;
                     if (map1_index) {   // map1 rows are compacted: row = map1_index[position]; -1 rows only ever carry weight 0
@@ -237,25 +240,27 @@ __device__ __forceinline__ void roi_align_body(const float* __restrict__ map0, c
     }
 }
 
-__global__ __launch_bounds__(256) void roi_align_kernel(const float* __restrict__ map0, const float* __restrict__ map1, const float* __restrict__ rois,
+template <class MT>
+__global__ __launch_bounds__(256) void roi_align_kernel(const MT* __restrict__ map0, const float* __restrict__ map1, const float* __restrict__ rois,
                                                         unsigned short* __restrict__ out0, unsigned short* __restrict__ out1,
                                                         float* __restrict__ out0_f32, float* __restrict__ out1_f32, int H, int W,
                                                         float spatial_scale, int sampling_ratio, const int* __restrict__ map1_index,
                                                         int out1_is_sum, int R, unsigned short* __restrict__ out0_lo,
                                                         unsigned short* __restrict__ out1_lo, unsigned char* __restrict__ out0_lo8,
                                                         unsigned char* __restrict__ out1_lo8, int* __restrict__ lo8_flag) {
-    roi_align_body<7>(map0, map1, rois, out0, out1, out0_f32, out1_f32, H, W, spatial_scale, sampling_ratio, map1_index, out1_is_sum, R, out0_lo,
+    roi_align_body<7, MT>(map0, map1, rois, out0, out1, out0_f32, out1_f32, H, W, spatial_scale, sampling_ratio, map1_index, out1_is_sum, R, out0_lo,
                       out1_lo, out0_lo8, out1_lo8, lo8_flag, 7);
 }
 
-__global__ __launch_bounds__(256) void roi_align_s_kernel(const float* __restrict__ map0, const float* __restrict__ map1, const float* __restrict__ rois,
+template <class MT>
+__global__ __launch_bounds__(256) void roi_align_s_kernel(const MT* __restrict__ map0, const float* __restrict__ map1, const float* __restrict__ rois,
                                                           unsigned short* __restrict__ out0, unsigned short* __restrict__ out1,
                                                           float* __restrict__ out0_f32, float* __restrict__ out1_f32, int H, int W,
                                                           float spatial_scale, int sampling_ratio, const int* __restrict__ map1_index,
                                                           int out1_is_sum, int R, unsigned short* __restrict__ out0_lo,
                                                           unsigned short* __restrict__ out1_lo, unsigned char* __restrict__ out0_lo8,
                                                           unsigned char* __restrict__ out1_lo8, int* __restrict__ lo8_flag, int s) {
-    roi_align_body<0>(map0, map1, rois, out0, out1, out0_f32, out1_f32, H, W, spatial_scale, sampling_ratio, map1_index, out1_is_sum, R, out0_lo,
+    roi_align_body<0, MT>(map0, map1, rois, out0, out1, out0_f32, out1_f32, H, W, spatial_scale, sampling_ratio, map1_index, out1_is_sum, R, out0_lo,
                       out1_lo, out0_lo8, out1_lo8, lo8_flag, s);
 }
 
@@ -980,8 +985,9 @@ __global__ __launch_bounds__(256) void pe_frustum_f32_kernel(const int* __restri
 // One wave per key position (4 per block): lane l moves channels 4l..4l+3 of the feature row with 16-byte accesses, computes depth
 // bin l of the frustum row (3 coordinates) and 6 sine channels; the two key16 (fp16) input rows (384 B, 768 B) are assembled in LDS and
 // written with 16-byte stores.  (Round 1: one block per position with 2- and 4-byte accesses ran at 2 TB/s of its 130 MB.)
-template <bool EXACT>      // EXACT: also the unrounded fp32 rows of the engine's index-exact validation mode (fp64 log, library sin / cos)
-__global__ __launch_bounds__(256) void pe_inputs_kernel(const int* __restrict__ s2pos, const int* __restrict__ S_dev, const float* __restrict__ featcl,
+// MT: element type of the feature map (common.h MapElem): a 16-bit row is one 8-byte load per lane, widened in registers.
+template <bool EXACT, class MT>      // EXACT: also the unrounded fp32 rows of the engine's index-exact validation mode (fp64 log, library sin / cos)
+__global__ __launch_bounds__(256) void pe_inputs_kernel(const int* __restrict__ s2pos, const int* __restrict__ S_dev, const MT* __restrict__ featcl,
                                                         const double* __restrict__ img2lidar, const double* __restrict__ coords_w, const double* __restrict__ coords_h,
                                                         const double* __restrict__ coords_d, const float* __restrict__ embeds, const float* __restrict__ dim_t,
                                                         unsigned short* __restrict__ A_frustum, unsigned short* __restrict__ A_sine, unsigned short* __restrict__ Xf_k16,
@@ -1000,7 +1006,7 @@ __global__ __launch_bounds__(256) void pe_inputs_kernel(const int* __restrict__ 
     unsigned short* si_row = rowbuf[wave] + 3 * 256;
     // feature row gather (fp32 kept for the K = feat + pe sum, key16 for the SE gate and the value rows)
     {
-        const float4 f = *reinterpret_cast<const float4*>(featcl + (long long)pos * C + 4 * lane);
+        const float4 f = MapElem<MT>::widen(MapElem<MT>::ld4(featcl + (long long)pos * C + 4 * lane));
         if (Xf_f32) *reinterpret_cast<float4*>(Xf_f32 + (long long)s * C + 4 * lane) = f;
         *reinterpret_cast<uint2*>(Xf_k16 + (long long)s * C + 4 * lane) = make_uint2(pack_k16x2(f.x, f.y), pack_k16x2(f.z, f.w));
     }
@@ -1349,25 +1355,45 @@ extern "C" int mv2d_posemb3d(const float* ref, const float* dim_t, float* posemb
 // RoI sizes of the size-taking entries: s x s bins, 1 <= s <= 14 (the S-path CSR, the conv + pool and the training kernels follow s)
 constexpr int ROI_SIZE_MAX = 14;
 
-extern "C" int mv2d_roi_align_s(const float* map0, const float* map1, const float* rois, void* out0, void* out1, float* out0_f32,
-                                float* out1_f32, int R, int H, int W, int channels, float spatial_scale, int sampling_ratio,
-                                const int* map1_index, int out1_is_sum, void* out0_lo, void* out1_lo, void* out0_lo8, void* out1_lo8, int* lo8_flag,
-                                int roi_size, void* stream) {
+template <class MT>
+static void roi_align_launch(const void* map0v, const float* map1, const float* rois, void* out0, void* out1, float* out0_f32, float* out1_f32, int R, int H,
+                             int W, float spatial_scale, int sampling_ratio, const int* map1_index, int out1_is_sum, void* out0_lo, void* out1_lo,
+                             void* out0_lo8, void* out1_lo8, int* lo8_flag, int roi_size, void* stream) {
+    const MT* map0 = (const MT*)map0v;
+    if (roi_size == 7)
+        hipLaunchKernelGGL(roi_align_kernel<MT>, dim3(56 * cdiv(R, 8)), dim3(256), 0, (hipStream_t)stream, map0, map1, rois, (unsigned short*)out0,
+                           (unsigned short*)out1, out0_f32, out1_f32, H, W, spatial_scale, sampling_ratio, map1_index, out1_is_sum, R,
+                           (unsigned short*)out0_lo, (unsigned short*)out1_lo, (unsigned char*)out0_lo8, (unsigned char*)out1_lo8, lo8_flag);
+    else
+        hipLaunchKernelGGL(roi_align_s_kernel<MT>, dim3(8 * roi_size * cdiv(R, 8)), dim3(256), 0, (hipStream_t)stream, map0, map1, rois, (unsigned short*)out0,
+                           (unsigned short*)out1, out0_f32, out1_f32, H, W, spatial_scale, sampling_ratio, map1_index, out1_is_sum, R,
+                           (unsigned short*)out0_lo, (unsigned short*)out1_lo, (unsigned char*)out0_lo8, (unsigned char*)out1_lo8, lo8_flag, roi_size);
+}
+
+// map_fmt: element format of map0 (common.h: 0 = fp32, 1 = fp16, 2 = bf16; 8-byte aligned rows for the 16-bit formats); map1 is fp32
+extern "C" int mv2d_roi_align_fmt(const void* map0, const float* map1, const float* rois, void* out0, void* out1, float* out0_f32,
+                                  float* out1_f32, int R, int H, int W, int channels, float spatial_scale, int sampling_ratio,
+                                  const int* map1_index, int out1_is_sum, void* out0_lo, void* out1_lo, void* out0_lo8, void* out1_lo8, int* lo8_flag,
+                                  int roi_size, int map_fmt, void* stream) {
     MV2D_CHECK_ARG(map0 && rois && channels == C, "mv2d_roi_align: needs 256-channel position-major maps");
     MV2D_CHECK_ARG(out0 || out0_f32, "mv2d_roi_align: no output");
     MV2D_CHECK_ARG((!(out0_lo || out0_lo8) || out0) && (!(out1_lo || out1_lo8) || out1), "mv2d_roi_align_ex: a lo output needs its key16 (hi) output");
     MV2D_CHECK_ARG(roi_size >= 1 && roi_size <= ROI_SIZE_MAX, "mv2d_roi_align_s: roi_size must be in [1, 14]");
+    MV2D_CHECK_ARG(map_fmt >= 0 && map_fmt <= 2, "mv2d_roi_align_fmt: map_fmt is 0 (fp32), 1 (fp16) or 2 (bf16)");
+    MV2D_CHECK_ARG(((uintptr_t)map0 & (map_fmt ? 7 : 15)) == 0, "mv2d_roi_align_fmt: map0 rows must be 16-byte (fp32) / 8-byte (16-bit) aligned");
     if (R == 0) return MV2D_OK;
-    if (roi_size == 7)
-        hipLaunchKernelGGL(roi_align_kernel, dim3(56 * cdiv(R, 8)), dim3(256), 0, (hipStream_t)stream, map0, map1, rois, (unsigned short*)out0,
-                           (unsigned short*)out1, out0_f32, out1_f32, H, W, spatial_scale, sampling_ratio, map1_index, out1_is_sum, R,
-                           (unsigned short*)out0_lo, (unsigned short*)out1_lo, (unsigned char*)out0_lo8, (unsigned char*)out1_lo8, lo8_flag);
-    else
-        hipLaunchKernelGGL(roi_align_s_kernel, dim3(8 * roi_size * cdiv(R, 8)), dim3(256), 0, (hipStream_t)stream, map0, map1, rois, (unsigned short*)out0,
-                           (unsigned short*)out1, out0_f32, out1_f32, H, W, spatial_scale, sampling_ratio, map1_index, out1_is_sum, R,
-                           (unsigned short*)out0_lo, (unsigned short*)out1_lo, (unsigned char*)out0_lo8, (unsigned char*)out1_lo8, lo8_flag, roi_size);
+    MV2D_MAP_DISPATCH(map_fmt, roi_align_launch<MT>(map0, map1, rois, out0, out1, out0_f32, out1_f32, R, H, W, spatial_scale, sampling_ratio, map1_index,
+                                                    out1_is_sum, out0_lo, out1_lo, out0_lo8, out1_lo8, lo8_flag, roi_size, stream));
     MV2D_LAUNCH_CHECK();
     return MV2D_OK;
+}
+
+extern "C" int mv2d_roi_align_s(const float* map0, const float* map1, const float* rois, void* out0, void* out1, float* out0_f32,
+                                float* out1_f32, int R, int H, int W, int channels, float spatial_scale, int sampling_ratio,
+                                const int* map1_index, int out1_is_sum, void* out0_lo, void* out1_lo, void* out0_lo8, void* out1_lo8, int* lo8_flag,
+                                int roi_size, void* stream) {
+    return mv2d_roi_align_fmt(map0, map1, rois, out0, out1, out0_f32, out1_f32, R, H, W, channels, spatial_scale, sampling_ratio, map1_index, out1_is_sum,
+                              out0_lo, out1_lo, out0_lo8, out1_lo8, lo8_flag, roi_size, MV2D_MAP_F32, stream);
 }
 
 extern "C" int mv2d_roi_align_ex(const float* map0, const float* map1, const float* rois, void* out0, void* out1, float* out0_f32,
@@ -1557,25 +1583,44 @@ extern "C" int mv2d_pe_frustum_f32(const int* s2pos, const int* S_dev, int S_max
     return MV2D_OK;
 }
 
-extern "C" int mv2d_pe_inputs(const int* s2pos, const int* S_dev, int S_max, const float* featcl, const double* img2lidar,
-                              const double* coords_w, const double* coords_h, const double* coords_d, const float* embeds,
-                              const float* dim_t, void* A_frustum, void* A_sine, void* Xf_k16, float* Xf_f32, float* A_frustum_f32,
-                              float* A_sine_f32, int V, int h, int w, int depth_num, const double* position_range, void* stream) {
-    MV2D_CHECK_ARG(s2pos && S_dev && featcl && img2lidar && coords_w && coords_h && coords_d && embeds && dim_t && A_frustum &&
-                       Xf_k16 && position_range, "mv2d_pe_inputs: null pointer");
-    MV2D_CHECK_ARG(A_sine || !A_sine_f32, "mv2d_pe_inputs: the exact rows need A_sine");
-    MV2D_CHECK_ARG(depth_num <= 256 && (depth_num % 8) == 0, "mv2d_pe_inputs: depth_num must be a multiple of 8, <= 256");
-    if (S_max == 0) return MV2D_OK;
-    MV2D_CHECK_ARG(A_frustum_f32 || !A_sine_f32, "mv2d_pe_inputs: fp32 sine rows only together with the fp32 frustum rows");
-#define MV2D_PEI(EX) hipLaunchKernelGGL(pe_inputs_kernel<EX>, dim3(cdiv(S_max, 4)), dim3(256), 0, (hipStream_t)stream, s2pos, S_dev, featcl, img2lidar, coords_w, \
+template <class MT>
+static void pe_inputs_launch(const int* s2pos, const int* S_dev, int S_max, const void* featcl, const double* img2lidar, const double* coords_w,
+                             const double* coords_h, const double* coords_d, const float* embeds, const float* dim_t, void* A_frustum, void* A_sine,
+                             void* Xf_k16, float* Xf_f32, float* A_frustum_f32, float* A_sine_f32, int V, int h, int w, int depth_num,
+                             const double* position_range, void* stream) {
+#define MV2D_PEI(EX) hipLaunchKernelGGL((pe_inputs_kernel<EX, MT>), dim3(cdiv(S_max, 4)), dim3(256), 0, (hipStream_t)stream, s2pos, S_dev, (const MT*)featcl, img2lidar, coords_w, \
                        coords_h, coords_d, embeds, dim_t, (unsigned short*)A_frustum, (unsigned short*)A_sine,                                      \
                        (unsigned short*)Xf_k16, Xf_f32, A_frustum_f32, A_sine_f32, h, w, V * h * w, depth_num, position_range[0], position_range[1], \
                        position_range[2], position_range[3] - position_range[0], position_range[4] - position_range[1],                               \
                        position_range[5] - position_range[2])
     if (A_frustum_f32) MV2D_PEI(true); else MV2D_PEI(false);
 #undef MV2D_PEI
+}
+
+// map_fmt: element format of featcl (common.h: 0 = fp32, 1 = fp16, 2 = bf16); Xf_f32, when given, holds the widened rows
+extern "C" int mv2d_pe_inputs_fmt(const int* s2pos, const int* S_dev, int S_max, const void* featcl, const double* img2lidar,
+                                  const double* coords_w, const double* coords_h, const double* coords_d, const float* embeds,
+                                  const float* dim_t, void* A_frustum, void* A_sine, void* Xf_k16, float* Xf_f32, float* A_frustum_f32,
+                                  float* A_sine_f32, int V, int h, int w, int depth_num, const double* position_range, int map_fmt, void* stream) {
+    MV2D_CHECK_ARG(s2pos && S_dev && featcl && img2lidar && coords_w && coords_h && coords_d && embeds && dim_t && A_frustum &&
+                       Xf_k16 && position_range, "mv2d_pe_inputs: null pointer");
+    MV2D_CHECK_ARG(A_sine || !A_sine_f32, "mv2d_pe_inputs: the exact rows need A_sine");
+    MV2D_CHECK_ARG(depth_num <= 256 && (depth_num % 8) == 0, "mv2d_pe_inputs: depth_num must be a multiple of 8, <= 256");
+    MV2D_CHECK_ARG(map_fmt >= 0 && map_fmt <= 2, "mv2d_pe_inputs_fmt: map_fmt is 0 (fp32), 1 (fp16) or 2 (bf16)");
+    if (S_max == 0) return MV2D_OK;
+    MV2D_CHECK_ARG(A_frustum_f32 || !A_sine_f32, "mv2d_pe_inputs: fp32 sine rows only together with the fp32 frustum rows");
+    MV2D_MAP_DISPATCH(map_fmt, pe_inputs_launch<MT>(s2pos, S_dev, S_max, featcl, img2lidar, coords_w, coords_h, coords_d, embeds, dim_t, A_frustum, A_sine,
+                                                    Xf_k16, Xf_f32, A_frustum_f32, A_sine_f32, V, h, w, depth_num, position_range, stream));
     MV2D_LAUNCH_CHECK();
     return MV2D_OK;
+}
+
+extern "C" int mv2d_pe_inputs(const int* s2pos, const int* S_dev, int S_max, const float* featcl, const double* img2lidar,
+                              const double* coords_w, const double* coords_h, const double* coords_d, const float* embeds,
+                              const float* dim_t, void* A_frustum, void* A_sine, void* Xf_k16, float* Xf_f32, float* A_frustum_f32,
+                              float* A_sine_f32, int V, int h, int w, int depth_num, const double* position_range, void* stream) {
+    return mv2d_pe_inputs_fmt(s2pos, S_dev, S_max, featcl, img2lidar, coords_w, coords_h, coords_d, embeds, dim_t, A_frustum, A_sine, Xf_k16, Xf_f32,
+                              A_frustum_f32, A_sine_f32, V, h, w, depth_num, position_range, MV2D_MAP_F32, stream);
 }
 
 extern "C" int mv2d_result_pack(const float* boxes, const float* scores, const long long* labels, const int* count, float score_thr, int max_num,

@@ -35,8 +35,9 @@ constexpr int OT_PITCH = 36;                                // floats per row of
 struct PFrag { uint4 u; };
 typedef unsigned int pt_u32x4 __attribute__((ext_vector_type(4)));   // staging registers (arrays of HIP's uint4 struct end up in scratch)
 
-struct PeTabParams {
-    const unsigned short* A1; const unsigned short* Xfb; const float* Xf32; const int* row_index; const int* m_dev; int M;
+template <class MT>         // MT: element type of the feature map Xf32 (common.h MapElem; the name dates from the fp32-only interface)
+struct PeTabParamsT {
+    const unsigned short* A1; const unsigned short* Xfb; const MT* Xf32; const int* row_index; const int* m_dev; int M;
     const unsigned short* W1a; const float* b1a; const unsigned short* W1b; const float* b1b;
     const unsigned short* Wr; const float* br; const unsigned short* We; const float* be;
     const float* sine_tab; int tab_period; float* pe; unsigned short* Xk;
@@ -138,8 +139,8 @@ __device__ __forceinline__ void layer1(PFrag (&wq)[S::RING][S::CT], PFrag (&a)[2
     __syncthreads();
 }
 
-template <class S>
-__global__ __launch_bounds__(S::NTHR, 2) void pe_tab_kernel(PeTabParams p) {
+template <class S, class MT>
+__global__ __launch_bounds__(S::NTHR, 2) void pe_tab_kernel(PeTabParamsT<MT> p) {
     constexpr int RT = S::RT, CT = S::CT, BM = S::BM, NTHR = S::NTHR;
     __shared__ __attribute__((aligned(16))) unsigned char smem[S::SMEM];
     unsigned char* As = smem;
@@ -254,12 +255,13 @@ __global__ __launch_bounds__(S::NTHR, 2) void pe_tab_kernel(PeTabParams p) {
     // ---- 3. pe = tab + (P1 + b) * gate, Xk = key16(pe + feat): through a wave-private LDS tile [BM rows][32 columns], then whole
     // 128-byte row pieces (the MFMA layout would store 16 rows x 16 bytes per instruction).  The feature and table rows of the first
     // 32 columns are requested before the gate math (their latency is this phase's floor).
-    float4 fv[NK], tv[NK];
+    typename MapElem<MT>::raw4 fv[NK];                 // as loaded (16-bit maps: 8 bytes), widened where it is used
+    float4 tv[NK];
     auto request = [&](int jp) {
         const long long gcol = wave * CT * 16 + jp * 32 + c4;
 #pragma unroll
         for (int k = 0; k < NK; ++k) {
-            if (p.Xk) fv[k] = *reinterpret_cast<const float4*>(p.Xf32 + (long long)ri[k] * C + gcol);   // (uniform: the S path has no use for Xk)
+            if (p.Xk) fv[k] = MapElem<MT>::ld4(p.Xf32 + (long long)ri[k] * C + gcol);   // (uniform: the S path has no use for Xk)
             tv[k] = *reinterpret_cast<const float4*>(p.sine_tab + (long long)(ri[k] % p.tab_period) * C + gcol);
         }
     };
@@ -297,9 +299,11 @@ __global__ __launch_bounds__(S::NTHR, 2) void pe_tab_kernel(PeTabParams p) {
             v = make_float4(v.x + tv[k].x, v.y + tv[k].y, v.z + tv[k].z, v.w + tv[k].w);
             if (m < M) {
                 if (p.pe) *reinterpret_cast<float4*>(p.pe + (long long)m * C + gcol) = v;
-                if (p.Xk)
+                if (p.Xk) {
+                    const float4& f = MapElem<MT>::widen(fv[k]);
                     *reinterpret_cast<uint2*>(p.Xk + (long long)m * C + gcol) =
-                        make_uint2(pack_k16x2(v.x + fv[k].x, v.y + fv[k].y), pack_k16x2(v.z + fv[k].z, v.w + fv[k].w));
+                        make_uint2(pack_k16x2(v.x + f.x, v.y + f.y), pack_k16x2(v.z + f.z, v.w + f.w));
+                }
             }
         }
         if (jp + 1 < CT / 2) request(jp + 1);
@@ -307,30 +311,65 @@ __global__ __launch_bounds__(S::NTHR, 2) void pe_tab_kernel(PeTabParams p) {
     }
 }
 
-template <class S>
-void launch(const PeTabParams& p, hipStream_t stream) {
-    hipLaunchKernelGGL(pe_tab_kernel<S>, dim3(cdiv(p.M, S::BM)), dim3(S::NTHR), 0, stream, p);
+template <class S, class MT>
+void launch(const PeTabParamsT<MT>& p, hipStream_t stream) {
+    hipLaunchKernelGGL((pe_tab_kernel<S, MT>), dim3(cdiv(p.M, S::BM)), dim3(S::NTHR), 0, stream, p);
+}
+
+template <class MT>
+void launch_fmt(const void* A1, const void* Xfb, const void* Xf32, const int* row_index, const int* m_dev, int M, const void* W1a, const float* b1a,
+                const void* W1b, const float* b1b, const void* Wr, const float* br, const void* We, const float* be, const float* sine_tab,
+                int tab_period, float* pe, void* Xk, int shape, hipStream_t st) {
+    PeTabParamsT<MT> p{(const unsigned short*)A1, (const unsigned short*)Xfb, (const MT*)Xf32, row_index, m_dev, M, (const unsigned short*)W1a, b1a,
+                       (const unsigned short*)W1b, b1b, (const unsigned short*)Wr, br, (const unsigned short*)We, be, sine_tab, tab_period, pe,
+                       (unsigned short*)Xk};
+    if (shape == 1) launch<Shape<6, 8, 2, 2, 4, 0>, MT>(p, st);
+    else launch<Shape<4, 4, 4, 1, 3, 0>, MT>(p, st);
 }
 
 }  // namespace
 
 // mv2d_pe_fused_tab (include/mv2d_hip.h) = shape 1; mv2d_pe_fused_tab2 exposes the shape for the kernel tests:
 // shape 1 = 96 rows x 8 waves, one block per CU (default); 0 = 64 rows x 4 waves, two blocks per CU (bit-identical, slower: 134 vs 110 us on 70 k rows)
+// The 16-bit-map instances are compiled in a translation unit of their own (pe_tab96_map16.hip includes this file with MV2D_PE_TAB_MAP16 defined and gets
+// the launcher below instead of the C entries): with them in this module hipcc allocates the registers of the fp32 instance differently (96 more
+// instructions, other spills) although its source is untouched -- and the fp32 instance keeps its instruction stream.
+__attribute__((visibility("hidden"))) void mv2d_pe_tab_map16(const void* A1, const void* Xfb, const void* Xf32, const int* row_index, const int* m_dev, int M,
+                                                             const void* W1a, const float* b1a, const void* W1b, const float* b1b, const void* Wr,
+                                                             const float* br, const void* We, const float* be, const float* sine_tab, int tab_period,
+                                                             float* pe, void* Xk, int shape, int map_fmt, void* stream);
+#ifdef MV2D_PE_TAB_MAP16
+void mv2d_pe_tab_map16(const void* A1, const void* Xfb, const void* Xf32, const int* row_index, const int* m_dev, int M, const void* W1a, const float* b1a,
+                       const void* W1b, const float* b1b, const void* Wr, const float* br, const void* We, const float* be, const float* sine_tab,
+                       int tab_period, float* pe, void* Xk, int shape, int map_fmt, void* stream) {
+    if (map_fmt == MV2D_MAP_F16)
+        launch_fmt<map_f16>(A1, Xfb, Xf32, row_index, m_dev, M, W1a, b1a, W1b, b1b, Wr, br, We, be, sine_tab, tab_period, pe, Xk, shape, (hipStream_t)stream);
+    else
+        launch_fmt<map_bf16>(A1, Xfb, Xf32, row_index, m_dev, M, W1a, b1a, W1b, b1b, Wr, br, We, be, sine_tab, tab_period, pe, Xk, shape, (hipStream_t)stream);
+}
+#else
+// mv2d_pe_fused_tab_fmt: the same with the element format of the feature map Xf32 (common.h: 0 = fp32, 1 = fp16, 2 = bf16)
+extern "C" int mv2d_pe_fused_tab_fmt(const void* A1, const void* Xfb, const void* Xf32, const int* row_index, const int* m_dev, int M,
+                                     const void* W1a, const float* b1a, const void* W1b, const float* b1b,
+                                     const void* Wr, const float* br, const void* We, const float* be,
+                                     const float* sine_tab, int tab_period, float* pe, void* Xk, int shape, int map_fmt, void* stream) {
+    MV2D_CHECK_ARG(A1 && Xfb && (Xf32 || !Xk) && W1a && b1a && W1b && b1b && Wr && br && We && be && sine_tab && (pe || Xk), "mv2d_pe_fused_tab: null pointer");
+    MV2D_CHECK_ARG(M >= 0 && tab_period > 0, "mv2d_pe_fused_tab: M must be >= 0 and tab_period > 0");
+    MV2D_CHECK_ARG(map_fmt >= 0 && map_fmt <= 2, "mv2d_pe_fused_tab_fmt: map_fmt is 0 (fp32), 1 (fp16) or 2 (bf16)");
+    if (M == 0) return MV2D_OK;
+    if (map_fmt == MV2D_MAP_F32)
+        launch_fmt<float>(A1, Xfb, Xf32, row_index, m_dev, M, W1a, b1a, W1b, b1b, Wr, br, We, be, sine_tab, tab_period, pe, Xk, shape, (hipStream_t)stream);
+    else
+        mv2d_pe_tab_map16(A1, Xfb, Xf32, row_index, m_dev, M, W1a, b1a, W1b, b1b, Wr, br, We, be, sine_tab, tab_period, pe, Xk, shape, map_fmt, stream);
+    MV2D_LAUNCH_CHECK();
+    return MV2D_OK;
+}
+
 extern "C" int mv2d_pe_fused_tab2(const void* A1, const void* Xfb, const float* Xf32, const int* row_index, const int* m_dev, int M,
                                   const void* W1a, const float* b1a, const void* W1b, const float* b1b,
                                   const void* Wr, const float* br, const void* We, const float* be,
                                   const float* sine_tab, int tab_period, float* pe, void* Xk, int shape, void* stream) {
-    MV2D_CHECK_ARG(A1 && Xfb && (Xf32 || !Xk) && W1a && b1a && W1b && b1b && Wr && br && We && be && sine_tab && (pe || Xk), "mv2d_pe_fused_tab: null pointer");
-    MV2D_CHECK_ARG(M >= 0 && tab_period > 0, "mv2d_pe_fused_tab: M must be >= 0 and tab_period > 0");
-    if (M == 0) return MV2D_OK;
-    PeTabParams p{(const unsigned short*)A1, (const unsigned short*)Xfb, Xf32, row_index, m_dev, M, (const unsigned short*)W1a, b1a,
-                  (const unsigned short*)W1b, b1b, (const unsigned short*)Wr, br, (const unsigned short*)We, be, sine_tab, tab_period, pe,
-                  (unsigned short*)Xk};
-    hipStream_t st = (hipStream_t)stream;
-    if (shape == 1) launch<Shape<6, 8, 2, 2, 4, 0>>(p, st);
-    else launch<Shape<4, 4, 4, 1, 3, 0>>(p, st);
-    MV2D_LAUNCH_CHECK();
-    return MV2D_OK;
+    return mv2d_pe_fused_tab_fmt(A1, Xfb, Xf32, row_index, m_dev, M, W1a, b1a, W1b, b1b, Wr, br, We, be, sine_tab, tab_period, pe, Xk, shape, MV2D_MAP_F32, stream);
 }
 
 extern "C" int mv2d_pe_fused_tab(const void* A1, const void* Xfb, const float* Xf32, const int* row_index, const int* m_dev, int M,
@@ -340,7 +379,9 @@ extern "C" int mv2d_pe_fused_tab(const void* A1, const void* Xfb, const float* X
     return mv2d_pe_fused_tab2(A1, Xfb, Xf32, row_index, m_dev, M, W1a, b1a, W1b, b1b, Wr, br, We, be, sine_tab, tab_period, pe, Xk, 1, stream);
 }
 
-#ifdef MV2D_PE_TRACE
+#endif  // MV2D_PE_TAB_MAP16
+
+#if defined(MV2D_PE_TRACE) && !defined(MV2D_PE_TAB_MAP16)
 extern "C" int mv2d_pe96_trace_read(long long* host, int n) {
     return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_pe96_trace), n * sizeof(long long)) == hipSuccess ? 0 : -2;
 }

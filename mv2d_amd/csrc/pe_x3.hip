@@ -41,8 +41,9 @@ static_assert(NW * BM * OT_PITCH * 4 <= 4 * IMG, "the waves' output tiles fit in
 typedef q16x8_t px_bf16x8;      // common.h "q16": fp16 pairs since round 5
 struct XFrag { uint4 h, l; };
 
-struct PeX3Params {
-    const float* A1; const float* Xmap; const int* row_index; const int* m_dev; int M;
+template <class MT>         // MT: element type of the feature map Xmap (common.h MapElem)
+struct PeX3ParamsT {
+    const float* A1; const MT* Xmap; const int* row_index; const int* m_dev; int M;
     const unsigned short* W1a_h; const unsigned short* W1a_l; const float* b1a; const unsigned short* W1b_h; const unsigned short* W1b_l; const float* b1b;
     const unsigned short* Wr_h; const unsigned short* Wr_l; const float* br; const unsigned short* We_h; const unsigned short* We_l; const float* be;
     const float* sine_tab; int tab_period;
@@ -165,12 +166,13 @@ __device__ __forceinline__ void layer1(XFrag (&wq)[RING][CT], XFrag (&a)[2][RT],
 
 // fp32 rows -> hi / lo LDS images: NCH 16-byte chunks (8 columns) per row, thread t moves float4 pieces (half a chunk each).  Two phases, so
 // that the loads can be in flight under MFMA work: stage_load issues them, stage_commit splits and writes the images.
-template <int NCH>
+// ET: element type of the rows (float, or a 16-bit feature map: the pieces stay in their 8-byte form until commit widens and splits them)
+template <int NCH, class ET = float>
 struct Stage {
     static constexpr int PIECES = BM * NCH * 2, PER = PIECES / NTHR;
     static_assert(PIECES % NTHR == 0, "");
-    float4 v[PER];
-    __device__ __forceinline__ void load(const float* __restrict__ src, long long ld, const int* __restrict__ ridx, int m0, int M, int tid) {
+    typename MapElem<ET>::raw4 v[PER];
+    __device__ __forceinline__ void load(const ET* __restrict__ src, long long ld, const int* __restrict__ ridx, int m0, int M, int tid) {
         // all row indices first, then all rows: written as one loop, the compiler waited for index i AND row i - 1 (vmcnt(0)) in front of every row -- PER
         // dependent round trips per block instead of two (round 6, tools/isa_waits.sh)
 #ifdef MV2D_PX_ROUND5_STAGE      // (timing A/B: the round-5 form)
@@ -179,7 +181,7 @@ struct Stage {
             const int c = tid + NTHR * i, row = c / (2 * NCH), piece = c - row * (2 * NCH);
             const int m = min(m0 + row, M - 1);
             const long long r = ridx ? ridx[m] : m;
-            v[i] = *reinterpret_cast<const float4*>(src + r * ld + piece * 4);
+            v[i] = MapElem<ET>::ld4(src + r * ld + piece * 4);
         }
 #else
         int r[PER];
@@ -192,7 +194,7 @@ struct Stage {
 #pragma unroll
         for (int i = 0; i < PER; ++i) {
             const int c = tid + NTHR * i, row = c / (2 * NCH), piece = c - row * (2 * NCH);
-            v[i] = *reinterpret_cast<const float4*>(src + (long long)r[i] * ld + piece * 4);
+            v[i] = MapElem<ET>::ld4(src + (long long)r[i] * ld + piece * 4);
         }
 #endif
     }
@@ -201,7 +203,8 @@ struct Stage {
         for (int i = 0; i < PER; ++i) {
             const int c = tid + NTHR * i, row = c / (2 * NCH), piece = c - row * (2 * NCH), chunk = piece >> 1;
             uint2 hv, lv;
-            split4(v[i].x, v[i].y, v[i].z, v[i].w, hv, lv);
+            const float4 f = MapElem<ET>::widen(v[i]);
+            split4(f.x, f.y, f.z, f.w, hv, lv);
             const int off = row * PITCH + ((chunk ^ (row & 15)) << 4) + (piece & 1) * 8;
             *reinterpret_cast<uint2*>(Lh + off) = hv;
             *reinterpret_cast<uint2*>(Ll + off) = lv;
@@ -221,12 +224,14 @@ struct Stage {
         const int c0_ = tid, c1_ = tid + NTHR;                                                             \
         const int ma_ = min(m0 + (c0_ >> 3), M - 1), mb_ = min(m0 + (c1_ >> 3), M - 1);                    \
         const long long ra_ = p.row_index ? p.row_index[ma_] : ma_, rb_ = p.row_index ? p.row_index[mb_] : mb_; \
-        touch0 = p.Xmap[ra_ * C + (c0_ & 7) * 32];                                                         \
-        touch1 = p.Xmap[rb_ * C + (c1_ & 7) * 32];                                                         \
+        touch0 = MapElem<MT>::ld1(p.Xmap + ra_ * C + (c0_ & (C / TOUCH_STEP - 1)) * TOUCH_STEP);                              \
+        touch1 = MapElem<MT>::ld1(p.Xmap + rb_ * C + (c1_ & (C / TOUCH_STEP - 1)) * TOUCH_STEP);                              \
         __builtin_amdgcn_sched_barrier(0);                                                                 \
     } while (0)
 
-__global__ __launch_bounds__(NTHR, 1) void pe_x3_kernel(PeX3Params p) {
+template <class MT>
+__global__ __launch_bounds__(NTHR, 1) void pe_x3_kernel(PeX3ParamsT<MT> p) {
+    constexpr int TOUCH_STEP = 128 / (int)sizeof(MT);   // elements per 128-byte cache line: the touch loads cover a row's lines
     __shared__ __attribute__((aligned(16))) unsigned char smem[SMEM];
     unsigned char* Ah = smem;
     unsigned char* Al = smem + IMG;
@@ -291,7 +296,7 @@ __global__ __launch_bounds__(NTHR, 1) void pe_x3_kernel(PeX3Params p) {
     PX_STAMP(7);
     // the feature rows of the tile (256 channels = 32 chunks per row, gathered through row_index) are requested a whole part ahead: they travel
     // under the MFMAs of layer 1 (stamps of the first version: 22 k of a block's 145 k cycles waited for them right here)
-    Stage<32> fs;
+    Stage<32, MT> fs;
     fs.load(p.Xmap, C, p.row_index, m0, M, tid);
 #ifndef MV2D_PX_ROUND5_STAGE
     __builtin_amdgcn_sched_barrier(0);                 // (without it hipcc sinks the 16 row loads to fs.commit below: 16 dependent round trips per block, tools/isa_waits.sh)
@@ -341,13 +346,14 @@ __global__ __launch_bounds__(NTHR, 1) void pe_x3_kernel(PeX3Params p) {
     }
     // the table rows (and, T path, the fp32 feature rows) of the first 32 output columns are requested before the gate's second layer
     const bool rows16 = p.Xk_hi != nullptr;
-    float4 tvq[NK], fvq[NK];
+    float4 tvq[NK];
+    typename MapElem<MT>::raw4 fvq[NK];                // as loaded, widened where it is used
     auto request = [&](int jp) {
         const long long gcol = wave * CT * 16 + jp * 32 + c4;
 #pragma unroll
         for (int k = 0; k < NK; ++k) {
             tvq[k] = *reinterpret_cast<const float4*>(p.sine_tab + (long long)(ri[k] % p.tab_period) * C + gcol);
-            if (rows16) fvq[k] = *reinterpret_cast<const float4*>(p.Xmap + (long long)ri[k] * C + gcol);
+            if (rows16) fvq[k] = MapElem<MT>::ld4(p.Xmap + (long long)ri[k] * C + gcol);
         }
     };
     request(0);
@@ -391,7 +397,7 @@ __global__ __launch_bounds__(NTHR, 1) void pe_x3_kernel(PeX3Params p) {
             if (m < M) {
                 if (p.pe) *reinterpret_cast<float4*>(p.pe + (long long)(p.pe_at_index ? ri[k] : m) * C + gcol) = v;
                 if (rows16) {
-                    const float4 f = fvq[k];
+                    const float4 f = MapElem<MT>::widen(fvq[k]);
                     uint2 h, l;
                     split_k16x2(v.x + f.x, v.y + f.y, h.x, l.x);
                     split_k16x2(v.z + f.z, v.w + f.w, h.y, l.y);
@@ -418,10 +424,24 @@ extern "C" int mv2d_px_trace_read(long long* host, int n) { return hipMemcpyFrom
 #endif
 
 // C-ABI: include/mv2d_hip.h
-extern "C" int mv2d_pe_fused_x3(const float* A1, const float* Xmap, const int* row_index, const int* m_dev, int M,
-                                const void* W1a_hi, const void* W1a_lo, const float* b1a, const void* W1b_hi, const void* W1b_lo, const float* b1b,
-                                const void* Wr_hi, const void* Wr_lo, const float* br, const void* We_hi, const void* We_lo, const float* be,
-                                const float* sine_tab, int tab_period, float* pe, void* Xk_hi, void* Xk_lo, void* Xv_hi, void* Xv_lo, int lo_fmt, int pe_at_index, int* lo8_flag, void* stream) {
+template <class MT>
+static void pe_x3_launch(const float* A1, const void* Xmap, const int* row_index, const int* m_dev, int M,
+                         const void* W1a_hi, const void* W1a_lo, const float* b1a, const void* W1b_hi, const void* W1b_lo, const float* b1b,
+                         const void* Wr_hi, const void* Wr_lo, const float* br, const void* We_hi, const void* We_lo, const float* be,
+                         const float* sine_tab, int tab_period, float* pe, void* Xk_hi, void* Xk_lo, void* Xv_hi, void* Xv_lo, int lo_fmt, int pe_at_index, int* lo8_flag, void* stream) {
+    PeX3ParamsT<MT> p{A1, (const MT*)Xmap, row_index, m_dev, M, (const unsigned short*)W1a_hi, (const unsigned short*)W1a_lo, b1a, (const unsigned short*)W1b_hi,
+                      (const unsigned short*)W1b_lo, b1b, (const unsigned short*)Wr_hi, (const unsigned short*)Wr_lo, br, (const unsigned short*)We_hi,
+                      (const unsigned short*)We_lo, be, sine_tab, tab_period, pe, (unsigned short*)Xk_hi, (unsigned short*)Xk_lo, (unsigned short*)Xv_hi,
+                      (unsigned short*)Xv_lo, lo_fmt, lo8_flag, pe_at_index};
+    hipLaunchKernelGGL(pe_x3_kernel<MT>, dim3(cdiv(M, BM)), dim3(NTHR), 0, (hipStream_t)stream, p);
+}
+
+// map_fmt: element format of the feature map Xmap (common.h: 0 = fp32, 1 = fp16, 2 = bf16)
+extern "C" int mv2d_pe_fused_x3_fmt(const float* A1, const void* Xmap, const int* row_index, const int* m_dev, int M,
+                                    const void* W1a_hi, const void* W1a_lo, const float* b1a, const void* W1b_hi, const void* W1b_lo, const float* b1b,
+                                    const void* Wr_hi, const void* Wr_lo, const float* br, const void* We_hi, const void* We_lo, const float* be,
+                                    const float* sine_tab, int tab_period, float* pe, void* Xk_hi, void* Xk_lo, void* Xv_hi, void* Xv_lo, int lo_fmt, int pe_at_index, int* lo8_flag,
+                                    int map_fmt, void* stream) {
     MV2D_CHECK_ARG(A1 && Xmap && W1a_hi && W1a_lo && b1a && W1b_hi && W1b_lo && b1b && Wr_hi && Wr_lo && br && We_hi && We_lo && be && sine_tab,
                    "mv2d_pe_fused_x3: null pointer");
     MV2D_CHECK_ARG(pe || Xk_hi, "mv2d_pe_fused_x3: no output");
@@ -430,13 +450,20 @@ extern "C" int mv2d_pe_fused_x3(const float* A1, const float* Xmap, const int* r
                    "mv2d_pe_fused_x3: the four key / value row outputs come together");
     MV2D_CHECK_ARG(M >= 0 && tab_period > 0, "mv2d_pe_fused_x3: M must be >= 0 and tab_period > 0");
     MV2D_CHECK_ARG(lo_fmt == 0 || lo_fmt == 1, "mv2d_pe_fused_x3: lo_fmt is 0 (key16 lo rows) or 1 (e4m3 lo rows)");
-    MV2D_CHECK_ARG(((uintptr_t)A1 & 15) == 0 && ((uintptr_t)Xmap & 15) == 0 && ((uintptr_t)sine_tab & 15) == 0, "mv2d_pe_fused_x3: rows must be 16-byte aligned");
+    MV2D_CHECK_ARG(map_fmt >= 0 && map_fmt <= 2, "mv2d_pe_fused_x3_fmt: map_fmt is 0 (fp32), 1 (fp16) or 2 (bf16)");
+    MV2D_CHECK_ARG(((uintptr_t)A1 & 15) == 0 && ((uintptr_t)Xmap & (map_fmt ? 7 : 15)) == 0 && ((uintptr_t)sine_tab & 15) == 0,
+                   "mv2d_pe_fused_x3: rows must be 16-byte aligned (a 16-bit map: 8-byte)");
     if (M == 0) return MV2D_OK;
-    PeX3Params p{A1, Xmap, row_index, m_dev, M, (const unsigned short*)W1a_hi, (const unsigned short*)W1a_lo, b1a, (const unsigned short*)W1b_hi,
-                 (const unsigned short*)W1b_lo, b1b, (const unsigned short*)Wr_hi, (const unsigned short*)Wr_lo, br, (const unsigned short*)We_hi,
-                 (const unsigned short*)We_lo, be, sine_tab, tab_period, pe, (unsigned short*)Xk_hi, (unsigned short*)Xk_lo, (unsigned short*)Xv_hi,
-                 (unsigned short*)Xv_lo, lo_fmt, lo8_flag, pe_at_index};
-    hipLaunchKernelGGL(pe_x3_kernel, dim3(cdiv(M, BM)), dim3(NTHR), 0, (hipStream_t)stream, p);
+    MV2D_MAP_DISPATCH(map_fmt, pe_x3_launch<MT>(A1, Xmap, row_index, m_dev, M, W1a_hi, W1a_lo, b1a, W1b_hi, W1b_lo, b1b, Wr_hi, Wr_lo, br, We_hi, We_lo, be, sine_tab,
+                                                tab_period, pe, Xk_hi, Xk_lo, Xv_hi, Xv_lo, lo_fmt, pe_at_index, lo8_flag, stream));
     MV2D_LAUNCH_CHECK();
     return MV2D_OK;
+}
+
+extern "C" int mv2d_pe_fused_x3(const float* A1, const float* Xmap, const int* row_index, const int* m_dev, int M,
+                                const void* W1a_hi, const void* W1a_lo, const float* b1a, const void* W1b_hi, const void* W1b_lo, const float* b1b,
+                                const void* Wr_hi, const void* Wr_lo, const float* br, const void* We_hi, const void* We_lo, const float* be,
+                                const float* sine_tab, int tab_period, float* pe, void* Xk_hi, void* Xk_lo, void* Xv_hi, void* Xv_lo, int lo_fmt, int pe_at_index, int* lo8_flag, void* stream) {
+    return mv2d_pe_fused_x3_fmt(A1, Xmap, row_index, m_dev, M, W1a_hi, W1a_lo, b1a, W1b_hi, W1b_lo, b1b, Wr_hi, Wr_lo, br, We_hi, We_lo, be, sine_tab, tab_period, pe,
+                                Xk_hi, Xk_lo, Xv_hi, Xv_lo, lo_fmt, pe_at_index, lo8_flag, MV2D_MAP_F32, stream);
 }

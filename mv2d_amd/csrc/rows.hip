@@ -130,13 +130,15 @@ __global__ void f32_to_key16_kernel(const float* __restrict__ x, unsigned short*
 }
 
 // NCHW fp32 [V,C,h*w] -> position-major [V*h*w, C] fp32 (LDS-tiled transpose, coalesced both ways)
-__global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const float* x, float* y, int V, int Cn, int HW) {
-    __shared__ float tile[32][33];
+// T = float, or unsigned short for a 16-bit map (fp16 and bf16 alike: the elements are moved, never interpreted)
+template <class T>
+__global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const T* x, T* y, int V, int Cn, int HW) {
+    __shared__ T tile[32][33];
     const int v = blockIdx.z, c0 = blockIdx.y * 32, p0 = blockIdx.x * 32;
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;   // 32 x 8
     for (int i = ty; i < 32; i += 8) {
         int c = c0 + i, p = p0 + tx;
-        tile[i][tx] = (c < Cn && p < HW) ? x[((long long)v * Cn + c) * HW + p] : 0.f;
+        tile[i][tx] = (c < Cn && p < HW) ? x[((long long)v * Cn + c) * HW + p] : T(0);
     }
     __syncthreads();
     for (int i = ty; i < 32; i += 8) {
@@ -211,6 +213,60 @@ __global__ __launch_bounds__(256) void nchw_to_nhwc64_masked_kernel(const float*
         if (p < HW && c < Cn && m[pl])
             *reinterpret_cast<float4*>(y + ((long long)v * HW + p) * Cn + c) =
                 make_float4(tile[tq * 4][pl], tile[tq * 4 + 1][pl], tile[tq * 4 + 2][pl], tile[tq * 4 + 3][pl]);
+    }
+}
+
+// The 64 x 64 transposition for 16-BIT maps (fp16 / bf16: 2-byte elements moved as they are), full and masked (MASKED: see above).  Needs HW % 4 == 0,
+// Cn % 4 == 0, 8-byte aligned x and y -- the fp32 kernel's rule, so the engine's choice between the masked and the full form does not depend on the
+// dtype.  A lane moves 4 elements = 8 bytes on both sides; 16 lanes cover a 128-byte line of one channel row (load) or of one position row (store: 64 of
+// the 256 channels of a 512-byte row).  LDS tile: 64 channel rows of 33 dwords (32 position PAIRS + 1).
+//   writes (two dwords per lane and row): the four rows of a wave are r, r + 1, r + 32, r + 33 with r even -- bank offsets 0, 33, 32, 1 (mod 64), each
+//     row taking 16 banks of one parity: 64 lanes, 64 different banks;
+//   reads (2-byte, channel 4 tq + j of position pl): dword (4 tq + j) * 33 + pl / 2 -- 4 * 33 = 4 (mod 64), so the 16 tq of a wave are 4 banks apart
+//     and its four consecutive pl add 0 or 1; the two lanes of a position pair read ONE dword (a broadcast, not a conflict).
+template <bool MASKED>
+__global__ __launch_bounds__(256) void nchw_to_nhwc64_h_kernel(const unsigned short* __restrict__ x, unsigned short* __restrict__ y,
+                                                              const unsigned char* __restrict__ mask, int V, int Cn, int HW) {
+    __shared__ unsigned int tile[64][33];
+    __shared__ unsigned char m[64];
+    __shared__ int any;
+    const int v = blockIdx.z, c0 = blockIdx.y * 64, p0 = blockIdx.x * 64;
+    if constexpr (MASKED) {
+        if (threadIdx.x == 0) any = 0;
+        __syncthreads();
+        if (threadIdx.x < 64) {
+            const int p = p0 + threadIdx.x;
+            const unsigned char b = p < HW ? mask[(long long)v * HW + p] : 0;
+            m[threadIdx.x] = b;
+            if (b) any = 1;
+        }
+        __syncthreads();
+        if (!any) return;
+    }
+    const int tq = threadIdx.x & 15, ty = threadIdx.x >> 4;
+    const int k = ty & 3, rw = (ty >> 2) * 2 + (k & 1) + 32 * (k >> 1);     // + 8 i: every row 0..63 once
+    uint2 in[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int c = c0 + rw + 8 * i, p = p0 + tq * 4;
+        in[i] = (c < Cn && p < HW) ? *reinterpret_cast<const uint2*>(x + ((long long)v * Cn + c) * HW + p) : make_uint2(0u, 0u);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        tile[rw + 8 * i][tq * 2] = in[i].x;
+        tile[rw + 8 * i][tq * 2 + 1] = in[i].y;
+    }
+    __syncthreads();
+    const unsigned short* t16 = reinterpret_cast<const unsigned short*>(&tile[0][0]);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int pl = ty + 16 * i, p = p0 + pl, c = c0 + tq * 4;
+        bool on = p < HW && c < Cn;
+        if constexpr (MASKED) on = on && m[pl];
+        if (on) {
+            const unsigned int e0 = t16[(tq * 4) * 66 + pl], e1 = t16[(tq * 4 + 1) * 66 + pl], e2 = t16[(tq * 4 + 2) * 66 + pl], e3 = t16[(tq * 4 + 3) * 66 + pl];
+            *reinterpret_cast<uint2*>(y + ((long long)v * HW + p) * Cn + c) = make_uint2(e0 | (e1 << 16), e2 | (e3 << 16));
+        }
     }
 }
 
@@ -315,25 +371,46 @@ extern "C" int mv2d_f32_to_key16(const float* x, void* hi, void* lo, long long n
     return MV2D_OK;
 }
 
-extern "C" int mv2d_nchw_to_nhwc_masked(const float* x, float* y, const unsigned char* mask, int V, int Cn, int HW, void* stream) {
+// map_fmt (common.h): 0 = fp32, 1 = fp16, 2 = bf16 -- x and y share it; the two 16-bit formats run the same kernels
+extern "C" int mv2d_nchw_to_nhwc_masked_fmt(const void* x, void* y, const unsigned char* mask, int V, int Cn, int HW, int map_fmt, void* stream) {
     MV2D_CHECK_ARG(x && y && mask && V > 0 && Cn > 0 && HW > 0, "mv2d_nchw_to_nhwc_masked: bad args");
-    MV2D_CHECK_ARG((HW % 4) == 0 && (Cn % 4) == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0,
-                   "mv2d_nchw_to_nhwc_masked: HW and C must be multiples of 4, x and y 16-byte aligned");
+    MV2D_CHECK_ARG(map_fmt >= 0 && map_fmt <= 2, "mv2d_nchw_to_nhwc_masked_fmt: map_fmt is 0 (fp32), 1 (fp16) or 2 (bf16)");
     dim3 grid(cdiv(HW, 64), cdiv(Cn, 64), V);
-    hipLaunchKernelGGL(nchw_to_nhwc64_masked_kernel, grid, dim3(256), 0, (hipStream_t)stream, x, y, mask, V, Cn, HW);
+    if (map_fmt == MV2D_MAP_F32) {
+        MV2D_CHECK_ARG((HW % 4) == 0 && (Cn % 4) == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0,
+                       "mv2d_nchw_to_nhwc_masked: HW and C must be multiples of 4, x and y 16-byte aligned");
+        hipLaunchKernelGGL(nchw_to_nhwc64_masked_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const float*)x, (float*)y, mask, V, Cn, HW);
+    } else {
+        MV2D_CHECK_ARG((HW % 4) == 0 && (Cn % 4) == 0 && ((uintptr_t)x & 7) == 0 && ((uintptr_t)y & 7) == 0,
+                       "mv2d_nchw_to_nhwc_masked_fmt: HW and C must be multiples of 4, 16-bit x and y 8-byte aligned");
+        hipLaunchKernelGGL(nchw_to_nhwc64_h_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, (const unsigned short*)x, (unsigned short*)y, mask, V, Cn, HW);
+    }
+    MV2D_LAUNCH_CHECK();
+    return MV2D_OK;
+}
+
+extern "C" int mv2d_nchw_to_nhwc_masked(const float* x, float* y, const unsigned char* mask, int V, int Cn, int HW, void* stream) {
+    return mv2d_nchw_to_nhwc_masked_fmt(x, y, mask, V, Cn, HW, MV2D_MAP_F32, stream);
+}
+
+extern "C" int mv2d_nchw_to_nhwc_fmt(const void* x, void* y, int V, int Cn, int HW, int map_fmt, void* stream) {
+    MV2D_CHECK_ARG(x && y && V > 0 && Cn > 0 && HW > 0, "mv2d_nchw_to_nhwc: bad args");
+    MV2D_CHECK_ARG(map_fmt >= 0 && map_fmt <= 2, "mv2d_nchw_to_nhwc_fmt: map_fmt is 0 (fp32), 1 (fp16) or 2 (bf16)");
+    const bool wide = (HW % 4) == 0 && (Cn % 4) == 0 && ((uintptr_t)x & (map_fmt ? 7 : 15)) == 0 && ((uintptr_t)y & (map_fmt ? 7 : 15)) == 0;
+    const dim3 grid = wide ? dim3(cdiv(HW, 64), cdiv(Cn, 64), V) : dim3(cdiv(HW, 32), cdiv(Cn, 32), V);
+    if (map_fmt == MV2D_MAP_F32) {
+        if (wide) hipLaunchKernelGGL(nchw_to_nhwc64_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const float*)x, (float*)y, V, Cn, HW);
+        else hipLaunchKernelGGL(nchw_to_nhwc_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)x, (float*)y, V, Cn, HW);
+    } else {
+        MV2D_CHECK_ARG(((uintptr_t)x & 1) == 0 && ((uintptr_t)y & 1) == 0, "mv2d_nchw_to_nhwc_fmt: 16-bit x and y must be 2-byte aligned");
+        if (wide) hipLaunchKernelGGL(nchw_to_nhwc64_h_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, (const unsigned short*)x, (unsigned short*)y,
+                                     (const unsigned char*)nullptr, V, Cn, HW);
+        else hipLaunchKernelGGL(nchw_to_nhwc_kernel<unsigned short>, grid, dim3(256), 0, (hipStream_t)stream, (const unsigned short*)x, (unsigned short*)y, V, Cn, HW);
+    }
     MV2D_LAUNCH_CHECK();
     return MV2D_OK;
 }
 
 extern "C" int mv2d_nchw_to_nhwc(const float* x, float* y, int V, int Cn, int HW, void* stream) {
-    MV2D_CHECK_ARG(x && y && V > 0 && Cn > 0 && HW > 0, "mv2d_nchw_to_nhwc: bad args");
-    if ((HW % 4) == 0 && (Cn % 4) == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0) {
-        dim3 grid(cdiv(HW, 64), cdiv(Cn, 64), V);
-        hipLaunchKernelGGL(nchw_to_nhwc64_kernel, grid, dim3(256), 0, (hipStream_t)stream, x, y, V, Cn, HW);
-    } else {
-        dim3 grid(cdiv(HW, 32), cdiv(Cn, 32), V);
-        hipLaunchKernelGGL(nchw_to_nhwc_kernel, grid, dim3(256), 0, (hipStream_t)stream, x, y, V, Cn, HW);
-    }
-    MV2D_LAUNCH_CHECK();
-    return MV2D_OK;
+    return mv2d_nchw_to_nhwc_fmt(x, y, V, Cn, HW, MV2D_MAP_F32, stream);
 }

@@ -38,6 +38,12 @@ def _t(x, device, dtype=None):
     return x.to(device).contiguous()
 
 
+def native_map(feat):
+    """The stride-16 map as the engine takes it: fp32, fp16 and bf16 maps are handed on as they are (a mixed-precision backbone's 16-bit map is
+    read natively, no fp32 copy); any other dtype is cast to fp32 as before."""
+    return feat if feat.dtype in ops.MAP_FMT else feat.float()
+
+
 class HeadEngine:
     def __init__(self, state_dict, kind, device, num_views=6, topk=None, expand_stride=None, num_layers=L_DEFAULT,
                  max_num=300, pc_range=(-51.2, -51.2, -5.0, 51.2, 51.2, 3.0),
@@ -265,18 +271,19 @@ class HeadEngine:
         return self.w[k]
 
     # ------------------------------------------------------------------------------------------ workspace
-    def _workspace(self, V, h, w, R, Vg=None):
+    def _workspace(self, V, h, w, R, Vg=None, map_dtype=F32):
         """Buffers of one (map shape, R) problem.  The number of RoIs changes from frame to frame in real use, so the STORAGE is
         allocated once per (map shape, R rounded up to a multiple of 32, at least 64) and every exact R only gets a dict of dense views into it
         (kernels index [*, R, *] tensors densely) plus its own hipGraph; staging buffers, calibration cache and the stream-order
         guard are shared by all R of a bucket."""
         Vg = V if Vg is None else Vg                     # views per sample; V = all views of the batch
-        key = (V, h, w, R, Vg, self.num_classes, self.roi_size)
+        # (the dtype of the feature map is part of both keys: ws['featcl'] has it, and a captured graph holds the launches of ONE element format)
+        key = (V, h, w, R, Vg, self.num_classes, self.roi_size, map_dtype)
         ws = self._ws.get(key)
         if ws is not None:
             return ws
         cap = max(64, -(-R // 32) * 32)
-        bkey = (V, h, w, cap, Vg, self.num_classes, self.roi_size)
+        bkey = (V, h, w, cap, Vg, self.num_classes, self.roi_size, map_dtype)
         base = self._ws_base.get(bkey)
         if base is None:
             store = []
@@ -288,7 +295,7 @@ class HeadEngine:
                     t = t.pin_memory()
                 store.append(t)
                 return t
-            self._build_ws(V, h, w, cap, alloc, Vg)
+            self._build_ws(V, h, w, cap, alloc, Vg, map_dtype)
             base = self._ws_base[bkey] = dict(store=store, shared={})
         it = iter(base['store'])
 
@@ -300,18 +307,18 @@ class HeadEngine:
             t = next(it)
             assert t.dtype == dt and t.numel() >= n
             return t.view(-1)[:n].view(shape)
-        ws = self._build_ws(V, h, w, R, view, Vg)
+        ws = self._build_ws(V, h, w, R, view, Vg, map_dtype)
         ws['shared'] = base['shared']
         self._ws[key] = ws
         return ws
 
-    def _build_ws(self, V, h, w, R, alloc, Vg):
+    def _build_ws(self, V, h, w, R, alloc, Vg, map_dtype=F32):
         d, L = self.dev, self.L
         P = V * h * w
         B = V // Vg                                      # samples sharing every launch
         e = lambda shape, dt=F32: alloc(shape, dt)
         z = lambda shape, dt=F32: alloc(shape, dt, zero=True)
-        ws = dict(P=P, B=B, Vg=Vg)
+        ws = dict(P=P, B=B, Vg=Vg, map_dtype=map_dtype)
         # calibration blob layout (fp64 tables first, then fp32, then bytes)
         lay, off = {}, 0
         for name, n, dt in [('viewK', V * 16, torch.float64), ('viewE', V * 16, torch.float64), ('img2lidar', V * 16, torch.float64),
@@ -337,7 +344,7 @@ class HeadEngine:
             ws['dt_rows' + sfx] = buf[o3:].view(F32)
         K16 = self.K16
         NC = self.cells                                  # RoI cells (s x s)
-        ws['featcl'] = e((P, C))
+        ws['featcl'] = e((P, C), map_dtype)               # position-major feature map in the INPUT's dtype (fp32 / fp16 / bf16): its readers widen in registers
         ws['enc'] = z((R, 1056)); ws['minv'] = e((R, 16))
         ws['roi_feat'] = e((R, NC, C), K16)
         ws['enc1'] = e((R, 512)); ws['enc2'] = e((R, C)); ws['center'] = e((R, 3))
@@ -421,7 +428,7 @@ class HeadEngine:
             self._shape_cache[skey] = sht
         return skey, sht
 
-    def _host_prepare(self, proposals_list, metas_list, V, h, w):
+    def _host_prepare(self, proposals_list, metas_list, V, h, w, map_dtype=F32):
         """Host side of one batch of samples: RoI lists + calibration tables into the workspace's pinned staging buffers.
         The camera matrices are compared with the previous frame's and, when they differ (every frame on the two-frame path: ego motion),
         the derived tables are rebuilt with batched calls and uploaded; the tables of the padding geometry only when the shapes change."""
@@ -443,7 +450,7 @@ class HeadEngine:
         # rows R..cap-1 are copies of the last RoI that belong to no sample (not in view_start / grp_start), so nothing attends to them,
         # nothing decodes them and the key set is unchanged; every R of a bucket shares one workspace and ONE captured graph.
         cap = max(64, -(-R // 32) * 32)
-        ws = self._workspace(V, h, w, cap, Vg)
+        ws = self._workspace(V, h, w, cap, Vg, map_dtype)
         sh = ws['shared']
         if 'done_ev' in sh:
             sh['done_ev'].synchronize()      # the previous frame on this workspace must have consumed the pinned staging buffers (its uploads have run)
@@ -886,7 +893,9 @@ class HeadEngine:
         return out
 
     def run(self, feat, proposals, img_metas, keep_stages=False, use_graph=False, payload=None):
-        """One sample.  feat [V,256,h,w] fp32 on the GPU (NCHW, or channels_last memory format); proposals list of [n,6].
+        """One sample.  feat [V,256,h,w] on the GPU, torch.float32, torch.float16 or torch.bfloat16 (NCHW, or channels_last memory format: zero-copy);
+        a 16-bit map is widened element by element inside the kernels that read it (the reference's force_fp32 = x.float(): exact), so the
+        results are bit for bit those of run(feat.float(), ...) and no fp32 copy of the map is made.  proposals list of [n,6].
         Enqueues the frame on the current stream; use_graph replays a captured hipGraph of the same shape.  payload (optional): fp32
         [1, max_num * 11 + 1] on the GPU -- the decode kernel also writes the wire row of the all-gather of decoded boxes (mv2d_amd.dist)
         there (its address is part of the graph key)."""
@@ -894,7 +903,7 @@ class HeadEngine:
 
     def run_batch(self, feats, proposals_list, metas_list, keep_stages=False, use_graph=False, payload=None):
         """Several samples through ONE sequence of launches (the reference runs one sample per call): feats = list of [V,256,h,w]
-        maps (or one stacked [B*V,256,h,w] tensor), proposals_list / metas_list = one entry per sample.  Outputs: cls / reg
+        maps (or one stacked [B*V,256,h,w] tensor; fp32, fp16 or bf16 like run's, one dtype per call), proposals_list / metas_list = one entry per sample.  Outputs: cls / reg
         [L,R_total,num_classes] / [L,R_total,10] with the samples' queries concatenated (out['grp_start']), boxes [B,max_num,9], scores, labels, count [B]."""
         return self._run(feats, proposals_list, metas_list, keep_stages, use_graph, batch=True, payload=payload)
 
@@ -906,7 +915,13 @@ class HeadEngine:
         stacked = torch.is_tensor(feats)
         fl = [feats] if stacked else list(feats)
         for f in fl:
-            assert f.is_cuda and f.dtype == F32 and f.dim() == 4 and f.shape[1] == C
+            assert f.is_cuda and f.dim() == 4 and f.shape[1] == C
+        map_dtype = fl[0].dtype
+        ops.map_format(map_dtype)                         # ValueError for anything but fp32 / fp16 / bf16
+        if any(f.dtype != map_dtype for f in fl):
+            raise ValueError(f'mv2d engine: the feature maps of a batch must share one dtype, got {sorted({str(f.dtype) for f in fl})}')
+        if map_dtype != F32 and self.pe_rows_in_waves and self.exact and 'pe' not in self.exact_skip:
+            raise ValueError('mv2d engine: pe_rows_in_waves (csrc/pe_x3b.hip) reads fp32 feature maps only; unset it for a torch.float16 / torch.bfloat16 map')
         if stacked or B == 1:
             feat = fl[0]
             if not (feat.is_contiguous(memory_format=torch.channels_last) and not feat.is_contiguous()):
@@ -921,7 +936,7 @@ class HeadEngine:
             V = Vg * B
             ptrs = tuple(f.data_ptr() for f in feat)
         assert V % B == 0
-        ws, R, sc = self._host_prepare(proposals_list, metas_list, V, h, w)
+        ws, R, sc = self._host_prepare(proposals_list, metas_list, V, h, w, map_dtype)
         # upload of the per-frame tables (RoI list, view / sample offsets, time steps): stream-ordered before the frame, outside the captured graph.
         # The "staging consumed" event stays at the END of the frame: recording it right behind this copy would let the host run a frame ahead on every
         # stream; measured in round 3: +1 % in long runs but 7400-7900 instead of 8300 samples/s in short ones -- without the host's wait the four
@@ -942,7 +957,7 @@ class HeadEngine:
             return dict(self._result(ws, R, keep_stages, batch), dt=sc['dt'])
         # the graph bakes in the input pointers (the producer's output buffers are static under graph replay) and the
         # frame scalars; anything else changing (RoI boxes, calibration tables, feature values) is data.
-        gkey = (ptrs, 0 if payload is None else payload.data_ptr(), sc['pad_h'], sc['pad_w'], sc['max_rows'], self.num_classes, self.roi_size, self._weights_version, self._stage_outputs, self.last_stage_heads,
+        gkey = (ptrs, map_dtype, 0 if payload is None else payload.data_ptr(), sc['pad_h'], sc['pad_w'], sc['max_rows'], self.num_classes, self.roi_size, self._weights_version, self._stage_outputs, self.last_stage_heads,
                 self.xattn_waves, self.fuse_maps, self.fuse_xattn, self.group_xattn, self.lo8_rows, self.pe_at_positions, self.pe_rows_in_waves, self.fold_sa0, self.masked_transpose, self.keep_sine_rows, self.force_nc, self.q_order,
                 self.fork_qg, self.exact_skip, self.ablate_zero_lo, self.stop_before_decoder)   # load_state() re-allocates the weights; every route option of __init__ is in the key
         graphs = ws.setdefault('graphs', {})             # one graph per (input buffers, frame scalars): a producer that alternates between
@@ -1004,9 +1019,9 @@ class HeadEngine:
                 fin = ws['feat_in']
                 fin0 = fin[0] if isinstance(fin, (list, tuple)) else fin
                 if fin0.is_contiguous(memory_format=torch.channels_last) and not fin0.is_contiguous():
-                    f0 = fin0.permute(0, 2, 3, 1).reshape(-1, C)[:1].contiguous()
+                    f0 = fin0.permute(0, 2, 3, 1).reshape(-1, C)[:1].float().contiguous()
                 else:
-                    f0 = fin0[0, :, 0, 0].reshape(1, C).contiguous()
+                    f0 = fin0[0, :, 0, 0].reshape(1, C).float().contiguous()     # (one row of a 16-bit map, widened: the map itself is never copied)
                 def mlp1(x32, n1, n2, **kw):
                     h3 = o.gemm_bf16(o.split3_rows(x32), self._c3(n1), W_['pe_b' + n1[1:]], act=1, split3=True)
                     return o.gemm_bf16(h3, self._c3(n2), W_['pe_b' + n2[1:]], out_dtype=F32, **kw)

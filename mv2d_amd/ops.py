@@ -64,6 +64,28 @@ def _lo_fmt(*los):
     return 0
 
 
+# element formats of the stride-16 feature map (csrc/common.h, the `map_fmt` argument of the *_fmt entries of include/mv2d_hip.h)
+MAP_FMT = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
+
+
+def map_format(dtype):
+    """map_fmt of a feature-map dtype: 0 = torch.float32, 1 = torch.float16, 2 = torch.bfloat16; any other dtype is refused."""
+    fmt = MAP_FMT.get(dtype)
+    if fmt is None:
+        raise ValueError(f'feature map of dtype {dtype}: the accepted dtypes are torch.float32, torch.float16 and torch.bfloat16')
+    return fmt
+
+
+def _req_map(t, name, map_fmt=None):
+    """The feature-map argument of a kernel that takes fp32 / fp16 / bf16 maps: returns its map_fmt.  A caller that states map_fmt itself
+    (a buffer it allocated for a known format) gets an error when the tensor's dtype disagrees, not a kernel reading the wrong element size."""
+    fmt = map_format(t.dtype)
+    if map_fmt is not None and int(map_fmt) != fmt:
+        raise _lib.Mv2dHipError(f'{name}: map_fmt {map_fmt} stated for a map of dtype {t.dtype} (map_fmt {fmt})')
+    _req(t, t.dtype, name)
+    return fmt
+
+
 LO8_SCALE = 4096.0            # csrc/common.h "lo8": byte = e4m3(key16_lo * 2^12)
 
 
@@ -415,25 +437,34 @@ def finalize_reg(reg, ref, L, R, pc_range_host, dt=0.0):
     check(_lib.load().mv2d_finalize_reg(_p(reg), _p(ref), L, R, pc_range_host.data_ptr(), float(dt), _stream()), 'mv2d_finalize_reg')
 
 
-def pe_fused_tab(A1, Xfb, Xf32, m_dev, wp, sine_tab, tab_period, pe, Xk, M=None, row_index=None, shape=1):
+def pe_fused_tab(A1, Xfb, Xf32, m_dev, wp, sine_tab, tab_period, pe, Xk, M=None, row_index=None, shape=1, map_fmt=None):
     """The PE block of the key side in one launch: pe = sine_tab[position] + position_encoder(A1) * gate(Xf), Xk = key16(pe + Xf32).
     wp: dict with the fragment-major key16 weights 'w1a','w1b','wr','we' (pack_key16) and fp32 biases 'b1a','b1b','br','be'; sine_tab
     [tab_period,256] fp32 (map position -> adapt_pos3d(sine) + bias).  Xk may be None (S path: only pe is needed; the feature rows are then
-    not read), pe may be None when Xk is given (T path).  shape: 1 = 96-row blocks (default), 0 = 64-row blocks (bit-identical)."""
-    _req16(A1, 'A1'); _req16(Xfb, 'Xfb'); _req(Xf32, torch.float32, 'Xf32'); _req(sine_tab, torch.float32, 'sine_tab'); _req16(Xk, 'Xk')
+    not read), pe may be None when Xk is given (T path).  shape: 1 = 96-row blocks (default), 0 = 64-row blocks (bit-identical).
+    Xf32 is the feature map, fp32, fp16 or bf16 (widened in the kernel: the results are those of the fp32 map Xf32.float())."""
+    _req16(A1, 'A1'); _req16(Xfb, 'Xfb'); _req(sine_tab, torch.float32, 'sine_tab'); _req16(Xk, 'Xk')
+    fmt = 0 if Xf32 is None else _req_map(Xf32, 'Xf32', map_fmt)
     M = A1.shape[0] if M is None else M
+    if fmt:
+        check(_lib.load().mv2d_pe_fused_tab_fmt(_p(A1), _p(Xfb), _p(Xf32), _p(row_index), _p(m_dev), M, _p(wp['w1a']), _p(wp['b1a']), _p(wp['w1b']),
+                                                _p(wp['b1b']), _p(wp['wr']), _p(wp['br']), _p(wp['we']), _p(wp['be']), _p(sine_tab), int(tab_period),
+                                                _p(pe), _p(Xk), int(shape), fmt, _stream()), 'mv2d_pe_fused_tab_fmt')
+        return pe, Xk
     check(_lib.load().mv2d_pe_fused_tab2(_p(A1), _p(Xfb), _p(Xf32), _p(row_index), _p(m_dev), M, _p(wp['w1a']), _p(wp['b1a']), _p(wp['w1b']),
                                          _p(wp['b1b']), _p(wp['wr']), _p(wp['br']), _p(wp['we']), _p(wp['be']), _p(sine_tab), int(tab_period),
                                          _p(pe), _p(Xk), int(shape), _stream()), 'mv2d_pe_fused_tab')
     return pe, Xk
 
 
-def pe_fused_x3(A1, Xmap, m_dev, wx, sine_tab, tab_period, pe=None, Xk=None, Xv=None, M=None, row_index=None, pe_at_index=False, lo8_flag=None):
-    """The PE block in split precision on unrounded inputs (index-exact route, csrc/pe_x3.hip).  A1 [M,192] fp32; Xmap fp32 feature rows
-    (indexed by row_index when given); wx: dict 'w1a','w1b','wr','we' = pack_x3(weight) pairs + fp32 biases 'b1a','b1b','br','be'; pe [M,256]
+def pe_fused_x3(A1, Xmap, m_dev, wx, sine_tab, tab_period, pe=None, Xk=None, Xv=None, M=None, row_index=None, pe_at_index=False, lo8_flag=None,
+                map_fmt=None):
+    """The PE block in split precision on unrounded inputs (index-exact route, csrc/pe_x3.hip).  A1 [M,192] fp32; Xmap feature rows, fp32, fp16 or
+    bf16 (widened in the kernel; indexed by row_index when given); wx: dict 'w1a','w1b','wr','we' = pack_x3(weight) pairs + fp32 biases 'b1a','b1b','br','be'; pe [M,256]
     fp32 and / or Xk = (hi, lo), Xv = (hi, lo) key16 [M,256] pairs (key rows pe + feat, value rows feat).  pe_at_index: pe row m goes to row
     row_index[m] of `pe` (a position-indexed map for roi_align without map1_index)."""
-    _req(A1, torch.float32, 'A1'); _req(Xmap, torch.float32, 'Xmap'); _req(sine_tab, torch.float32, 'sine_tab'); _req(pe, torch.float32, 'pe')
+    _req(A1, torch.float32, 'A1'); _req(sine_tab, torch.float32, 'sine_tab'); _req(pe, torch.float32, 'pe')
+    fmt = _req_map(Xmap, 'Xmap', map_fmt)
     _req(row_index, torch.int32, 'row_index'); _req(m_dev, torch.int32, 'm_dev')
     for pair in (Xk, Xv):
         if pair is not None:
@@ -443,6 +474,13 @@ def pe_fused_x3(A1, Xmap, m_dev, wx, sine_tab, tab_period, pe=None, Xk=None, Xv=
         _req(wx[k][0], q16_dtype(), k); _req(wx[k][1], q16_dtype(), k)
     M = A1.shape[0] if M is None else M
     xk, xv = Xk or (None, None), Xv or (None, None)
+    if fmt:
+        check(_lib.load().mv2d_pe_fused_x3_fmt(_p(A1), _p(Xmap), _p(row_index), _p(m_dev), M, _p(wx['w1a'][0]), _p(wx['w1a'][1]), _p(wx['b1a']),
+                                               _p(wx['w1b'][0]), _p(wx['w1b'][1]), _p(wx['b1b']), _p(wx['wr'][0]), _p(wx['wr'][1]), _p(wx['br']),
+                                               _p(wx['we'][0]), _p(wx['we'][1]), _p(wx['be']), _p(sine_tab), int(tab_period), _p(pe), _p(xk[0]), _p(xk[1]),
+                                               _p(xv[0]), _p(xv[1]), lo_fmt, 1 if (pe_at_index and row_index is not None) else 0, _p(lo8_flag), fmt,
+                                               _stream()), 'mv2d_pe_fused_x3_fmt')
+        return pe
     check(_lib.load().mv2d_pe_fused_x3(_p(A1), _p(Xmap), _p(row_index), _p(m_dev), M, _p(wx['w1a'][0]), _p(wx['w1a'][1]), _p(wx['b1a']),
                                        _p(wx['w1b'][0]), _p(wx['w1b'][1]), _p(wx['b1b']), _p(wx['wr'][0]), _p(wx['wr'][1]), _p(wx['br']),
                                        _p(wx['we'][0]), _p(wx['we'][1]), _p(wx['be']), _p(sine_tab), int(tab_period), _p(pe), _p(xk[0]), _p(xk[1]),
@@ -453,7 +491,7 @@ def pe_fused_x3(A1, Xmap, m_dev, wx, sine_tab, tab_period, pe=None, Xk=None, Xv=
 def pe_fused_x3b(A1, Xmap, m_dev, wx, sine_tab, tab_period, pe=None, Xk=None, Xv=None, M=None, row_index=None, pe_at_index=False, lo8_flag=None):
     """pe_fused_x3 on the second shape of the kernel (csrc/pe_x3b.hip: a wave owns 16 rows through both layers, the hidden layer stays in registers, the
     weights go through an LDS ring): bitwise the same outputs.  wx additionally holds 'w1a_p', 'wr_p' = pack_x3_rowperm of the two first-layer weights."""
-    _req(A1, torch.float32, 'A1'); _req(Xmap, torch.float32, 'Xmap'); _req(sine_tab, torch.float32, 'sine_tab'); _req(pe, torch.float32, 'pe')
+    _req(A1, torch.float32, 'A1'); _req(Xmap, torch.float32, 'Xmap (pe_fused_x3b has no 16-bit-map instance)'); _req(sine_tab, torch.float32, 'sine_tab'); _req(pe, torch.float32, 'pe')
     _req(row_index, torch.int32, 'row_index'); _req(m_dev, torch.int32, 'm_dev')
     for pair in (Xk, Xv):
         if pair is not None:
@@ -548,14 +586,23 @@ def map_conv3x3(x_cl, Wp, bias, V, h, w, out=None):
     return out
 
 
-def nchw_to_nhwc(x, out=None, mask=None):
-    """[V,C,h,w] fp32 -> position-major [V*h*w, C] fp32.  mask (uint8 [V*h*w], device; needs `out`): only the rows whose byte is set are written."""
-    _req(x, torch.float32, 'x'); _req(mask, torch.uint8, 'mask')
+def nchw_to_nhwc(x, out=None, mask=None, map_fmt=None):
+    """[V,C,h,w] -> position-major [V*h*w, C] of the same dtype (fp32, fp16 or bf16).  mask (uint8 [V*h*w], device; needs `out`): only the rows whose
+    byte is set are written."""
+    fmt = _req_map(x, 'x', map_fmt)
+    _req(mask, torch.uint8, 'mask')
     V, Cn, h, w = x.shape
     if out is None:
         if mask is not None:
             raise _lib.Mv2dHipError('nchw_to_nhwc: the masked form writes into a caller-owned buffer')
-        out = torch.empty((V * h * w, Cn), device=x.device, dtype=torch.float32)
+        out = torch.empty((V * h * w, Cn), device=x.device, dtype=x.dtype)
+    _req(out, x.dtype, 'out')
+    if fmt:
+        if mask is not None:
+            check(_lib.load().mv2d_nchw_to_nhwc_masked_fmt(_p(x), _p(out), _p(mask), V, Cn, h * w, fmt, _stream()), 'mv2d_nchw_to_nhwc_masked_fmt')
+        else:
+            check(_lib.load().mv2d_nchw_to_nhwc_fmt(_p(x), _p(out), V, Cn, h * w, fmt, _stream()), 'mv2d_nchw_to_nhwc_fmt')
+        return out
     if mask is not None:
         check(_lib.load().mv2d_nchw_to_nhwc_masked(_p(x), _p(out), _p(mask), V, Cn, h * w, _stream()), 'mv2d_nchw_to_nhwc_masked')
     else:
@@ -851,12 +898,20 @@ def posemb3d(ref, dim_t, out=None):
 
 def roi_align(map0, rois, H, W, *, map1=None, out0=None, out1=None, out0_f32=None, out1_f32=None, spatial_scale=1.0 / 16,
               sampling_ratio=-1, map1_index=None, out1_is_sum=False, R=None, out0_lo=None, out1_lo=None, out0_lo8=None, out1_lo8=None, lo8_flag=None,
-              roi_size=7):
-    """roi_size s (1..14): s x s bins, every output [R, s*s, 256]; 7 runs the 7x7 entry mv2d_roi_align_ex."""
-    _req(map0, torch.float32, 'map0'); _req(map1, torch.float32, 'map1'); _req(rois, torch.float32, 'rois')
+              roi_size=7, map_fmt=None):
+    """roi_size s (1..14): s x s bins, every output [R, s*s, 256]; 7 runs the 7x7 entry mv2d_roi_align_ex.  map0 (the feature map) is fp32, fp16 or
+    bf16 -- a 16-bit map is widened in the kernel (mv2d_roi_align_fmt), the outputs are those of map0.float(); map1 (the PE map) is fp32."""
+    fmt = _req_map(map0, 'map0', map_fmt)
+    _req(map1, torch.float32, 'map1'); _req(rois, torch.float32, 'rois')
     _req16(out0, 'out0'); _req16(out1, 'out1'); _req16(out0_lo, 'out0_lo'); _req16(out1_lo, 'out1_lo')
     _req(out0_lo8, torch.uint8, 'out0_lo8'); _req(out1_lo8, torch.uint8, 'out1_lo8'); _req(lo8_flag, torch.int32, 'lo8_flag')
     s = _roi_size(roi_size)
+    if fmt:
+        check(_lib.load().mv2d_roi_align_fmt(_p(map0), _p(map1), _p(rois), _p(out0), _p(out1), _p(out0_f32), _p(out1_f32),
+                                             rois.shape[0] if R is None else R, H, W, map0.shape[-1], spatial_scale, sampling_ratio,
+                                             _p(map1_index), 1 if out1_is_sum else 0, _p(out0_lo), _p(out1_lo), _p(out0_lo8), _p(out1_lo8), _p(lo8_flag), s,
+                                             fmt, _stream()), 'mv2d_roi_align_fmt')
+        return
     if s != 7:
         check(_lib.load().mv2d_roi_align_s(_p(map0), _p(map1), _p(rois), _p(out0), _p(out1), _p(out0_f32), _p(out1_f32),
                                            rois.shape[0] if R is None else R, H, W, map0.shape[-1], spatial_scale, sampling_ratio,
@@ -935,10 +990,17 @@ def csr_from_corr(match, row_ptr, col_idx, nnz_out, R, V, topk, roi_size=7):
 
 
 def pe_inputs(s2pos, S_dev, S_max, featcl, img2lidar, coords_w, coords_h, coords_d, embeds, dim_t, A_frustum, A_sine, Xf_k16,
-              Xf_f32, V, h, w, depth_num, position_range_host, A_frustum_f32=None, A_sine_f32=None):
-    """A_frustum [S,3D], A_sine [S,384] (may be None), Xf_k16 [S,256]: key16 rows; *_f32: the same rows unrounded (optional)."""
+              Xf_f32, V, h, w, depth_num, position_range_host, A_frustum_f32=None, A_sine_f32=None, map_fmt=None):
+    """A_frustum [S,3D], A_sine [S,384] (may be None), Xf_k16 [S,256]: key16 rows; *_f32: the same rows unrounded (optional).  featcl: the
+    position-major feature map, fp32, fp16 or bf16 (widened in the kernel)."""
     _req16(A_frustum, 'A_frustum'); _req16(A_sine, 'A_sine'); _req16(Xf_k16, 'Xf_k16')
-    _req(A_frustum_f32, torch.float32, 'A_frustum_f32'); _req(A_sine_f32, torch.float32, 'A_sine_f32')
+    _req(A_frustum_f32, torch.float32, 'A_frustum_f32'); _req(A_sine_f32, torch.float32, 'A_sine_f32'); _req(Xf_f32, torch.float32, 'Xf_f32')
+    fmt = _req_map(featcl, 'featcl', map_fmt)
+    if fmt:
+        check(_lib.load().mv2d_pe_inputs_fmt(_p(s2pos), _p(S_dev), S_max, _p(featcl), _p(img2lidar), _p(coords_w), _p(coords_h), _p(coords_d),
+                                             _p(embeds), _p(dim_t), _p(A_frustum), _p(A_sine), _p(Xf_k16), _p(Xf_f32), _p(A_frustum_f32),
+                                             _p(A_sine_f32), V, h, w, depth_num, position_range_host.data_ptr(), fmt, _stream()), 'mv2d_pe_inputs_fmt')
+        return
     check(_lib.load().mv2d_pe_inputs(_p(s2pos), _p(S_dev), S_max, _p(featcl), _p(img2lidar), _p(coords_w), _p(coords_h), _p(coords_d),
                                      _p(embeds), _p(dim_t), _p(A_frustum), _p(A_sine), _p(Xf_k16), _p(Xf_f32), _p(A_frustum_f32),
                                      _p(A_sine_f32), V, h, w, depth_num, position_range_host.data_ptr(), _stream()), 'mv2d_pe_inputs')

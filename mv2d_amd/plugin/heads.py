@@ -15,7 +15,7 @@ import torch
 import torch.nn as nn
 
 from .. import calib, ops
-from ..engine import HeadEngine
+from ..engine import HeadEngine, native_map
 from ..registry import HEADS, build_bbox_coder, build_head, build_loss, build_roi_extractor, build_transformer
 from .modules import BoxCorrelation, PE, QueryGenerator, _f, _rows, roi_size_of
 
@@ -245,7 +245,7 @@ class MV2DHead(nn.Module):
         feat = x[self.feat_lvl]
         eng = self.engine(feat.device, img_metas)
         self.box_corr_module.check_counts([len(p) for p in proposal_list])
-        out = eng.run(feat.float(), proposal_list, img_metas)
+        out = eng.run(native_map(feat), proposal_list, img_metas)                 # a 16-bit map goes in as it is (the engine widens in its kernels)
         boxes, scores, labels = eng.results(out)
         boxes = boxes.clone()
         box_type = img_metas[0].get('box_type_3d')
@@ -262,7 +262,7 @@ class MV2DHead(nn.Module):
         feat = x[self.feat_lvl]
         assert feat.shape[0] % B == 0 and all(len(m) == feat.shape[0] // B for m in img_metas_list)
         eng = self.engine(feat.device, img_metas_list[0])
-        out = eng.run_batch(feat.float(), proposal_lists, img_metas_list)
+        out = eng.run_batch(native_map(feat), proposal_lists, img_metas_list)
         res = []
         for b, (boxes, scores, labels) in enumerate(eng.results_batch(out)):
             boxes = boxes.clone()
@@ -280,6 +280,7 @@ class MV2DHead(nn.Module):
         row_ptr = ws['row_ptr'][:R + 1].clone()
         # the input map, position-major, as a differentiable view: its gradient comes back through RoIAlign and the key rows
         V, _, h, w = feat.shape
+        # (a 16-bit map is widened HERE, by a differentiable torch op like the reference's force_fp32: feat.grad comes back in feat's dtype, rounded once)
         fm = feat.float().permute(0, 2, 3, 1).reshape(V * h * w, C)
         rois = ws['rois'][:R].clone()
         s = self.roi_cells
@@ -361,7 +362,7 @@ class MV2DHead(nn.Module):
         eng.keep_sine_rows = bool(autograd)                 # the autograd route evaluates the sine branch of the PE block itself
         eng.stop_before_decoder = bool(autograd)            # ... and runs its own decoder: the engine stops after the query generator
         try:
-            out = eng.run(feat.detach().float(), [p[:, :6] for p in proposal_list], img_metas)
+            out = eng.run(native_map(feat.detach()), [p[:, :6] for p in proposal_list], img_metas)
         finally:
             eng.stop_before_decoder = False
         g = ori_gt_bboxes_3d[0]

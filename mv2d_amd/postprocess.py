@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .engine import native_map
 
 
 def process_2d_detections(results, device, min_bbox_size=0):
@@ -80,7 +81,7 @@ def simple_test_batch_from_detections(roi_head, feat_maps, det_results_list, img
     feat = feat_maps[roi_head.feat_lvl]
     proposals = [process_2d_detections(d, feat.device, min_bbox_size) for d in det_results_list]
     eng = roi_head.engine(feat.device, img_metas_list[0])
-    out = eng.run_batch(feat.float(), proposals, img_metas_list)
+    out = eng.run_batch(native_map(feat), proposals, img_metas_list)
     res = pack_results_batch(out['boxes'], out['scores'], out['labels'], out['count'], rcnn_test_cfg.get('score_thr', 0.0),
                              rcnn_test_cfg.get('max_per_scene', 300), nms_thr)
     if int(out['ws']['nnz'][1].item()) != 0:
@@ -101,7 +102,7 @@ def simple_test_from_detections(roi_head, feat_maps, det_results, img_metas, rcn
     feat = feat_maps[roi_head.feat_lvl]
     proposals = process_2d_detections(det_results, feat.device, min_bbox_size)
     eng = roi_head.engine(feat.device, img_metas)
-    out = eng.run(feat.float(), proposals, img_metas)
+    out = eng.run(native_map(feat), proposals, img_metas)
     res = pack_results(out['boxes'], out['scores'], out['labels'], out['count'], rcnn_test_cfg.get('score_thr', 0.0),
                        rcnn_test_cfg.get('max_per_scene', 300), nms_thr)
     if int(out['ws']['nnz'][1].item()) != 0:

@@ -1,0 +1,69 @@
+#!/usr/bin/env python
+"""Are the instruction streams of a source file's kernels what they were at another commit?
+
+    python tools/cmp_kernel_isa.py <git-rev> rows.hip geometry.hip pe_x3.hip pe_tab96.hip
+
+Compiles mv2d_amd/csrc/<file> of <git-rev> and of the working tree for gfx950 (device code only, the flags of mv2d_amd/build.py), disassembles both code
+objects with llvm-objdump -d and compares kernel by kernel.  A kernel that gained a template argument is matched with its `float` instance
+(`roi_align_kernel` <-> `roi_align_kernel<float>`, `pe_inputs_kernel<true>` <-> `pe_inputs_kernel<true, float>`).  No GPU needed.  Exit status 1
+when a kernel of <git-rev> is missing or differs."""
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from mv2d_amd.build import FLAGS, _hipcc  # noqa: E402
+
+LLVM = os.path.join(os.environ.get('ROCM_PATH', '/opt/rocm'), 'llvm', 'bin')
+
+
+def kernels(src, tmp, tag):
+    bundle, co = os.path.join(tmp, tag + '.bundle'), os.path.join(tmp, tag + '.co')
+    subprocess.run([_hipcc()] + FLAGS + ['--cuda-device-only', '-c', src, '-o', bundle], check=True)
+    subprocess.run([os.path.join(LLVM, 'clang-offload-bundler'), '--unbundle', '--type=o', '--targets=hipv4-amdgcn-amd-amdhsa--gfx950',
+                    '--input=' + bundle, '--output=' + co], check=True)
+    txt = subprocess.run([os.path.join(LLVM, 'llvm-objdump'), '-d', '--no-show-raw-insn', co], check=True, capture_output=True, text=True).stdout
+    out, cur = {}, None
+    for line in txt.splitlines():
+        m = re.match(r'^[0-9a-f]+ <(.+)>:$', line)
+        if m:
+            cur = out.setdefault(m.group(1), [])
+            continue
+        ins = line.split('//')[0].strip()
+        if cur is None or not ins or ins == '...':           # (padding behind s_endpgm)
+            continue
+        cur.append(re.sub(r'<[^>]+>', '<sym>', ins))
+    names = subprocess.run(['c++filt'], input='\n'.join(out), capture_output=True, text=True, check=True).stdout.split('\n')
+    res = {}
+    for mangled, name in zip(out, names):
+        name = name.replace('(anonymous namespace)::', '').replace('void ', '').split('(')[0].replace('> >', '>>')
+        name = name[:-len(' [clone .kd]')] if name.endswith(' [clone .kd]') else name
+        res[name] = out[mangled]
+    return res
+
+
+def main():
+    rev, files = sys.argv[1], sys.argv[2:]
+    bad = 0
+    with tempfile.TemporaryDirectory() as tmp:
+        old = os.path.join(tmp, 'old')
+        os.makedirs(old)
+        tar = subprocess.run(['git', '-C', ROOT, 'archive', rev, 'mv2d_amd/csrc'], check=True, capture_output=True).stdout
+        subprocess.run(['tar', '-x', '-C', old], input=tar, check=True)
+        for f in files:
+            a = kernels(os.path.join(old, 'mv2d_amd', 'csrc', f), tmp, 'old_' + f)
+            b = kernels(os.path.join(ROOT, 'mv2d_amd', 'csrc', f), tmp, 'new_' + f)
+            for name, ins in sorted(a.items()):
+                cands = [name, name + '<float>', re.sub(r'>$', ', float>', name)]
+                now = next((c for c in cands if c in b), None)
+                verdict = 'MISSING' if now is None else ('identical' if b[now] == ins else 'DIFFERENT (%d -> %d instructions)' % (len(ins), len(b[now])))
+                bad += verdict != 'identical'
+                print('%-14s %-78s %6d  %s' % (f, (now or name)[:78], len(ins), verdict))
+    return 1 if bad else 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())
