@@ -236,6 +236,20 @@ int mv2d_heads_fused_x3(const float* outs, const void* const* cls_w, const void*
  * linear at one tile.  mv2d_heads_fused_x3 is this entry with num_classes = 10; the fp32 mv2d_heads_fused above stays 10-class only. */
 int mv2d_heads_fused_x3_nc(const float* outs, const void* const* cls_w, const void* const* reg_w, const float* ref, float* cls, float* reg,
                            int M, int L, int num_classes, float eps, const float* pc_range, float dt, const float* dt_rows, void* stream);
+/* The class branch alone (the regression branch then runs as mv2d_reg_layer_x3): the same kernels with one branch in the grid; cls is bit for
+ * bit the cls of mv2d_heads_fused_x3_nc. */
+int mv2d_heads_cls_x3_nc(const float* outs, const void* const* cls_w, float* cls, int M, int L, int num_classes, float eps, void* stream);
+/* The regression branches as the reference's RegLayer (CrossAttentionBoxHead(use_reg_layer=True)) + the box-code tail of the launches above
+ * (reference point, sigmoid, pc_range, velocity / dt): per layer two shared Linear(256,256)+ReLU, then per group g of group_dims a task head
+ * Linear(256,256)+ReLU+Linear(256,d_g) whose outputs are concatenated to the 10-value box code.  The 256x256 linears run in split precision,
+ * the output layers in exact fp32.  outs [L,M,256], ref [M,3], out reg [L,M,10].
+ * w = {s1_hi,s1_lo,s1_b, s2_hi,s2_lo,s2_b, t1_hi,t1_lo,t1_b, t2_w,t2_b} device pointers: the shared layers' matrices as per-layer
+ * mv2d_split_q16x2 + mv2d_pack_wfrag_bf16 copies stacked over L (biases [L,256]); the task heads' first layers the same, stacked [L][G]
+ * (biases [L,G,256]); the second layers as ONE fp32 matrix t2_w [L,10,256] whose row o is the row of the group that owns output column o, with
+ * t2_b [L,10].  group_dims: HOST array of n_groups entries (1 <= n_groups <= 10, every entry >= 1, sum 10), read during the call and passed to
+ * the kernel by value (safe under stream capture); anything else returns -1. */
+int mv2d_reg_layer_x3(const float* outs, const void* const* w, const float* ref, float* reg, int M, int L, int n_groups, const int* group_dims,
+                      const float* pc_range, float dt, const float* dt_rows, void* stream);
 
 /* Fused FFN partial sums (mmcv FFN 256 -> hidden -> 256 of the decoder layer, configs/mv2d/exp/*:78-79):
  * slabs[s] = relu(X . W1[64s:64s+64]^T + b1[64s:64s+64]) . W2[:, 64s:64s+64]^T  for the hidden/64 slices s, exact fp32.

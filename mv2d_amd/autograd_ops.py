@@ -298,6 +298,17 @@ BRANCH_PARAMS = ('cls_branches.{l}.0.weight', 'cls_branches.{l}.0.bias', 'cls_br
                  'reg_branches.{l}.2.weight', 'reg_branches.{l}.2.bias', 'reg_branches.{l}.4.weight', 'reg_branches.{l}.4.bias')
 
 
+def reg_layer_params(group_reg_dims):
+    """Parameter names of one layer's RegLayer regression branch (CrossAttentionBoxHead(use_reg_layer=True)), in module order."""
+    names = [f'reg_branches.{{l}}.reg_branch.{n}.{k}' for n in (0, 3) for k in ('weight', 'bias')]
+    return tuple(names + [f'reg_branches.{{l}}.task_heads.{g}.{n}.{k}' for g in range(len(group_reg_dims)) for n in (0, 2) for k in ('weight', 'bias')])
+
+
+def branch_params(use_reg_layer=False, group_reg_dims=()):
+    """BRANCH_PARAMS for a head: with use_reg_layer the three reg_branches linears give way to the RegLayer's parameters."""
+    return BRANCH_PARAMS if not use_reg_layer else BRANCH_PARAMS[:10] + reg_layer_params(group_reg_dims)
+
+
 def _flat_grads(params, dev):
     """one flat fp32 buffer + the views the C entries write the parameter gradients into (64-float aligned pieces)"""
     offs, n = [], 0

@@ -92,22 +92,30 @@ def _set_roi_size(d, roi_size):
     return d
 
 
-def roi_head_cfg_s(num_classes=10, roi_size=ROI_SIZE):
+def _set_reg_layer(d, group_reg_dims):
+    # ``bbox_head.use_reg_layer`` / ``group_reg_dims`` of the reference head; None leaves the shipped Sequential regression branches (no key added)
+    if group_reg_dims is not None:
+        d['bbox_head'].update(use_reg_layer=True, group_reg_dims=tuple(group_reg_dims))
+    return d
+
+
+def roi_head_cfg_s(num_classes=10, roi_size=ROI_SIZE, reg_layer_dims=None):
     """CFG-S:40-121 (MV2D-S single frame); ``num_classes`` sets ``bbox_head.num_classes`` and ``bbox_head.bbox_coder.num_classes``,
-    ``roi_size`` sets ``bbox_roi_extractor.roi_layer.output_size`` and ``query_generator.roi_feat_size``."""
+    ``roi_size`` sets ``bbox_roi_extractor.roi_layer.output_size`` and ``query_generator.roi_feat_size``; ``reg_layer_dims`` (a tuple of
+    group widths) sets ``bbox_head.use_reg_layer=True`` with that ``group_reg_dims``."""
     d = dict(type='MV2DSHead', use_denoise=False)
     d.update(_common(with_cp=False))
     d['box_correlation'] = dict(correlation_mode='topk_matched:1:0.0:0.0')
-    return copy.deepcopy(_set_roi_size(_set_num_classes(d, num_classes), roi_size))
+    return copy.deepcopy(_set_reg_layer(_set_roi_size(_set_num_classes(d, num_classes), roi_size), reg_layer_dims))
 
 
-def roi_head_cfg_t(num_classes=10, roi_size=ROI_SIZE):
-    """CFG-T:40-125 (MV2D-T two frames); ``num_classes`` and ``roi_size`` as in ``roi_head_cfg_s``."""
+def roi_head_cfg_t(num_classes=10, roi_size=ROI_SIZE, reg_layer_dims=None):
+    """CFG-T:40-125 (MV2D-T two frames); ``num_classes``, ``roi_size`` and ``reg_layer_dims`` as in ``roi_head_cfg_s``."""
     d = dict(type='MV2DTHead', use_denoise=True, neg_bbox_loss=True,
              denoise_noise_scale=1.25, denoise_split=0.6)
     d.update(_common(with_cp=True))
     d['box_correlation'] = dict(expand_stride=2, correlation_mode='topk_matched:20:0.0:0.0')
-    return copy.deepcopy(_set_roi_size(_set_num_classes(d, num_classes), roi_size))
+    return copy.deepcopy(_set_reg_layer(_set_roi_size(_set_num_classes(d, num_classes), roi_size), reg_layer_dims))
 
 
 TEST_CFG_RCNN = dict(score_thr=0.0, nms=dict(nms_thr=1.0, use_rotate_nms=True), max_per_scene=300)  # CFG-T:154-158

@@ -11,21 +11,9 @@
 // Why: the round-1 profile showed ~5 us of fixed cost per dependent kernel; these chains were 3-9 launches of 7 us each.
 // A 256x256 fp32 linear on one CU costs ~3.4 us of MFMA time (256 FLOP/clk/CU), so chains of up to ~3 linears fit.
 // Weights stream from L2 as MFMA fragments (16 float4 per lane per 16-column tile, next tile in flight behind the current one).
-#include "common.h"
+#include "x3_tile.h"
 
 namespace {
-
-constexpr int C = 256;
-
-__device__ __forceinline__ int toff(int row, int col) { return row * C + ((((col >> 2) ^ (row & 15))) << 2) + (col & 3); }
-
-struct Frag { float4 v[16]; };
-
-__device__ __forceinline__ void load_w(Frag& f, const float* __restrict__ W, int ldw, int nrow, int nmax, int fg) {
-    const float* wp = W + (long long)min(nrow, nmax - 1) * ldw + 4 * fg;
-#pragma unroll
-    for (int c = 0; c < 16; ++c) f.v[c] = *reinterpret_cast<const float4*>(wp + 16 * c);
-}
 
 // the same fragment from a FRAGMENT-MAJOR weight copy (mv2d_pack_wfrag_f32: [16-row tile][k chunk c][lane][4]): one contiguous
 // 1 KB per load instead of 16 rows x 64 B
@@ -33,19 +21,6 @@ __device__ __forceinline__ void load_w_frag(Frag& f, const float* __restrict__ W
     const float* wp = Wp + ((long long)tile * 16 * 64 + lane) * 4;
 #pragma unroll
     for (int c = 0; c < 16; ++c) f.v[c] = *reinterpret_cast<const float4*>(wp + c * 256);
-}
-
-__device__ __forceinline__ f32x4_t tile_mma(const float* __restrict__ As, const Frag& f, int fr, int fg) {
-    f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int c = 0; c < 16; ++c) {
-        const float4 a = *reinterpret_cast<const float4*>(As + fr * C + (((4 * c + fg) ^ fr) << 2));
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, f.v[c].x, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, f.v[c].y, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, f.v[c].z, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, f.v[c].w, acc, 0, 0, 0);
-    }
-    return acc;
 }
 
 // Out[16,256] = As[16,256] . W[256,256]^T: wave w computes columns 64w .. 64w+63 (4 tiles), results returned in registers.
@@ -207,41 +182,6 @@ struct AttnOutX3Params {
     // QMAP: the query tile goes on into the per-head query maps Qt (packed WA, see xattn_qmap_kernel) instead of q_out
     const uint4* WAh; const uint4* WAl; uint4* Qt;
 };
-
-typedef q16x8_t mfma_bf16x8;      // the query side's 16-bit split format (common.h "q16": fp16 pairs since round 5)
-union BFrag { uint4 u; mfma_bf16x8 v; };
-
-__device__ __forceinline__ void split4(const float4& v, uint2& hi, uint2& lo) {
-    split_q16x4(v, hi, lo);
-}
-
-// one 16x16 tile: sum over 8 k-steps of a_hi.w_hi + a_lo.w_hi + a_hi.w_lo; activation rows from the bf16 LDS images (512 B rows,
-// 16-byte chunk c of row r at c ^ r), weight fragments (hi, lo) already in registers
-__device__ __forceinline__ f32x4_t tile_mma_x3(const unsigned char* __restrict__ ah, const unsigned char* __restrict__ al, const BFrag wh[8],
-                                               const BFrag wl[8], int fr, int fg) {
-    f32x4_t a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int s = 0; s < 8; ++s) {
-        BFrag xh, xl;
-        const int off = fr * 512 + (((4 * s + fg) ^ fr) << 4);
-        xh.u = *reinterpret_cast<const uint4*>(ah + off);
-        xl.u = *reinterpret_cast<const uint4*>(al + off);
-        a0 = mfma_q16_16x16x32(xh.v, wh[s].v, a0, 0, 0, 0);
-        a1 = mfma_q16_16x16x32(xl.v, wh[s].v, a1, 0, 0, 0);
-        a1 = mfma_q16_16x16x32(xh.v, wl[s].v, a1, 0, 0, 0);
-    }
-    return f32x4_t{a0[0] + a1[0], a0[1] + a1[1], a0[2] + a1[2], a0[3] + a1[3]};
-}
-
-__device__ __forceinline__ void load_w_x3(BFrag wh[8], BFrag wl[8], const unsigned short* __restrict__ Wh, const unsigned short* __restrict__ Wl,
-                                          int tile, int lane) {
-#pragma unroll
-    for (int s = 0; s < 8; ++s) {                 // fragment-major [k-step][16 column tiles][lane][8]
-        const long long o = (((long long)s * 16 + tile) * 64 + lane) * 8;
-        wh[s].u = *reinterpret_cast<const uint4*>(Wh + o);
-        wl[s].u = *reinterpret_cast<const uint4*>(Wl + o);
-    }
-}
 
 // RT row tiles (16 rows each) per block share one fetch of the weight fragments.  A block is bound by fetching its 0.5 MB of weights
 // through one CU's L1 (~57 GB/s), whatever the number of rows: with a batch of samples (M > 512) two row tiles per block take the
@@ -1329,15 +1269,23 @@ extern "C" int mv2d_heads_fused(const float* outs, const float* const* cls_w, co
     return MV2D_OK;
 }
 
-extern "C" int mv2d_heads_fused_x3_nc(const float* outs, const void* const* cls_w, const void* const* reg_w, const float* ref, float* cls,
-                                      float* reg, int M, int L, int num_classes, float eps, const float* pc_range, float dt, const float* dt_rows,
-                                      void* stream) {
+// branches = 2: the class and the regression branch (gridDim.z = 2); branches = 1: the class branch alone -- with gridDim.z = 1 the kernel's
+// `branch` is 0 in every block, which reads cls_w and writes cls only (reg_w, ref, reg, pc_range, dt are never touched and may be NULL)
+static int heads_x3_launch(const float* outs, const void* const* cls_w, const void* const* reg_w, const float* ref, float* cls, float* reg, int M,
+                           int L, int num_classes, float eps, const float* pc_range, float dt, const float* dt_rows, void* stream, int branches) {
     // cls_w: {w0_hi,w0_lo,b0,lnw1,lnb1,w3_hi,w3_lo,b3,lnw4,lnb4,w6,b6}; reg_w: {w0_hi,w0_lo,b0,w2_hi,w2_lo,b2,w4,b4} device pointers,
     // every tensor stacked over the L layers; the *_hi/_lo matrices are per-layer mv2d_split_bf16x2 + mv2d_pack_wfrag_bf16 copies
-    MV2D_CHECK_ARG(outs && cls_w && reg_w && ref && cls && reg && pc_range && L > 0, "mv2d_heads_fused_x3: null pointer");
+    static const void* const no_reg_w[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    static const float no_range[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (branches == 2) {
+        MV2D_CHECK_ARG(outs && cls_w && reg_w && ref && cls && reg && pc_range && L > 0, "mv2d_heads_fused_x3: null pointer");
+    } else {
+        MV2D_CHECK_ARG(outs && cls_w && cls && L > 0, "mv2d_heads_cls_x3: null pointer");
+        reg_w = no_reg_w, pc_range = no_range, ref = nullptr, reg = nullptr, dt = 0.f, dt_rows = nullptr;
+    }
     MV2D_CHECK_ARG(num_classes >= 1 && num_classes <= 64, "mv2d_heads_fused_x3: num_classes must be in [1, 64]");
     for (int i = 0; i < 12; ++i) MV2D_CHECK_ARG(cls_w[i] != nullptr, "mv2d_heads_fused_x3: null cls weight");
-    for (int i = 0; i < 8; ++i) MV2D_CHECK_ARG(reg_w[i] != nullptr, "mv2d_heads_fused_x3: null reg weight");
+    for (int i = 0; i < 8 && branches == 2; ++i) MV2D_CHECK_ARG(reg_w[i] != nullptr, "mv2d_heads_fused_x3: null reg weight");
     if (M == 0) return MV2D_OK;
     typedef const unsigned short* U; typedef const float* Fp;
     HeadsX3Params p{outs, (U)cls_w[0], (U)cls_w[1], (Fp)cls_w[2], (Fp)cls_w[3], (Fp)cls_w[4], (U)cls_w[5], (U)cls_w[6], (Fp)cls_w[7], (Fp)cls_w[8],
@@ -1350,11 +1298,11 @@ extern "C" int mv2d_heads_fused_x3_nc(const float* outs, const void* const* cls_
     const hipStream_t st = (hipStream_t)stream;
 #define MV2D_HEADS_X3(RT)                                                                                                             \
     switch (ct) {                                                                                                                     \
-        case 0: hipLaunchKernelGGL((heads_fused_x3_kernel<RT, 1, 10>), dim3(cdiv(M, 16 * RT), L, 2), dim3(1024), 0, st, p); break;    \
-        case 1: hipLaunchKernelGGL((heads_fused_x3_kernel<RT, 1, 0>), dim3(cdiv(M, 16 * RT), L, 2), dim3(1024), 0, st, p); break;     \
-        case 2: hipLaunchKernelGGL((heads_fused_x3_kernel<RT, 2, 0>), dim3(cdiv(M, 16 * RT), L, 2), dim3(1024), 0, st, p); break;     \
-        case 3: hipLaunchKernelGGL((heads_fused_x3_kernel<RT, 3, 0>), dim3(cdiv(M, 16 * RT), L, 2), dim3(1024), 0, st, p); break;     \
-        default: hipLaunchKernelGGL((heads_fused_x3_kernel<RT, 4, 0>), dim3(cdiv(M, 16 * RT), L, 2), dim3(1024), 0, st, p); break;    \
+        case 0: hipLaunchKernelGGL((heads_fused_x3_kernel<RT, 1, 10>), dim3(cdiv(M, 16 * RT), L, branches), dim3(1024), 0, st, p); break;    \
+        case 1: hipLaunchKernelGGL((heads_fused_x3_kernel<RT, 1, 0>), dim3(cdiv(M, 16 * RT), L, branches), dim3(1024), 0, st, p); break;     \
+        case 2: hipLaunchKernelGGL((heads_fused_x3_kernel<RT, 2, 0>), dim3(cdiv(M, 16 * RT), L, branches), dim3(1024), 0, st, p); break;     \
+        case 3: hipLaunchKernelGGL((heads_fused_x3_kernel<RT, 3, 0>), dim3(cdiv(M, 16 * RT), L, branches), dim3(1024), 0, st, p); break;     \
+        default: hipLaunchKernelGGL((heads_fused_x3_kernel<RT, 4, 0>), dim3(cdiv(M, 16 * RT), L, branches), dim3(1024), 0, st, p); break;    \
     }
     if (M <= 512) { MV2D_HEADS_X3(1) }
     else if (M <= 1024) { MV2D_HEADS_X3(2) }
@@ -1362,6 +1310,16 @@ extern "C" int mv2d_heads_fused_x3_nc(const float* outs, const void* const* cls_
 #undef MV2D_HEADS_X3
     MV2D_LAUNCH_CHECK();
     return MV2D_OK;
+}
+
+extern "C" int mv2d_heads_fused_x3_nc(const float* outs, const void* const* cls_w, const void* const* reg_w, const float* ref, float* cls,
+                                      float* reg, int M, int L, int num_classes, float eps, const float* pc_range, float dt, const float* dt_rows,
+                                      void* stream) {
+    return heads_x3_launch(outs, cls_w, reg_w, ref, cls, reg, M, L, num_classes, eps, pc_range, dt, dt_rows, stream, 2);
+}
+
+extern "C" int mv2d_heads_cls_x3_nc(const float* outs, const void* const* cls_w, float* cls, int M, int L, int num_classes, float eps, void* stream) {
+    return heads_x3_launch(outs, cls_w, nullptr, nullptr, cls, nullptr, M, L, num_classes, eps, nullptr, 0.f, nullptr, stream, 1);
 }
 
 extern "C" int mv2d_heads_fused_x3(const float* outs, const void* const* cls_w, const void* const* reg_w, const float* ref, float* cls, float* reg,

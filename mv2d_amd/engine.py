@@ -48,7 +48,8 @@ class HeadEngine:
     def __init__(self, state_dict, kind, device, num_views=6, topk=None, expand_stride=None, num_layers=L_DEFAULT,
                  max_num=300, pc_range=(-51.2, -51.2, -5.0, 51.2, 51.2, 3.0),
                  post_range=(-61.2, -61.2, -10.0, 61.2, 61.2, 10.0), depth_num=64, stride=16, col_cap_per_query=2048,
-                 iou_thr=0.0, ratio=0.0, masked_row='nan', exact=None, num_classes=10, roi_size=7):
+                 iou_thr=0.0, ratio=0.0, masked_row='nan', exact=None, num_classes=10, roi_size=7, use_reg_layer=False,
+                 group_reg_dims=(2, 2, 1, 1, 2, 2)):
         assert kind in ('S', 'T')
         self.kind = kind
         self.dev = torch.device(device)
@@ -65,6 +66,11 @@ class HeadEngine:
         if self.roi_size != roi_size or not 1 <= self.roi_size <= 14:
             raise ValueError(f'HeadEngine: roi_size must be an int in [1, 14], got {roi_size}')
         self.cells = self.roi_size * self.roi_size
+        # the regression branches as the reference's RegLayer (CrossAttentionBoxHead(use_reg_layer=True): two shared linears, one task head per
+        # entry of group_reg_dims) -- mv2d_reg_layer_x3 next to the class-only launch of the fused branches.  Fixed per engine: the state dict's
+        # key layout has to agree (load_state), and it is part of the graph key.
+        self.use_reg_layer = bool(use_reg_layer)
+        self.group_reg_dims = ops.check_group_reg_dims(group_reg_dims) if self.use_reg_layer else tuple(group_reg_dims)
         self.depth_num = depth_num
         self.stride = stride
         self.iou_thr, self.ratio = iou_thr, ratio
@@ -211,8 +217,18 @@ class HeadEngine:
         for n in ('1', '4'):
             w[f'cls_lnw{n}'], w[f'cls_lnb{n}'] = st('bbox_head.cls_branches.{}.' + n + '.weight'), st('bbox_head.cls_branches.{}.' + n + '.bias')
         w['cls_w6'], w['cls_b6'] = st('bbox_head.cls_branches.{}.6.weight'), st('bbox_head.cls_branches.{}.6.bias')
-        for n in ('0', '2', '4'):
-            w[f'reg_w{n}'], w[f'reg_b{n}'] = st('bbox_head.reg_branches.{}.' + n + '.weight'), st('bbox_head.reg_branches.{}.' + n + '.bias')
+        rb = 'bbox_head.reg_branches.'
+        self.check_reg_layout(sd, self.use_reg_layer, self.group_reg_dims)
+        if self.use_reg_layer:
+            G = len(self.group_reg_dims)
+            for n, k in (('s1', 'reg_branch.0'), ('s2', 'reg_branch.3')):
+                w[f'rl_{n}_w'], w[f'rl_{n}_b'] = st(rb + '{}.' + k + '.weight'), st(rb + '{}.' + k + '.bias')
+            stg = lambda fmt, cat: torch.stack([cat([g(rb + fmt.format(l, g_)) for g_ in range(G)]) for l in range(L)]).contiguous()
+            w['rl_t1_w'], w['rl_t1_b'] = stg('{}.task_heads.{}.0.weight', torch.stack), stg('{}.task_heads.{}.0.bias', torch.stack)
+            w['rl_t2_w'], w['rl_t2_b'] = stg('{}.task_heads.{}.2.weight', torch.cat), stg('{}.task_heads.{}.2.bias', torch.cat)
+        else:
+            for n in ('0', '2', '4'):
+                w[f'reg_w{n}'], w[f'reg_b{n}'] = st(rb + '{}.' + n + '.weight'), st(rb + '{}.' + n + '.bias')
         q = 'query_generator.'
         conv = g(q + 'shared_convs.0.conv.weight').permute(0, 2, 3, 1).reshape(C, 9 * C).contiguous()       # [256,256,3,3] -> [out][tap][cin]
         w['qg_conv_wp'] = k16(conv)                                                   # key16, fragment-major: the fused conv kernel
@@ -252,15 +268,39 @@ class HeadEngine:
             w['pe_x3']['wr_p'] = ops.pack_x3_rowperm(c1('fpe.conv_reduce.weight'))
             w['qg_conv_wx3'] = ops.pack_key16_x3(conv)
         self.w = w
-        for k in ('cls_w0', 'cls_w3', 'reg_w0', 'reg_w2'):                              # [L,256,256] -> bf16x3, fragment-major, stacked over L
+        for k in ('cls_w0', 'cls_w3') + (() if self.use_reg_layer else ('reg_w0', 'reg_w2')):   # [L,256,256] -> bf16x3, fragment-major, stacked over L
             w[k + 'x'] = ops.pack_x3_stack(w[k])
         cls_t = (*w['cls_w0x'], w['cls_b0'], w['cls_lnw1'], w['cls_lnb1'], *w['cls_w3x'], w['cls_b3'], w['cls_lnw4'], w['cls_lnb4'], w['cls_w6'], w['cls_b6'])
-        reg_t = (*w['reg_w0x'], w['reg_b0'], *w['reg_w2x'], w['reg_b2'], w['reg_w4'], w['reg_b4'])
+        if self.use_reg_layer:              # the weight table of mv2d_reg_layer_x3 (every tensor stacked over L, like the tables above)
+            reg_t = w['rl_table'] = tuple(ops.pack_reg_layer(*(w[f'rl_{n}_{k}'] for n in ('s1', 's2', 't1', 't2') for k in ('w', 'b'))))
+        else:
+            reg_t = (*w['reg_w0x'], w['reg_b0'], *w['reg_w2x'], w['reg_b2'], w['reg_w4'], w['reg_b4'])
         self.cls_ptrs_x3, self.reg_ptrs_x3 = ops.make_ptr_array(list(cls_t)), ops.make_ptr_array(list(reg_t))
         # the same tensors from the last decoder layer on: the launch of the last_stage_heads option (every tensor is stacked over L)
         ll = self.L - 1
         self._last_cls, self._last_reg = [t[ll:] for t in cls_t], [t[ll:] for t in reg_t]
         self.cls_ptrs_x3_last, self.reg_ptrs_x3_last = ops.make_ptr_array(self._last_cls), ops.make_ptr_array(self._last_reg)
+
+    @staticmethod
+    def check_reg_layout(sd, use_reg_layer, group_reg_dims):
+        """ValueError unless the regression branches of the state dict have the layout of the switch: a Sequential
+        (``reg_branches.{l}.{0,2,4}.*``) without it, a RegLayer (``reg_branches.{l}.reg_branch.{0,3}.*`` and
+        ``reg_branches.{l}.task_heads.{g}.{0,2}.*``) of exactly ``group_reg_dims`` with it."""
+        rb = 'bbox_head.reg_branches.0.'
+        layouts = {False: 'the Sequential layout (reg_branches.{l}.{0,2,4}.*)',
+                   True: 'the RegLayer layout (reg_branches.{l}.reg_branch.{0,3}.*, reg_branches.{l}.task_heads.{g}.{0,2}.*)'}
+        found = {False: rb + '0.weight' in sd, True: rb + 'reg_branch.0.weight' in sd}
+        if not found[bool(use_reg_layer)] or found[not use_reg_layer]:
+            held = ' and '.join(layouts[k] for k in (False, True) if found[k]) or 'neither layout'
+            raise ValueError(f'HeadEngine: use_reg_layer={bool(use_reg_layer)} expects {layouts[bool(use_reg_layer)]}, the state dict holds {held}; '
+                             f'the other switch value expects {layouts[not use_reg_layer]}')
+        if use_reg_layer:
+            dims, g = [], 0
+            while f'{rb}task_heads.{g}.2.weight' in sd:
+                dims.append(int(tuple(sd[f'{rb}task_heads.{g}.2.weight'].shape)[0]))
+                g += 1
+            if tuple(dims) != tuple(group_reg_dims):
+                raise ValueError(f'HeadEngine: group_reg_dims={tuple(group_reg_dims)}, the task heads of the state dict are {tuple(dims)} wide')
 
     def _c3(self, name):
         """K-concatenated split-precision copy [w_hi | w_hi | w_lo] of a PE weight ('w1a', 'w1b', 'w2a', 'w2b', 'wr', 'we'), built on first use
@@ -864,6 +904,14 @@ class HeadEngine:
     def _enqueue_heads(self, ws, R, dt):
         # a14: every per-layer cls / reg branch + the reference-point tail in ONE launch (row-block fused, bf16x3)
         dt_rows = ws['dt_rows'] if self.kind == 'T' else None
+        if self.use_reg_layer:
+            # RegLayer regression branches: the class branch alone through the fused kernel, the regression branch + tail through its own
+            last = self.last_stage_heads and not getattr(self, '_stage_outputs', False)
+            ll, n = (self.L - 1, 1) if last else (0, self.L)
+            ops.heads_cls_x3(ws['outs'][ll:], self.cls_ptrs_x3_last if last else self.cls_ptrs_x3, ws['cls'][ll:], R, n, num_classes=self.num_classes)
+            ops.reg_layer_x3(ws['outs'][ll:], self.reg_ptrs_x3_last if last else self.reg_ptrs_x3, ws['ref'], ws['reg'][ll:], R, n,
+                             self.group_reg_dims, self.pc_range_h, dt, dt_rows=dt_rows)
+            return
         if self.last_stage_heads and not getattr(self, '_stage_outputs', False):
             # inference needs the branches of the LAST decoder layer only (the reference evaluates all six and reads [-1],
             # cross_attention_head.py:202-242 / RH/mv2d_head.py:170-194); cls / reg of the other layers are then not written
@@ -957,7 +1005,7 @@ class HeadEngine:
             return dict(self._result(ws, R, keep_stages, batch), dt=sc['dt'])
         # the graph bakes in the input pointers (the producer's output buffers are static under graph replay) and the
         # frame scalars; anything else changing (RoI boxes, calibration tables, feature values) is data.
-        gkey = (ptrs, map_dtype, 0 if payload is None else payload.data_ptr(), sc['pad_h'], sc['pad_w'], sc['max_rows'], self.num_classes, self.roi_size, self._weights_version, self._stage_outputs, self.last_stage_heads,
+        gkey = (ptrs, map_dtype, 0 if payload is None else payload.data_ptr(), sc['pad_h'], sc['pad_w'], sc['max_rows'], self.num_classes, self.roi_size, self.use_reg_layer, self.group_reg_dims, self._weights_version, self._stage_outputs, self.last_stage_heads,
                 self.xattn_waves, self.fuse_maps, self.fuse_xattn, self.group_xattn, self.lo8_rows, self.pe_at_positions, self.pe_rows_in_waves, self.fold_sa0, self.masked_transpose, self.keep_sine_rows, self.force_nc, self.q_order,
                 self.fork_qg, self.exact_skip, self.ablate_zero_lo, self.stop_before_decoder)   # load_state() re-allocates the weights; every route option of __init__ is in the key
         graphs = ws.setdefault('graphs', {})             # one graph per (input buffers, frame scalars): a producer that alternates between

@@ -354,6 +354,47 @@ def pack_x3_stack(W):
     return torch.stack([p[0].view(-1) for p in packs]).contiguous(), torch.stack([p[1].view(-1) for p in packs]).contiguous()
 
 
+def heads_cls_x3(outs, cls_ptrs, cls, M, L, eps=1e-5, num_classes=10):
+    """The class branch of heads_fused_x3 alone (cls bit for bit the same); the regression branch then runs through reg_layer_x3."""
+    num_classes = int(num_classes)
+    if not 1 <= num_classes <= 64:
+        raise ValueError(f'heads_cls_x3: num_classes must be in [1, 64], got {num_classes}')
+    check(_lib.load().mv2d_heads_cls_x3_nc(_p(outs), cls_ptrs, _p(cls), M, L, num_classes, float(eps), _stream()), 'mv2d_heads_cls_x3_nc')
+
+
+def check_group_reg_dims(group_reg_dims, code_size=10):
+    """group_reg_dims of a RegLayer as a tuple of ints: 1 to code_size groups, every one at least 1 wide, code_size columns in all."""
+    try:
+        dims = tuple(int(d) for d in group_reg_dims)
+        ok = all(d == g for d, g in zip(dims, group_reg_dims))
+    except (TypeError, ValueError):
+        dims, ok = (), False
+    if not ok or not 1 <= len(dims) <= code_size or min(dims) < 1 or sum(dims) != code_size:
+        raise ValueError(f'group_reg_dims must be 1 to {code_size} positive ints that sum to {code_size}, got {group_reg_dims!r}')
+    return dims
+
+
+def pack_reg_layer(s1_w, s1_b, s2_w, s2_b, t1_w, t1_b, t2_w, t2_b):
+    """The weight table of reg_layer_x3 (include/mv2d_hip.h, mv2d_reg_layer_x3) from fp32 tensors stacked over the L decoder layers:
+    shared layers s1_w / s2_w [L,256,256], s1_b / s2_b [L,256]; task heads' first layers t1_w [L,G,256,256], t1_b [L,G,256]; their second
+    layers concatenated over the groups t2_w [L,10,256], t2_b [L,10].  Returns the 11 tensors in table order (keep them alive next to the
+    make_ptr_array of them)."""
+    L, G = t1_w.shape[0], t1_w.shape[1]
+    t1 = [t.view(L, -1) for t in pack_x3_stack(t1_w.reshape(L * G, 256, 256))]        # every tensor of the table: layer-major
+    f = lambda t: t.to(torch.float32).contiguous()
+    return [*pack_x3_stack(s1_w), f(s1_b), *pack_x3_stack(s2_w), f(s2_b), t1[0], t1[1], f(t1_b), f(t2_w), f(t2_b)]
+
+
+def reg_layer_x3(outs, ptrs, ref, reg, M, L, group_reg_dims, pc_range_host, dt=0.0, dt_rows=None):
+    """reg [L,M,10] = box codes of the RegLayer regression branches on outs [L,M,256] (ptrs: make_ptr_array(pack_reg_layer(...))), with the
+    reference-point / sigmoid / pc_range / dt tail of heads_fused_x3."""
+    import ctypes
+    dims = check_group_reg_dims(group_reg_dims)
+    _req(outs, torch.float32, 'outs'); _req(ref, torch.float32, 'ref'); _req(reg, torch.float32, 'reg'); _req(dt_rows, torch.float32, 'dt_rows')
+    check(_lib.load().mv2d_reg_layer_x3(_p(outs), ptrs, _p(ref), _p(reg), M, L, len(dims), (ctypes.c_int * len(dims))(*dims),
+                                        pc_range_host.data_ptr(), float(dt), _p(dt_rows), _stream()), 'mv2d_reg_layer_x3')
+
+
 def ffn_pack_weights(W1, W2):
     """nn.Linear weights W1 [hidden,256], W2 [256,hidden] -> fragment-major copies (W1p, W2p) for ffn_fused."""
     _req(W1, torch.float32, 'W1'); _req(W2, torch.float32, 'W2')

@@ -22,6 +22,26 @@ from .modules import BoxCorrelation, PE, QueryGenerator, _f, _rows, roi_size_of
 C = 256
 
 
+class RegLayer(nn.Module):
+    """RH/bbox_heads/cross_attention_head.py:52-83: the regression branch of a decoder layer as shared layers + one task head per group of
+    box-code columns.  Parameter names as in the reference: ``reg_branch.{0,3}`` (Linear, ReLU, Dropout per shared layer) and
+    ``task_heads.{g}.{0,2}``.  The module holds the parameters; the head evaluates it through mv2d_reg_layer_x3 (inference) or the autograd
+    operators (training), ``forward`` is the plain torch statement of it."""
+
+    def __init__(self, embed_dims=256, shared_reg_fcs=2, group_reg_dims=(2, 1, 3, 2, 2), drop=0.0):
+        super().__init__()
+        shared = []
+        for _ in range(shared_reg_fcs):
+            shared += [nn.Linear(embed_dims, embed_dims), nn.ReLU(), nn.Dropout(drop)]
+        self.reg_branch = nn.Sequential(*shared)
+        self.task_heads = nn.ModuleList([nn.Sequential(nn.Linear(embed_dims, embed_dims), nn.ReLU(), nn.Linear(embed_dims, d))
+                                         for d in group_reg_dims])
+
+    def forward(self, x):
+        feat = self.reg_branch(x)
+        return torch.cat([head(feat) for head in self.task_heads], -1)
+
+
 @HEADS.register_module()
 class CrossAttentionBoxHead(nn.Module):
     """RH/bbox_heads/cross_attention_head.py:86-242,357-377 (forward + get_bboxes)."""
@@ -34,8 +54,10 @@ class CrossAttentionBoxHead(nn.Module):
                                  pc_range=[-51.2, -51.2, -5.0, 51.2, 51.2, 3.0], max_num=100, num_classes=10),
                  sync_cls_avg_factor=False, train_cfg=None, test_cfg=None, **kwargs):
         super().__init__()
-        assert not use_reg_layer and not pre_embed and embed_dims == C and num_reg_fcs == 2, \
-            'kernel path implements the shipped head configuration'
+        assert not pre_embed and embed_dims == C and num_reg_fcs == 2, 'kernel path implements the shipped head configuration'
+        # the box code has 10 columns; with use_reg_layer every group is one task head of the RegLayer (mv2d_reg_layer_x3: 1 to 10 groups)
+        self.use_reg_layer = bool(use_reg_layer)
+        self.group_reg_dims = ops.check_group_reg_dims(group_reg_dims) if self.use_reg_layer else tuple(group_reg_dims)
         # the class output layer of the fused prediction branches (mv2d_heads_fused_x3_nc) holds up to 4 column tiles of 16 classes
         if not 1 <= int(num_classes) <= 64:
             raise ValueError(f'CrossAttentionBoxHead: num_classes must be in [1, 64] (the fused heads kernel), got {num_classes}')
@@ -59,7 +81,8 @@ class CrossAttentionBoxHead(nn.Module):
             reg_branch += [nn.Linear(embed_dims, embed_dims), nn.ReLU()]
         reg_branch.append(nn.Linear(embed_dims, sum(group_reg_dims)))
         self.cls_branches = nn.ModuleList([copy.deepcopy(nn.Sequential(*cls_branch)) for _ in range(self.num_pred)])
-        self.reg_branches = nn.ModuleList([copy.deepcopy(nn.Sequential(*reg_branch)) for _ in range(self.num_pred)])
+        reg_branch = RegLayer(embed_dims, num_reg_fcs, self.group_reg_dims) if self.use_reg_layer else nn.Sequential(*reg_branch)
+        self.reg_branches = nn.ModuleList([copy.deepcopy(reg_branch) for _ in range(self.num_pred)])
         self.bbox_coder = build_bbox_coder(bbox_coder)
         self.code_size = kwargs.get('code_size', 10)
         cw = kwargs.get('code_weights', [1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 0.2, 0.2])[:self.code_size]
@@ -104,13 +127,28 @@ class CrossAttentionBoxHead(nn.Module):
         NC = self.num_classes
         cls = torch.empty((L, M, NC), device=dev)
         ops.gemm_f32(h2, st(6, 'weight'), st(6, 'bias'), out=cls, M=M, lda=C, ldc=NC, groups=L, a_gs=M * C, c_gs=M * NC)
+        ref = reference_points.reshape(M, 3).float().contiguous()
+        pc_range_h = torch.tensor(self.pc_range, dtype=torch.float32)
+        if self.use_reg_layer:
+            # the RegLayer branches + the box-code tail in one launch (csrc/reglayer.hip)
+            del self._cur
+            one = lambda name: torch.stack([_f(br.get_parameter(name)) for br in self.reg_branches])
+            per_group = lambda fmt, join: torch.stack([join([_f(br.get_parameter(fmt.format(g))) for g in range(len(self.group_reg_dims))])
+                                                       for br in self.reg_branches])
+            table = ops.pack_reg_layer(one('reg_branch.0.weight'), one('reg_branch.0.bias'), one('reg_branch.3.weight'), one('reg_branch.3.bias'),
+                                       per_group('task_heads.{}.0.weight', torch.stack), per_group('task_heads.{}.0.bias', torch.stack),
+                                       per_group('task_heads.{}.2.weight', torch.cat), per_group('task_heads.{}.2.bias', torch.cat))
+            reg = torch.empty((L, M, 10), device=dev)
+            ops.reg_layer_x3(od, ops.make_ptr_array(table), ref, reg, M, L, self.group_reg_dims, pc_range_h, 0.0)
+            all_cls_scores, all_bbox_preds = cls.view(L, bs, Q, NC), reg.view(L, bs, Q, 10)
+            return (all_cls_scores, all_bbox_preds, outs_dec[-1]) if return_query_feats else (all_cls_scores, all_bbox_preds)
         self._cur = self.reg_branches
         r1 = ops.gemm_f32(od, st(0, 'weight'), st(0, 'bias'), act=1, M=M, lda=C, ldc=C, **gk)
         r2 = ops.gemm_f32(r1, st(2, 'weight'), st(2, 'bias'), act=1, M=M, lda=C, ldc=C, **gk)
         reg = torch.empty((L, M, 10), device=dev)
         ops.gemm_f32(r2, st(4, 'weight'), st(4, 'bias'), out=reg, M=M, lda=C, ldc=10, groups=L, a_gs=M * C, c_gs=M * 10)
         del self._cur
-        ops.finalize_reg(reg, reference_points.reshape(M, 3).float().contiguous(), L, M, torch.tensor(self.pc_range, dtype=torch.float32), 0.0)
+        ops.finalize_reg(reg, ref, L, M, pc_range_h, 0.0)
         all_cls_scores, all_bbox_preds = cls.view(L, bs, Q, NC), reg.view(L, bs, Q, 10)
         if return_query_feats:
             return all_cls_scores, all_bbox_preds, outs_dec[-1]
@@ -232,6 +270,8 @@ class MV2DHead(nn.Module):
                                       pc_range=tuple(self.pc_range), post_range=tuple(coder.post_center_range),
                                       depth_num=self.position_encoding.depth_num, stride=self.strides[self.feat_lvl],
                                       iou_thr=bc.iou_thr, ratio=bc.ratio, num_classes=self.bbox_head.num_classes, roi_size=self.roi_cells,
+                                      use_reg_layer=getattr(self.bbox_head, 'use_reg_layer', False),
+                                      group_reg_dims=getattr(self.bbox_head, 'group_reg_dims', (2, 2, 1, 1, 2, 2)),
                                       masked_row=(self.test_cfg or {}).get('masked_row', 'nan'),
                                       exact=(self.test_cfg or {}).get('index_exact', None))      # None: MV2D_EXACT decides
             if 'lo8_rows' in (self.test_cfg or {}):                              # test_cfg.lo8_rows=False: fp16 lo halves of the key / value rows (engine.py; default: e4m3 bytes)

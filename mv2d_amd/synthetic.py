@@ -193,6 +193,33 @@ def make_head_state(seed=0, num_layers=NUM_LAYERS, num_classes=NUM_CLASSES):
 # ---------------------------------------------------------------------------------------------
 # The five BASELINE.json configs as concrete synthetic problems.
 # ---------------------------------------------------------------------------------------------
+def make_reg_layer_state(seed=0, num_layers=NUM_LAYERS, group_reg_dims=(2, 2, 1, 1, 2, 2)):
+    """The regression branches as the reference's RegLayer (CrossAttentionBoxHead(use_reg_layer=True)): OrderedDict of
+    ``bbox_head.reg_branches.{l}.reg_branch.{0,3}.*`` (two shared Linear(256,256)) and ``.task_heads.{g}.{0,2}.*`` (Linear(256,256),
+    Linear(256,d_g) per group).  To be merged over make_head_state's dict AFTER dropping its ``bbox_head.reg_branches.*`` keys
+    (with_reg_layer_state does both); its own stream of draws, make_head_state is untouched."""
+    g = _rng(seed + 7919)
+    C = EMBED
+    sd = OrderedDict()
+    for l in range(num_layers):
+        p = f'bbox_head.reg_branches.{l}.'
+        for n in ('reg_branch.0', 'reg_branch.3'):
+            sd[f'{p}{n}.weight'] = _xavier(g, (C, C)); sd[f'{p}{n}.bias'] = _bias(g, C)
+        for t, d in enumerate(group_reg_dims):
+            sd[f'{p}task_heads.{t}.0.weight'] = _xavier(g, (C, C)); sd[f'{p}task_heads.{t}.0.bias'] = _bias(g, C)
+            # (the gain of the 10-row output layer of the shipped branch, whatever the group's width)
+            sd[f'{p}task_heads.{t}.2.weight'] = _xavier(g, (CODE_SIZE, C))[:d].copy(); sd[f'{p}task_heads.{t}.2.bias'] = _bias(g, d, 0.3)
+    return sd
+
+
+def with_reg_layer_state(sd, seed=0, group_reg_dims=(2, 2, 1, 1, 2, 2)):
+    """A copy of a make_head_state dict with its regression branches replaced by make_reg_layer_state's."""
+    num_layers = len({k.split('.')[2] for k in sd if k.startswith('bbox_head.reg_branches.')})
+    out = OrderedDict((k, v) for k, v in sd.items() if not k.startswith('bbox_head.reg_branches.'))
+    out.update(make_reg_layer_state(seed, num_layers, group_reg_dims))
+    return out
+
+
 WORKLOADS = {
     # name: (head kind, views/frame, frames, img_h, img_w, pad_w, boxes/view)
     'micro_t': ('T', 2, 1, 128, 192, None, 6),

@@ -252,6 +252,8 @@ class TrainDecoder:
         # nn.Dropout objects of the reference's layers (mmcv MultiheadAttention: attn_drop on the probabilities + dropout_layer on the
         # output path; FFN: after the activation and after the second linear); they are applied here when the head is in training mode
         self.roi_head = roi_head
+        # RegLayer regression branches (the head's use_reg_layer switch): the branches then run as per-operator autograd nodes, not as HeadsFn
+        self.use_reg_layer, self.group_reg_dims = bool(getattr(bh, 'use_reg_layer', False)), tuple(getattr(bh, 'group_reg_dims', ()))
         self.layers = getattr(getattr(bh.transformer, 'decoder', None), 'layers', None)
         self._warned = False
         import os
@@ -406,6 +408,8 @@ class TrainDecoder:
         ln = lambda t, n: layer_norm(t, P[n + '.weight'], P[n + '.bias'])  # noqa: E731
         if torch.is_tensor(outs) and outs.shape[1] == 0:
             outs = list(outs.unbind(0))
+        if torch.is_tensor(outs) and self.use_reg_layer:
+            outs = list(outs.unbind(0))
         if torch.is_tensor(outs):
             # (round 5) all branches of all layers as one autograd node, the layers side by side on streams (mv2d_train_heads_fwd / _bwd)
             from .autograd_ops import BRANCH_PARAMS, HeadsFn
@@ -418,6 +422,12 @@ class TrainDecoder:
             y = F.relu(ln(linear(outs[l], P[c + '0.weight'], P[c + '0.bias']), c + '1'))
             y = F.relu(ln(linear(y, P[c + '3.weight'], P[c + '3.bias']), c + '4'))
             all_cls.append(linear(y, P[c + '6.weight'], P[c + '6.bias']))
+            if self.use_reg_layer:
+                # RegLayer (cross_attention_head.py:52-83): two shared linears, then one Linear-ReLU-Linear task head per group, concatenated
+                t = linear(linear(outs[l], P[g + 'reg_branch.0.weight'], P[g + 'reg_branch.0.bias'], 1), P[g + 'reg_branch.3.weight'], P[g + 'reg_branch.3.bias'], 1)
+                ts.append(torch.cat([linear(linear(t, P[f'{g}task_heads.{k}.0.weight'], P[f'{g}task_heads.{k}.0.bias'], 1),
+                                            P[f'{g}task_heads.{k}.2.weight'], P[f'{g}task_heads.{k}.2.bias']) for k in range(len(self.group_reg_dims))], -1))
+                continue
             t = linear(outs[l], P[g + '0.weight'], P[g + '0.bias'], 1)
             ts.append(linear(linear(t, P[g + '2.weight'], P[g + '2.bias'], 1), P[g + '4.weight'], P[g + '4.bias']))
         return torch.stack(all_cls), self._box_code(torch.stack(ts), ref, pad, dt)
