@@ -16,43 +16,11 @@
 //
 // mv2d_xattn_group_tables builds the per-group tables once per frame from the CSR and a query order (groups = runs of 8 consecutive slots of
 // a sample's order: queries that share keys should be neighbours in it -- mv2d_xattn_query_order, or mv2d_xattn_cluster_order below).
-#include "common.h"
+#include "xattn_walk.h"
 
 namespace {
 
-constexpr int C = 256, HEADS = 8, QB = 8;
-constexpr float LOG2E = 1.4426950408889634f;
-
-typedef q16x8_t xg_q16x8;
-union XgFrag { uint4 u; xg_q16x8 v; };
-typedef unsigned int xg_u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void xg_split8(const float4& x0, const float4& x1, XgFrag& hi, XgFrag& lo) {
-    const float f[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
-    unsigned int h[4], l[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) split_q16x2(f[2 * i], f[2 * i + 1], h[i], l[i]);
-    hi.u = make_uint4(h[0], h[1], h[2], h[3]);
-    lo.u = make_uint4(l[0], l[1], l[2], l[3]);
-}
-__device__ __forceinline__ void xg_split8_k16(const float4& x0, const float4& x1, XgFrag& hi, XgFrag& lo) {
-    const float f[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
-    unsigned int h[4], l[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) split_k16x2(f[2 * i], f[2 * i + 1], h[i], l[i]);
-    hi.u = make_uint4(h[0], h[1], h[2], h[3]);
-    lo.u = make_uint4(l[0], l[1], l[2], l[3]);
-}
-__device__ __forceinline__ unsigned int xg_lo_pair(unsigned int a, unsigned int b) { return __builtin_amdgcn_perm(b, a, 0x05040100u); }
-__device__ __forceinline__ unsigned int xg_hi_pair(unsigned int a, unsigned int b) { return __builtin_amdgcn_perm(b, a, 0x07060302u); }
-#define XG_DPP(v, ctrl) __uint_as_float((unsigned)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(v), ctrl, 0xF, 0xF, true))
-__device__ __forceinline__ float xg_row16_max(float v) {
-    v = fmaxf(v, XG_DPP(v, 0xB1));
-    v = fmaxf(v, XG_DPP(v, 0x4E));
-    v = fmaxf(v, XG_DPP(v, 0x141));
-    v = fmaxf(v, XG_DPP(v, 0x140));
-    return v;
-}
+constexpr int QB = 8;
 
 // ------------------------------------------------------------------------------------------------------------------------------
 // group tables.  One block per group g: members = the (up to 8) query rows order[slot0 .. slot0 + cnt) of ONE sample (a sample's result must not
@@ -353,20 +321,20 @@ __global__ __launch_bounds__(64 * QB, 2) void xattn_group_kernel(const float* __
         if (t < ntile) issue(t);
     // ---------------------------------------------------------------- phase A: Qt_h of the group's queries (split-precision MFMAs on the fp32 query,
     // packed weights WA from L2; xattn_fused.hip) -> the wave's scratch -> its A operand: row n = (query n & 7, part n >> 3)
-    XgFrag qa[8];
+    Frag qa[8];
     {
         const int r = rq[n & 7];
         const float* qp = q + (long long)r * C + 32 * h + 8 * g;
-        XgFrag bh, bl;
-        xg_split8(*reinterpret_cast<const float4*>(qp), *reinterpret_cast<const float4*>(qp + 4), bh, bl);
+        Frag bh, bl;
+        split8(*reinterpret_cast<const float4*>(qp), *reinterpret_cast<const float4*>(qp + 4), bh, bl);
         const uint4* wh = WA_hi + (long long)h * 16 * 64 + lane;
         const uint4* wl = WA_lo + (long long)h * 16 * 64 + lane;
         uint4* qt = reinterpret_cast<uint4*>(scr) + (n & 7) * 64;
-        xg_u32x4 wa_h[16], wa_l[16];
+        u32x4 wa_h[16], wa_l[16];
 #pragma unroll
         for (int t = 0; t < 16; ++t) {
-            wa_h[t] = *reinterpret_cast<const xg_u32x4*>(wh + t * 64);
-            wa_l[t] = *reinterpret_cast<const xg_u32x4*>(wl + t * 64);
+            wa_h[t] = *reinterpret_cast<const u32x4*>(wh + t * 64);
+            wa_l[t] = *reinterpret_cast<const u32x4*>(wl + t * 64);
         }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -380,8 +348,8 @@ __global__ __launch_bounds__(64 * QB, 2) void xattn_group_kernel(const float* __
                 c = mfma_q16_16x16x32(wa_h[2 * u + k], bh.v, c);
                 a[k] = c;
             }
-            XgFrag hi, lo;
-            xg_split8_k16(make_float4(a[0][0], a[0][1], a[0][2], a[0][3]), make_float4(a[1][0], a[1][1], a[1][2], a[1][3]), hi, lo);
+            Frag hi, lo;
+            split8_k16(make_float4(a[0][0], a[0][1], a[0][2], a[0][3]), make_float4(a[1][0], a[1][1], a[1][2], a[1][3]), hi, lo);
             if (n < 8) {
                 qt[u * 8 + g * 2] = hi.u;
                 qt[u * 8 + g * 2 + 1] = lo.u;
@@ -432,7 +400,7 @@ __global__ __launch_bounds__(64 * QB, 2) void xattn_group_kernel(const float* __
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const float tm = xg_row16_max(sv[i]);
+            const float tm = row16_max(sv[i]);
             const float m_new = fmaxf(m_run[i], tm);
             const float m_use = m_new == -INFINITY ? 0.f : m_new;          // a query that lists no key so far: p = 0, nothing to rescale
             const bool moved = m_new != m_run[i];
@@ -529,11 +497,11 @@ __global__ __launch_bounds__(64 * QB, 2) void xattn_group_kernel(const float* __
         const uint4* wh = WB_hi + (long long)h * 16 * 64 + lane;
         const uint4* wl = WB_lo + (long long)h * 16 * 64 + lane;
         f32x4_t acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-        xg_u32x4 wb_h[16], wb_l[16];
+        u32x4 wb_h[16], wb_l[16];
 #pragma unroll
         for (int t = 0; t < 16; ++t) {
-            wb_h[t] = *reinterpret_cast<const xg_u32x4*>(wh + t * 64);
-            wb_l[t] = *reinterpret_cast<const xg_u32x4*>(wl + t * 64);
+            wb_h[t] = *reinterpret_cast<const u32x4*>(wh + t * 64);
+            wb_l[t] = *reinterpret_cast<const u32x4*>(wl + t * 64);
         }
         int rr_[4], rp0_[4], rp1_[4];
 #pragma unroll
@@ -548,8 +516,8 @@ __global__ __launch_bounds__(64 * QB, 2) void xattn_group_kernel(const float* __
         for (int s = 0; s < 8; ++s) {
             const float4 x0 = *reinterpret_cast<const float4*>(zp + 32 * s);
             const float4 x1 = *reinterpret_cast<const float4*>(zp + 32 * s + 4);
-            XgFrag ah, al;
-            xg_split8(x0, x1, ah, al);
+            Frag ah, al;
+            split8(x0, x1, ah, al);
 #pragma unroll
             for (int nt = 0; nt < 2; ++nt) {
                 acc[nt] = mfma_q16_16x16x32(al.v, wb_h[s * 2 + nt], acc[nt]);

@@ -696,6 +696,33 @@ def test_xattn_tile_equals_projected_attention(dev, R, S, dens, waves):
         assert bool(torch.isnan(cn[5]).all()) and torch.equal(cn[6:], ctx[6:])
 
 
+def test_xattn_tile_debug_logits_only_add_a_store(dev):
+    """The debug instances of the tile kernel on the index-exact route (hi + key16 lo rows, hi + e4m3 lo rows; csrc/xattn_walk.h: the DBG parameter of
+    the shared tile walk): the same z, bit for bit, as without dbg_logits, and a finite logit written for every listed (query, key) pair.  Rows of
+    ~90 keys on 4 waves: every wave walks tiles and has a ragged last one; an empty row and a single-key row."""
+    from mv2d_amd import ops
+    from oracle import mv2d_oracle as O
+    R, S = 20, 300
+    g = np.random.Generator(np.random.PCG64(760))
+    allowed = torch.from_numpy(g.random((R, S)) < 0.3)
+    allowed[5] = False
+    allowed[7, :] = False
+    allowed[7, 123] = True
+    q = (rnd((R, 256), 761) * 0.3).to(dev)
+    Xk, Xk_lo = ops.f32_to_key16(rnd((S, 256), 762).to(dev), with_lo=True)
+    Xv, Xv_lo = ops.f32_to_key16(rnd((S, 256), 763).to(dev), with_lo=True)
+    WA, _ = ops.pack_xattn_maps(rnd((256, 256), 764, 0.06).to(dev), rnd((256, 256), 766, 0.06).to(dev))
+    row_ptr, col = O.csr_from_allowed(allowed)
+    row_ptr, col = row_ptr.to(dev), col.to(dev)
+    Qt = ops.xattn_qmap(q, WA)
+    for k_lo, v_lo in ((Xk_lo, Xv_lo), (ops.lo8_encode(Xk_lo), ops.lo8_encode(Xv_lo))):
+        dbg = torch.full((8, int(col.numel())), float('nan'), device=dev)
+        z_dbg = ops.xattn_tile(Qt, Xk, Xv, row_ptr, col, empty_nan=False, waves=4, Xk_lo=k_lo, Xv_lo=v_lo, dbg_logits=dbg)
+        z = ops.xattn_tile(Qt, Xk, Xv, row_ptr, col, empty_nan=False, waves=4, Xk_lo=k_lo, Xv_lo=v_lo)
+        assert torch.equal(z_dbg, z), k_lo.dtype
+        assert bool(torch.isfinite(dbg).all()), k_lo.dtype
+
+
 # ------------------------------------------------------------------------------------------ geometry
 def _problem(name):
     prob = synthetic.make_problem(name, seed=0)

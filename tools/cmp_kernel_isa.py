@@ -1,12 +1,17 @@
 #!/usr/bin/env python
 """Are the instruction streams of a source file's kernels what they were at another commit?
 
-    python tools/cmp_kernel_isa.py <git-rev> rows.hip geometry.hip pe_x3.hip pe_tab96.hip
+    python tools/cmp_kernel_isa.py [--work-classes] <git-rev> rows.hip geometry.hip pe_x3.hip pe_tab96.hip
 
 Compiles mv2d_amd/csrc/<file> of <git-rev> and of the working tree for gfx950 (device code only, the flags of mv2d_amd/build.py), disassembles both code
 objects with llvm-objdump -d and compares kernel by kernel.  A kernel that gained a template argument is matched with its `float` instance
 (`roi_align_kernel` <-> `roi_align_kernel<float>`, `pe_inputs_kernel<true>` <-> `pe_inputs_kernel<true, float>`).  No GPU needed.  Exit status 1
-when a kernel of <git-rev> is missing or differs."""
+when a kernel of <git-rev> is missing or differs.
+
+--work-classes: for code that moved between functions, where the compiler re-numbers registers and re-pairs scalar arithmetic.  A kernel that
+differs gets its old and new instruction counts per opcode prefix printed, and passes when the counts of the WORK classes are equal: MFMAs, global
+loads and stores, LDS instructions, v_exp / v_rcp / v_perm / v_cvt, barriers and every DPP instruction.  (Two v_mul_f32 that became one
+v_pk_mul_f32 give the same bits; an MFMA, a load or a conversion more or less does not.)"""
 import os
 import re
 import subprocess
@@ -45,8 +50,37 @@ def kernels(src, tmp, tag):
     return res
 
 
+WORK = ('v_mfma', 'global_load', 'global_store', 'ds_', 'v_exp', 'v_rcp', 'v_perm', 'v_cvt', 's_barrier')
+
+
+def classes(ins):
+    """instruction count per opcode prefix: the work classes by their names, `*_dpp`, everything else by its first two words (v_mul, s_add, ...)"""
+    out = {}
+    for i in ins:
+        op = i.split()[0]
+        key = next((w for w in WORK if op.startswith(w)), None) or ('*_dpp' if op.endswith('_dpp') else '_'.join(op.split('_')[:2]))
+        out[key] = out.get(key, 0) + 1
+    return out
+
+
+def work_equal(old, new, label):
+    a, b = classes(old), classes(new)
+    same = True
+    for key in sorted(set(a) | set(b)):
+        work = key in WORK or key == '*_dpp'
+        if a.get(key, 0) != b.get(key, 0):
+            print('    %-14s %6d -> %6d%s' % (key, a.get(key, 0), b.get(key, 0), '   <-- WORK CLASS' if work else ''))
+            same = same and not work
+        elif work:
+            print('    %-14s %6d    %6d' % (key, a[key], b[key]))
+    return same
+
+
 def main():
-    rev, files = sys.argv[1], sys.argv[2:]
+    args = sys.argv[1:]
+    by_class = '--work-classes' in args
+    args = [a for a in args if a != '--work-classes']
+    rev, files = args[0], args[1:]
     bad = 0
     with tempfile.TemporaryDirectory() as tmp:
         old = os.path.join(tmp, 'old')
@@ -60,8 +94,13 @@ def main():
                 cands = [name, name + '<float>', re.sub(r'>$', ', float>', name)]
                 now = next((c for c in cands if c in b), None)
                 verdict = 'MISSING' if now is None else ('identical' if b[now] == ins else 'DIFFERENT (%d -> %d instructions)' % (len(ins), len(b[now])))
-                bad += verdict != 'identical'
                 print('%-14s %-78s %6d  %s' % (f, (now or name)[:78], len(ins), verdict))
+                if by_class and verdict.startswith('DIFFERENT'):
+                    ok = work_equal(ins, b[now], now)
+                    print('    -> work classes %s' % ('equal' if ok else 'DIFFER'))
+                    bad += not ok
+                else:
+                    bad += verdict != 'identical'
     return 1 if bad else 0
 
 
