@@ -136,6 +136,16 @@ int mv2d_pe_fused_x3_fmt(const float* A1, const void* Xmap, const int* row_index
                          const void* Wr_hi, const void* Wr_lo, const float* br, const void* We_hi, const void* We_lo, const float* be,
                          const float* sine_tab, int tab_period, float* pe, void* Xk_hi, void* Xk_lo, void* Xv_hi, void* Xv_lo, int lo_fmt, int pe_at_index,
                          int* lo8_flag, int map_fmt, void* stream);
+/* mv2d_pe_fused_x3_fmt for any number of depth bins (PE depth_num 8 .. 80 in steps of 8).  Kp = 32 * ceil(3 * depth_num / 32), a multiple of 32 in
+ * [32, 256], is the number of columns AND the row pitch of A1 [M,Kp] fp32 and the K of W1a ([1024,Kp] before packing): both are zero-padded from
+ * 3 * depth_num to Kp columns (mv2d_pe_frustum_f32_ld / mv2d_pe_inputs_ld write such rows; a padded column adds exactly +0 to the fp32 accumulators).
+ * One compile-time instance of the kernel per Kp / 32; Kp = 192 runs the instance of mv2d_pe_fused_x3_fmt, which is this entry with Kp = 192.  Any
+ * other Kp is an argument error.  (mv2d_pe_fused_tab* and mv2d_pe_fused_x3b stay 64-bin kernels.) */
+int mv2d_pe_fused_x3_k(const float* A1, const void* Xmap, const int* row_index, const int* m_dev, int M,
+                       const void* W1a_hi, const void* W1a_lo, const float* b1a, const void* W1b_hi, const void* W1b_lo, const float* b1b,
+                       const void* Wr_hi, const void* Wr_lo, const float* br, const void* We_hi, const void* We_lo, const float* be,
+                       const float* sine_tab, int tab_period, float* pe, void* Xk_hi, void* Xk_lo, void* Xv_hi, void* Xv_lo, int lo_fmt, int pe_at_index,
+                       int* lo8_flag, int map_fmt, int Kp, void* stream);
 /* The same block on the second shape of the kernel (round 6, csrc/pe_x3b.hip): a wave owns 16 rows through both layers of each MLP, the hidden layer
  * stays in registers (no LDS image, no barrier between the layers), the weights go through a 4-deep LDS ring (LDS-DMA) shared by the 8 waves of a 128-row
  * block, two waves per SIMD.  Same operands EXCEPT that W1a and Wr (the first layers) are packed from the weight with its rows in the order
@@ -545,6 +555,10 @@ int mv2d_roi_positions_csr_s(const float* rois, const unsigned char* pad_mask, u
  * logarithm table travels as a kernel argument (round 6): no per-device state, safe inside a stream capture and with several GPUs per process. */
 int mv2d_pe_frustum_f32(const int* s2pos, const int* S_dev, int S_max, const double* img2lidar, const double* coords_w, const double* coords_h,
                         const double* coords_d, float* out, int V, int h, int w, int depth_num, const double* position_range, void* stream);
+/* mv2d_pe_frustum_f32 with a row pitch: out [S, ld] fp32, ld in [3 * depth_num, 1024]; the kernel itself writes zeros into the columns
+ * 3 * depth_num .. ld - 1 of every row it writes (no zeroed buffer needed).  mv2d_pe_frustum_f32 is this entry with ld = 3 * depth_num. */
+int mv2d_pe_frustum_f32_ld(const int* s2pos, const int* S_dev, int S_max, const double* img2lidar, const double* coords_w, const double* coords_h,
+                           const double* coords_d, float* out, int V, int h, int w, int depth_num, const double* position_range, int ld, void* stream);
 
 /* PE inputs at the listed key positions only (MU/pe.py:84-135 frustum, MU/positional_encoding.py:78-95 sine) + feature gather.
  * out: A_frustum [S,3*D] key16, A_sine [S,384] key16, Xf_k16 [S,256] key16, Xf_f32 [S,256] (optional: NULL when mv2d_pe_fused_tab reads the map).
@@ -560,6 +574,13 @@ int mv2d_pe_inputs_fmt(const int* s2pos, const int* S_dev, int S_max, const void
                        const double* coords_w, const double* coords_h, const double* coords_d, const float* embeds,
                        const float* dim_t, void* A_frustum, void* A_sine, void* Xf_k16, float* Xf_f32, float* A_frustum_f32,
                        float* A_sine_f32, int V, int h, int w, int depth_num, const double* position_range, int map_fmt, void* stream);
+/* mv2d_pe_inputs_fmt with a row pitch for the frustum rows: A_frustum [S,ld] key16 and A_frustum_f32 [S,ld] fp32, ld a multiple of 8 in
+ * [3 * depth_num, 768]; the kernel itself writes zeros into their columns 3 * depth_num .. ld - 1 (no zeroed buffer needed).  The other rows keep
+ * their pitches.  mv2d_pe_inputs_fmt is this entry with ld = 3 * depth_num. */
+int mv2d_pe_inputs_ld(const int* s2pos, const int* S_dev, int S_max, const void* featcl, const double* img2lidar,
+                      const double* coords_w, const double* coords_h, const double* coords_d, const float* embeds,
+                      const float* dim_t, void* A_frustum, void* A_sine, void* Xf_k16, float* Xf_f32, float* A_frustum_f32,
+                      float* A_sine_f32, int V, int h, int w, int depth_num, const double* position_range, int map_fmt, int ld, void* stream);
 
 /* NMSFreeCoder.decode_single + get_bboxes (CB/coders/nms_free_coder.py:49-102, CB/util.py:60-87,
  * RH/bbox_heads/cross_attention_head.py:357-377): top-k over R*num_classes logits, denormalise, centre-range filter.

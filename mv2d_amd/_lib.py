@@ -42,6 +42,7 @@ SIGNATURES = {
     'mv2d_pe_fused_x3': (I, [P, P, P, P, I] + [P] * 13 + [I] + [P] * 5 + [I, I, P, P]),
     'mv2d_pe_fused_tab_fmt': (I, [P, P, P, P, P, I] + [P] * 9 + [I, P, P, I, I, P]),
     'mv2d_pe_fused_x3_fmt': (I, [P, P, P, P, I] + [P] * 13 + [I] + [P] * 5 + [I, I, P, I, P]),
+    'mv2d_pe_fused_x3_k': (I, [P, P, P, P, I] + [P] * 13 + [I] + [P] * 5 + [I, I, P, I, I, P]),
     'mv2d_pe_fused_x3b': (I, [P, P, P, P, I] + [P] * 13 + [I] + [P] * 5 + [I, I, P, P]),
     'mv2d_key16_format': (I, []),
     'mv2d_f32_to_key16': (I, [P, P, P, LL, P]),
@@ -122,6 +123,8 @@ SIGNATURES = {
     'mv2d_pe_inputs': (I, [P, P, I, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, P, P]),
     'mv2d_pe_inputs_fmt': (I, [P, P, I, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, P, I, P]),
     'mv2d_pe_frustum_f32': (I, [P, P, I, P, P, P, P, P, I, I, I, I, P, P]),
+    'mv2d_pe_frustum_f32_ld': (I, [P, P, I, P, P, P, P, P, I, I, I, I, P, I, P]),
+    'mv2d_pe_inputs_ld': (I, [P, P, I, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, P, I, I, P]),
     'mv2d_result_pack': (I, [P, P, P, P, F, I, P, P, P, P, I, I, P]),
     'mv2d_nms_bev': (I, [P, P, P, P, F, P, I, I, P]),
     'mv2d_pack_detections': (I, [P, P, P, P, P, I, I, I, P]),

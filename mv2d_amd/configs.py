@@ -92,6 +92,17 @@ def _set_roi_size(d, roi_size):
     return d
 
 
+def _set_pe_depth(d, depth_num, depth_start, position_range):
+    # the reference PE's ``depth_num`` / ``depth_start`` / ``position_range`` (MU/pe.py:52-63).  The shipped configs leave depth_start at the PE's
+    # default (no key) and set position_range = POST_RANGE: the defaults here give exactly that dict
+    d['pe']['depth_num'] = depth_num
+    if depth_start != 1:
+        d['pe']['depth_start'] = depth_start
+    if position_range is not None:
+        d['pe']['position_range'] = list(position_range)
+    return d
+
+
 def _set_reg_layer(d, group_reg_dims):
     # ``bbox_head.use_reg_layer`` / ``group_reg_dims`` of the reference head; None leaves the shipped Sequential regression branches (no key added)
     if group_reg_dims is not None:
@@ -99,22 +110,25 @@ def _set_reg_layer(d, group_reg_dims):
     return d
 
 
-def roi_head_cfg_s(num_classes=10, roi_size=ROI_SIZE, reg_layer_dims=None):
+def roi_head_cfg_s(num_classes=10, roi_size=ROI_SIZE, reg_layer_dims=None, depth_num=64, depth_start=1, position_range=None):
     """CFG-S:40-121 (MV2D-S single frame); ``num_classes`` sets ``bbox_head.num_classes`` and ``bbox_head.bbox_coder.num_classes``,
     ``roi_size`` sets ``bbox_roi_extractor.roi_layer.output_size`` and ``query_generator.roi_feat_size``; ``reg_layer_dims`` (a tuple of
-    group widths) sets ``bbox_head.use_reg_layer=True`` with that ``group_reg_dims``."""
+    group widths) sets ``bbox_head.use_reg_layer=True`` with that ``group_reg_dims``; ``depth_num`` (a multiple of 8 in [8, 80]), ``depth_start``
+    and ``position_range`` (None: the shipped POST_RANGE) set the keys of the same names in ``pe``."""
     d = dict(type='MV2DSHead', use_denoise=False)
     d.update(_common(with_cp=False))
     d['box_correlation'] = dict(correlation_mode='topk_matched:1:0.0:0.0')
+    d = _set_pe_depth(d, depth_num, depth_start, position_range)
     return copy.deepcopy(_set_reg_layer(_set_roi_size(_set_num_classes(d, num_classes), roi_size), reg_layer_dims))
 
 
-def roi_head_cfg_t(num_classes=10, roi_size=ROI_SIZE, reg_layer_dims=None):
-    """CFG-T:40-125 (MV2D-T two frames); ``num_classes``, ``roi_size`` and ``reg_layer_dims`` as in ``roi_head_cfg_s``."""
+def roi_head_cfg_t(num_classes=10, roi_size=ROI_SIZE, reg_layer_dims=None, depth_num=64, depth_start=1, position_range=None):
+    """CFG-T:40-125 (MV2D-T two frames); ``num_classes``, ``roi_size``, ``reg_layer_dims`` and the three ``pe`` keys as in ``roi_head_cfg_s``."""
     d = dict(type='MV2DTHead', use_denoise=True, neg_bbox_loss=True,
              denoise_noise_scale=1.25, denoise_split=0.6)
     d.update(_common(with_cp=True))
     d['box_correlation'] = dict(expand_stride=2, correlation_mode='topk_matched:20:0.0:0.0')
+    d = _set_pe_depth(d, depth_num, depth_start, position_range)
     return copy.deepcopy(_set_reg_layer(_set_roi_size(_set_num_classes(d, num_classes), roi_size), reg_layer_dims))
 
 

@@ -947,35 +947,23 @@ __global__ __launch_bounds__(256) void pe_frustum_f32_kernel(const int* __restri
                                                              const double* __restrict__ coords_w, const double* __restrict__ coords_h,
                                                              const double* __restrict__ coords_d, float* __restrict__ out, int h, int w, int D,
                                                              double pr0, double pr1, double pr2, double ipd0, double ipd1, double ipd2, LogTab lt) {
-    __shared__ double tab[256];
-    tab[threadIdx.x] = lt.t[threadIdx.x];
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int S = *S_dev;
-    for (int s = blockIdx.x * 4 + wave; s < S; s += gridDim.x * 4) {
-        const int pos = __builtin_amdgcn_readfirstlane(s2pos[s]);
-        const int v = pos / (h * w), rem = pos - v * h * w, y = rem / w, x = rem - y * w;
-        const double* M = img2lidar + v * 16;
-        const double cw = coords_w[x], chh = coords_h[y];
-        const double u[3] = {fma(M[0], cw, M[1] * chh), fma(M[4], cw, M[5] * chh), fma(M[8], cw, M[9] * chh)};
-        const double m2[3] = {M[2], M[6], M[10]}, m3[3] = {M[3] - pr0, M[7] - pr1, M[11] - pr2};
-        const double ipd[3] = {ipd0, ipd1, ipd2};
-        for (int dk = lane; dk < D; dk += 64) {
-            const double d = coords_d[dk];
-            const double dm = d < 1e-3 ? 1e-3 : d;
-            float o[3];
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                double n = fma(u[i], dm, fma(m2[i], d, m3[i])) * ipd[i];
-                n = n < 0.0 ? 0.0 : (n > 1.0 ? 1.0 : n);
-                const double x1 = n < 1e-5 ? 1e-5 : n;
-                const double x2 = (1.0 - n) < 1e-5 ? 1e-5 : (1.0 - n);
-                o[i] = (float)log_diff_tab(x1, x2, tab);
-            }
-            float* dst = out + (long long)s * (3 * D) + dk * 3;
-            dst[0] = o[0]; dst[1] = o[1]; dst[2] = o[2];
-        }
-    }
+#define MV2D_FR_LD (3 * D)
+#define MV2D_FR_PITCHED 0
+#include "pe_frustum_body.inc"
+#undef MV2D_FR_LD
+#undef MV2D_FR_PITCHED
+}
+
+// the same rows with pitch ld >= 3 D (the padded rows of mv2d_pe_fused_x3_k): the pad columns are written as zeros
+__global__ __launch_bounds__(256) void pe_frustum_f32_ld_kernel(const int* __restrict__ s2pos, const int* __restrict__ S_dev, const double* __restrict__ img2lidar,
+                                                             const double* __restrict__ coords_w, const double* __restrict__ coords_h,
+                                                             const double* __restrict__ coords_d, float* __restrict__ out, int h, int w, int D,
+                                                             double pr0, double pr1, double pr2, double ipd0, double ipd1, double ipd2, LogTab lt, int ld) {
+#define MV2D_FR_LD ld
+#define MV2D_FR_PITCHED 1
+#include "pe_frustum_body.inc"
+#undef MV2D_FR_LD
+#undef MV2D_FR_PITCHED
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -994,96 +982,27 @@ __global__ __launch_bounds__(256) void pe_inputs_kernel(const int* __restrict__ 
                                                         float* __restrict__ Xf_f32, float* __restrict__ A_frustum_f32, float* __restrict__ A_sine_f32,
                                                         int h, int w, int P, int D, double pr0, double pr1, double pr2,
                                                         double pd0, double pd1, double pd2) {
-    __shared__ __attribute__((aligned(16))) unsigned short rowbuf[4][3 * 256 + 384];      // frustum row (<= 768 values) | sine row (384)
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int s = blockIdx.x * 4 + wave;
-    if (s >= *S_dev) return;                                  // (whole waves leave; no block barrier below)
-    // (the position is the same for all lanes of the wave: made uniform explicitly, so that the per-view matrix and the column / row
-    // coordinates are scalar loads instead of 14 broadcast vector loads per lane)
-    const int pos = __builtin_amdgcn_readfirstlane(s2pos[s]);
-    const int v = pos / (h * w), rem = pos - v * h * w, y = rem / w, x = rem - y * w;
-    unsigned short* fr_row = rowbuf[wave];
-    unsigned short* si_row = rowbuf[wave] + 3 * 256;
-    // feature row gather (fp32 kept for the K = feat + pe sum, key16 for the SE gate and the value rows)
-    {
-        const float4 f = MapElem<MT>::widen(MapElem<MT>::ld4(featcl + (long long)pos * C + 4 * lane));
-        if (Xf_f32) *reinterpret_cast<float4*>(Xf_f32 + (long long)s * C + 4 * lane) = f;
-        *reinterpret_cast<uint2*>(Xf_k16 + (long long)s * C + 4 * lane) = make_uint2(pack_k16x2(f.x, f.y), pack_k16x2(f.z, f.w));
-    }
-    if constexpr (EXACT) {
-        for (int dk = lane; dk < D; dk += 64) {
-            const double d = coords_d[dk];
-            const double dm = d < 1e-3 ? 1e-3 : d;
-            const double p[4] = {coords_w[x] * dm, coords_h[y] * dm, d, 1.0};
-            const double* M = img2lidar + v * 16;
-            const double pr[3] = {pr0, pr1, pr2}, pd[3] = {pd0, pd1, pd2};
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                double acc = 0.0;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) acc = acc + M[i * 4 + k] * p[k];
-                double n = (acc - pr[i]) / pd[i];
-                n = n < 0.0 ? 0.0 : (n > 1.0 ? 1.0 : n);          // inverse_sigmoid: clamp(0,1)
-                const double x1 = n < 1e-5 ? 1e-5 : n;
-                const double x2 = (1.0 - n) < 1e-5 ? 1e-5 : (1.0 - n);
-                fr_row[dk * 3 + i] = f32_to_k16(logf((float)x1 / (float)x2));
-                // index-exact route: the unrounded fp32 row, every step in fp64 and in the reference's operation order (MU/pe.py:119-130)
-                A_frustum_f32[(long long)s * (3 * D) + dk * 3 + i] = (float)log(x1 / x2);
-            }
-        }
-    } else {
-        // default route (round 4): the point of depth bin d is linear in d -- M (cw dm, ch dm, d, 1) = dm (M0 cw + M1 ch) + d M2 + M3 -- so the
-        // per-position part is hoisted (wave-uniform) and a coordinate costs two fp64 FMAs; the normalisation multiplies by 1 / range.  (Before:
-        // 4 fp64 products + sums and an fp64 DIVISION per coordinate, 192 per position; 96.8 -> 88.6 us per 140 k positions.)  The fp64 result
-        // moves by ~1e-16 relative; it is rounded to fp32 for the quotient / logarithm and to key16 right after.
-        const double* M = img2lidar + v * 16;
-        const double cw = coords_w[x], chh = coords_h[y];
-        const double u[3] = {fma(M[0], cw, M[1] * chh), fma(M[4], cw, M[5] * chh), fma(M[8], cw, M[9] * chh)};
-        const double m2[3] = {M[2], M[6], M[10]}, m3[3] = {M[3] - pr0, M[7] - pr1, M[11] - pr2};
-        const double ipd[3] = {1.0 / pd0, 1.0 / pd1, 1.0 / pd2};
-        for (int dk = lane; dk < D; dk += 64) {
-            const double d = coords_d[dk];
-            const double dm = d < 1e-3 ? 1e-3 : d;
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                double n = fma(u[i], dm, fma(m2[i], d, m3[i])) * ipd[i];
-                n = n < 0.0 ? 0.0 : (n > 1.0 ? 1.0 : n);          // inverse_sigmoid: clamp(0,1)
-                const double x1 = n < 1e-5 ? 1e-5 : n;
-                const double x2 = (1.0 - n) < 1e-5 ? 1e-5 : (1.0 - n);
-                // quotient and logarithm in fp32: 1e-7 absolute against a value that is rounded to key16 (fp16) right here
-                fr_row[dk * 3 + i] = f32_to_k16(logf((float)x1 / (float)x2));
-            }
-        }
-    }
-    // sine features, channel order (n | y | x).  NOT interleaved: the reference stacks sin/cos on dim=4 of a
-    // 5-D tensor (MU/positional_encoding.py:86-94), so within an axis channels 0..63 = sin(e / dim_t[2j]) and
-    // channels 64..127 = cos(e / dim_t[2j+1]).
-    if (!A_sine) {                                            // the sine branch comes from the engine's folded table: only the frustum row is needed
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_s_waitcnt(0xc07f);
-        const int nf0 = 3 * D / 8;
-        for (int q = lane; q < nf0; q += 64)
-            *reinterpret_cast<uint4*>(A_frustum + (long long)s * (3 * D) + 8 * q) = *reinterpret_cast<const uint4*>(fr_row + 8 * q);
-        return;
-    }
-    const float en = embeds[pos], ey = embeds[P + pos], ex = embeds[2 * P + pos];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        const int ch = lane + 64 * k;
-        const int axis = ch >> 7, i = ch & 127;
-        const float e = axis == 0 ? en : (axis == 1 ? ey : ex);
-        // arguments lie in [0, 2 pi]: the hardware sin / cos (v_sin_f32 on x / 2 pi, ~1e-6 absolute) is as good as the library call
-        // for a value that is rounded to key16 (fp16) right here
-        const float a = e / dim_t[i < 64 ? 2 * i : 2 * (i - 64) + 1];
-        si_row[ch] = f32_to_k16(i < 64 ? __sinf(a) : __cosf(a));
-        if (EXACT) A_sine_f32[(long long)s * 384 + ch] = i < 64 ? sinf(a) : cosf(a);
-    }
-    __builtin_amdgcn_wave_barrier();                          // the rows are read back by the same wave only
-    __builtin_amdgcn_s_waitcnt(0xc07f);                       // lgkmcnt(0): LDS writes landed
-    const int nf = 3 * D / 8;                                 // 16-byte chunks of the frustum row (D % 8 == 0)
-    for (int q = lane; q < nf; q += 64)
-        *reinterpret_cast<uint4*>(A_frustum + (long long)s * (3 * D) + 8 * q) = *reinterpret_cast<const uint4*>(fr_row + 8 * q);
-    if (lane < 48) *reinterpret_cast<uint4*>(A_sine + (long long)s * 384 + 8 * lane) = *reinterpret_cast<const uint4*>(si_row + 8 * lane);
+#define MV2D_FR_LD (3 * D)
+#define MV2D_FR_PITCHED 0
+#include "pe_inputs_body.inc"
+#undef MV2D_FR_LD
+#undef MV2D_FR_PITCHED
+}
+
+// the same rows with the frustum rows (key16 and fp32) at pitch ld >= 3 D, a multiple of 8: their pad columns are written as zeros
+template <bool EXACT, class MT>
+__global__ __launch_bounds__(256) void pe_inputs_ld_kernel(const int* __restrict__ s2pos, const int* __restrict__ S_dev, const MT* __restrict__ featcl,
+                                                        const double* __restrict__ img2lidar, const double* __restrict__ coords_w, const double* __restrict__ coords_h,
+                                                        const double* __restrict__ coords_d, const float* __restrict__ embeds, const float* __restrict__ dim_t,
+                                                        unsigned short* __restrict__ A_frustum, unsigned short* __restrict__ A_sine, unsigned short* __restrict__ Xf_k16,
+                                                        float* __restrict__ Xf_f32, float* __restrict__ A_frustum_f32, float* __restrict__ A_sine_f32,
+                                                        int h, int w, int P, int D, double pr0, double pr1, double pr2,
+                                                        double pd0, double pd1, double pd2, int ld) {
+#define MV2D_FR_LD ld
+#define MV2D_FR_PITCHED 1
+#include "pe_inputs_body.inc"
+#undef MV2D_FR_LD
+#undef MV2D_FR_PITCHED
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1559,10 +1478,12 @@ extern "C" int mv2d_roi_positions_csr(const float* rois, const unsigned char* pa
                                     Vg, topk, grp_start, n_samples, order, order_flags, 7, stream);
 }
 
-extern "C" int mv2d_pe_frustum_f32(const int* s2pos, const int* S_dev, int S_max, const double* img2lidar, const double* coords_w, const double* coords_h,
-                                   const double* coords_d, float* out, int V, int h, int w, int depth_num, const double* position_range, void* stream) {
+// ld: row pitch of `out` in floats (>= 3 * depth_num); the columns 3 * depth_num .. ld - 1 of every written row are set to zero
+extern "C" int mv2d_pe_frustum_f32_ld(const int* s2pos, const int* S_dev, int S_max, const double* img2lidar, const double* coords_w, const double* coords_h,
+                                      const double* coords_d, float* out, int V, int h, int w, int depth_num, const double* position_range, int ld, void* stream) {
     MV2D_CHECK_ARG(s2pos && S_dev && img2lidar && coords_w && coords_h && coords_d && out && position_range, "mv2d_pe_frustum_f32: null pointer");
     MV2D_CHECK_ARG(depth_num > 0 && depth_num <= 256 && V > 0 && h > 0 && w > 0, "mv2d_pe_frustum_f32: bad sizes");
+    MV2D_CHECK_ARG(ld >= 3 * depth_num && ld <= 1024, "mv2d_pe_frustum_f32_ld: ld must be in [3 * depth_num, 1024]");
     if (S_max == 0) return MV2D_OK;
     // the logarithm table travels as a kernel argument (round 6; it was a __device__ symbol filled once per PROCESS: a second GPU of the process read
     // zeros, and a first call under graph capture broke the capture -- ADVICE r5); built once, thread-safe
@@ -1576,32 +1497,48 @@ extern "C" int mv2d_pe_frustum_f32(const int* s2pos, const int* S_dev, int S_max
         return t;
     }();
     const int blocks = cdiv(S_max, 4) < 4096 ? cdiv(S_max, 4) : 4096;
-    hipLaunchKernelGGL(pe_frustum_f32_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, s2pos, S_dev, img2lidar, coords_w, coords_h, coords_d, out, h, w,
-                       depth_num, position_range[0], position_range[1], position_range[2], 1.0 / (position_range[3] - position_range[0]),
-                       1.0 / (position_range[4] - position_range[1]), 1.0 / (position_range[5] - position_range[2]), lt);
+    if (ld == 3 * depth_num)
+        hipLaunchKernelGGL(pe_frustum_f32_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, s2pos, S_dev, img2lidar, coords_w, coords_h, coords_d, out, h, w,
+                           depth_num, position_range[0], position_range[1], position_range[2], 1.0 / (position_range[3] - position_range[0]),
+                           1.0 / (position_range[4] - position_range[1]), 1.0 / (position_range[5] - position_range[2]), lt);
+    else
+        hipLaunchKernelGGL(pe_frustum_f32_ld_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, s2pos, S_dev, img2lidar, coords_w, coords_h, coords_d, out, h, w,
+                           depth_num, position_range[0], position_range[1], position_range[2], 1.0 / (position_range[3] - position_range[0]),
+                           1.0 / (position_range[4] - position_range[1]), 1.0 / (position_range[5] - position_range[2]), lt, ld);
     MV2D_LAUNCH_CHECK();
     return MV2D_OK;
+}
+
+extern "C" int mv2d_pe_frustum_f32(const int* s2pos, const int* S_dev, int S_max, const double* img2lidar, const double* coords_w, const double* coords_h,
+                                   const double* coords_d, float* out, int V, int h, int w, int depth_num, const double* position_range, void* stream) {
+    return mv2d_pe_frustum_f32_ld(s2pos, S_dev, S_max, img2lidar, coords_w, coords_h, coords_d, out, V, h, w, depth_num, position_range, 3 * depth_num, stream);
 }
 
 template <class MT>
 static void pe_inputs_launch(const int* s2pos, const int* S_dev, int S_max, const void* featcl, const double* img2lidar, const double* coords_w,
                              const double* coords_h, const double* coords_d, const float* embeds, const float* dim_t, void* A_frustum, void* A_sine,
                              void* Xf_k16, float* Xf_f32, float* A_frustum_f32, float* A_sine_f32, int V, int h, int w, int depth_num,
-                             const double* position_range, void* stream) {
-#define MV2D_PEI(EX) hipLaunchKernelGGL((pe_inputs_kernel<EX, MT>), dim3(cdiv(S_max, 4)), dim3(256), 0, (hipStream_t)stream, s2pos, S_dev, (const MT*)featcl, img2lidar, coords_w, \
-                       coords_h, coords_d, embeds, dim_t, (unsigned short*)A_frustum, (unsigned short*)A_sine,                                      \
-                       (unsigned short*)Xf_k16, Xf_f32, A_frustum_f32, A_sine_f32, h, w, V * h * w, depth_num, position_range[0], position_range[1], \
-                       position_range[2], position_range[3] - position_range[0], position_range[4] - position_range[1],                               \
-                       position_range[5] - position_range[2])
+                             const double* position_range, int ld, void* stream) {
+#define MV2D_PEI_A s2pos, S_dev, (const MT*)featcl, img2lidar, coords_w, coords_h, coords_d, embeds, dim_t, (unsigned short*)A_frustum, (unsigned short*)A_sine,   \
+                   (unsigned short*)Xf_k16, Xf_f32, A_frustum_f32, A_sine_f32, h, w, V * h * w, depth_num, position_range[0], position_range[1],                \
+                   position_range[2], position_range[3] - position_range[0], position_range[4] - position_range[1], position_range[5] - position_range[2]
+#define MV2D_PEI(EX)                                                                                                                              \
+    do {                                                                                                                                          \
+        if (ld == 3 * depth_num) hipLaunchKernelGGL((pe_inputs_kernel<EX, MT>), dim3(cdiv(S_max, 4)), dim3(256), 0, (hipStream_t)stream, MV2D_PEI_A); \
+        else hipLaunchKernelGGL((pe_inputs_ld_kernel<EX, MT>), dim3(cdiv(S_max, 4)), dim3(256), 0, (hipStream_t)stream, MV2D_PEI_A, ld);          \
+    } while (0)
     if (A_frustum_f32) MV2D_PEI(true); else MV2D_PEI(false);
 #undef MV2D_PEI
+#undef MV2D_PEI_A
 }
 
 // map_fmt: element format of featcl (common.h: 0 = fp32, 1 = fp16, 2 = bf16); Xf_f32, when given, holds the widened rows
-extern "C" int mv2d_pe_inputs_fmt(const int* s2pos, const int* S_dev, int S_max, const void* featcl, const double* img2lidar,
-                                  const double* coords_w, const double* coords_h, const double* coords_d, const float* embeds,
-                                  const float* dim_t, void* A_frustum, void* A_sine, void* Xf_k16, float* Xf_f32, float* A_frustum_f32,
-                                  float* A_sine_f32, int V, int h, int w, int depth_num, const double* position_range, int map_fmt, void* stream) {
+// ld: row pitch of A_frustum and of A_frustum_f32 in elements (a multiple of 8 in [3 * depth_num, 768]); their columns 3 * depth_num .. ld - 1 are set to zero
+extern "C" int mv2d_pe_inputs_ld(const int* s2pos, const int* S_dev, int S_max, const void* featcl, const double* img2lidar,
+                                 const double* coords_w, const double* coords_h, const double* coords_d, const float* embeds,
+                                 const float* dim_t, void* A_frustum, void* A_sine, void* Xf_k16, float* Xf_f32, float* A_frustum_f32,
+                                 float* A_sine_f32, int V, int h, int w, int depth_num, const double* position_range, int map_fmt, int ld, void* stream) {
+    MV2D_CHECK_ARG(depth_num > 0 && ld >= 3 * depth_num && ld <= 768 && (ld % 8) == 0, "mv2d_pe_inputs_ld: ld must be a multiple of 8 in [3 * depth_num, 768]");
     MV2D_CHECK_ARG(s2pos && S_dev && featcl && img2lidar && coords_w && coords_h && coords_d && embeds && dim_t && A_frustum &&
                        Xf_k16 && position_range, "mv2d_pe_inputs: null pointer");
     MV2D_CHECK_ARG(A_sine || !A_sine_f32, "mv2d_pe_inputs: the exact rows need A_sine");
@@ -1610,9 +1547,17 @@ extern "C" int mv2d_pe_inputs_fmt(const int* s2pos, const int* S_dev, int S_max,
     if (S_max == 0) return MV2D_OK;
     MV2D_CHECK_ARG(A_frustum_f32 || !A_sine_f32, "mv2d_pe_inputs: fp32 sine rows only together with the fp32 frustum rows");
     MV2D_MAP_DISPATCH(map_fmt, pe_inputs_launch<MT>(s2pos, S_dev, S_max, featcl, img2lidar, coords_w, coords_h, coords_d, embeds, dim_t, A_frustum, A_sine,
-                                                    Xf_k16, Xf_f32, A_frustum_f32, A_sine_f32, V, h, w, depth_num, position_range, stream));
+                                                    Xf_k16, Xf_f32, A_frustum_f32, A_sine_f32, V, h, w, depth_num, position_range, ld, stream));
     MV2D_LAUNCH_CHECK();
     return MV2D_OK;
+}
+
+extern "C" int mv2d_pe_inputs_fmt(const int* s2pos, const int* S_dev, int S_max, const void* featcl, const double* img2lidar,
+                                  const double* coords_w, const double* coords_h, const double* coords_d, const float* embeds,
+                                  const float* dim_t, void* A_frustum, void* A_sine, void* Xf_k16, float* Xf_f32, float* A_frustum_f32,
+                                  float* A_sine_f32, int V, int h, int w, int depth_num, const double* position_range, int map_fmt, void* stream) {
+    return mv2d_pe_inputs_ld(s2pos, S_dev, S_max, featcl, img2lidar, coords_w, coords_h, coords_d, embeds, dim_t, A_frustum, A_sine, Xf_k16, Xf_f32,
+                             A_frustum_f32, A_sine_f32, V, h, w, depth_num, position_range, map_fmt, 3 * depth_num, stream);
 }
 
 extern "C" int mv2d_pe_inputs(const int* s2pos, const int* S_dev, int S_max, const float* featcl, const double* img2lidar,

@@ -49,7 +49,7 @@ class HeadEngine:
                  max_num=300, pc_range=(-51.2, -51.2, -5.0, 51.2, 51.2, 3.0),
                  post_range=(-61.2, -61.2, -10.0, 61.2, 61.2, 10.0), depth_num=64, stride=16, col_cap_per_query=2048,
                  iou_thr=0.0, ratio=0.0, masked_row='nan', exact=None, num_classes=10, roi_size=7, use_reg_layer=False,
-                 group_reg_dims=(2, 2, 1, 1, 2, 2)):
+                 group_reg_dims=(2, 2, 1, 1, 2, 2), depth_start=1, position_range=None):
         assert kind in ('S', 'T')
         self.kind = kind
         self.dev = torch.device(device)
@@ -71,7 +71,14 @@ class HeadEngine:
         # key layout has to agree (load_state), and it is part of the graph key.
         self.use_reg_layer = bool(use_reg_layer)
         self.group_reg_dims = ops.check_group_reg_dims(group_reg_dims) if self.use_reg_layer else tuple(group_reg_dims)
-        self.depth_num = depth_num
+        # the PE's depth_num / depth_start / position_range (MU/pe.py:52-63).  Every consumer of the frustum rows takes them with Kp = pe_kp(depth_num)
+        # columns (3 * depth_num zero-padded to a multiple of 32) and position_encoder.0.weight zero-padded to [1024, Kp]: one instance of the fused PE
+        # kernel per Kp / 32 (csrc/pe_x3_kernel.h).  position_range=None: the coder's post_range, as in the shipped configs; the decode's centre filter
+        # always uses post_range.
+        self.depth_num = ops.check_pe_depth(depth_num, 'HeadEngine')
+        self.pe_kp = ops.pe_kp(self.depth_num)
+        self.depth_start, pe_range = ops.check_pe_range(depth_start, post_range if position_range is None else position_range, 'HeadEngine')
+        self.pe_range_h64 = torch.tensor(pe_range, dtype=torch.float64)
         self.stride = stride
         self.iou_thr, self.ratio = iou_thr, ratio
         self.col_cap_per_query = col_cap_per_query
@@ -181,6 +188,9 @@ class HeadEngine:
         nc = int(tuple(sd['bbox_head.cls_branches.0.6.weight'].shape)[0])
         if nc != self.num_classes:
             raise ValueError(f'HeadEngine: the state dict has {nc} classes (cls_branches.*.6.weight), num_classes={self.num_classes}')
+        k1 = int(tuple(sd['position_encoding.position_encoder.0.weight'].shape)[1])
+        if k1 != 3 * self.depth_num:
+            raise ValueError(f'HeadEngine: the state dict has {k1} frustum channels (position_encoder.0.weight), 3 * depth_num = {3 * self.depth_num}')
         self._weights_version = getattr(self, '_weights_version', 0) + 1
         g = lambda k: _t(sd[k], d, F32)
         k16 = ops.pack_key16                                                             # fp32 [N,K] -> key16, fragment-major (key-side kernels)
@@ -242,7 +252,8 @@ class HeadEngine:
         # LDS-tiled bf16x3 linears (mv2d_linear_x3)
         w['qg_fc_wx'], w['qg_e0_wx'], w['qg_e2_wx'] = ops.pack_x3(g(q + 'shared_fcs.0.weight')), ops.pack_x3(e0p), ops.pack_x3(g(q + 'extra_enc.2.weight'))
         pe = 'position_encoding.'
-        c1 = lambda k: g(pe + k).flatten(1).contiguous()
+        # (position_encoder.0.weight with its K zero-padded to Kp: the padded frustum rows meet zero columns)
+        c1 = lambda k: ops.pad_pe_w1a(g(pe + k)) if k == 'position_encoder.0.weight' else g(pe + k).flatten(1).contiguous()
         pe_names = (('w1a', 'position_encoder.0'), ('w1b', 'position_encoder.2'), ('w2a', 'adapt_pos3d.0'), ('w2b', 'adapt_pos3d.2'),
                     ('wr', 'fpe.conv_reduce'), ('we', 'fpe.conv_expand'))
         for n_, k_ in pe_names:
@@ -419,13 +430,13 @@ class HeadEngine:
                              umask=alloc(ucap, torch.uint8, zero=True), ucap=ucap, ctl=ws['grp_ctl'])
         # key16 rows of the PE block's inputs: frustum [.,192], sine [.,384] (training route only: the inference kernel reads the folded
         # table), feature rows [.,256] (the SE gate's input; the value rows of the T path)
-        ws['A1'] = e((P, 3 * self.depth_num), K16); ws['A2'] = e((P, 384), K16)
+        ws['A1'] = e((P, self.pe_kp), K16); ws['A2'] = e((P, 384), K16)
         ws['Xf_b'] = e((P, C), K16)
         if self.exact:
             # index-exact route: the unrounded fp32 frustum rows of the PE block (the feature rows are read from the map), the lo halves of the
             # key / value rows and RoI cells -- all pre-allocated (no per-frame allocation, no host synchronisation: the route is
             # graph-replayable like the default one)
-            ws['xa1'] = e((P, 3 * self.depth_num)); ws['xa2'] = e((P, 384))
+            ws['xa1'] = e((P, self.pe_kp)); ws['xa2'] = e((P, 384))
             lo8 = self._lo8()
             LO = torch.uint8 if lo8 else K16
             if self.kind == 'T':
@@ -461,8 +472,8 @@ class HeadEngine:
         skey = (calib.meta_shapes(img_metas), h, w)
         sht = self._shape_cache.get(skey)
         if sht is None:
-            sht = calib.shape_tables(skey[0], h, w, stride=self.stride, depth_num=self.depth_num,
-                                     position_range=tuple(self.post_range_h64.tolist()))
+            sht = calib.shape_tables(skey[0], h, w, stride=self.stride, depth_num=self.depth_num, depth_start=self.depth_start,
+                                     position_range=tuple(self.pe_range_h64.tolist()))
             if len(self._shape_cache) >= 16:
                 self._shape_cache.pop(next(iter(self._shape_cache)))
             self._shape_cache[skey] = sht
@@ -550,10 +561,10 @@ class HeadEngine:
             s2 = torch.arange(Pt, dtype=torch.int32, device=self.dev)
             k16e = lambda n_: torch.empty((Pt, n_), device=self.dev, dtype=self.K16)
             a2f = torch.empty((Pt, 384), device=self.dev, dtype=F32)
-            a1f = torch.empty((Pt, 3 * self.depth_num), device=self.dev, dtype=F32)
+            a1f = torch.empty((Pt, self.pe_kp), device=self.dev, dtype=F32)
             o.pe_inputs(s2, torch.tensor([Pt], dtype=torch.int32, device=self.dev), Pt, ws['featcl'], T['img2lidar'], T['coords_w'], T['coords_h'],
-                        T['coords_d'], T['embeds'], self.const['dim_t'], k16e(3 * self.depth_num), k16e(384), k16e(C), None, V, h, w, self.depth_num,
-                        self.post_range_h64, A_frustum_f32=a1f, A_sine_f32=a2f)
+                        T['coords_d'], T['embeds'], self.const['dim_t'], k16e(self.pe_kp), k16e(384), k16e(C), None, V, h, w, self.depth_num,
+                        self.pe_range_h64, A_frustum_f32=a1f, A_sine_f32=a2f, ld=self._pe_ld())
             w2a, w2b = self._pe_w32['w2a'], self._pe_w32['w2b']
             h2 = o.linear_x3(a2f, W_['pe_w2a_x3'], W_['pe_b2a'], N=w2a.shape[0], K=w2a.shape[1], act=1)
             tab = o.linear_x3(h2, W_['pe_w2b_x3'], W_['pe_b2b'], N=w2b.shape[0], K=w2b.shape[1])
@@ -694,7 +705,7 @@ class HeadEngine:
             tk('pe_inputs')
             o.pe_inputs(ws['s2pos'], md, P, featcl, T['img2lidar'], T['coords_w'], T['coords_h'], T['coords_d'], T['embeds'],
                         self.const['dim_t'], ws['A1'], ws['A2'] if self.keep_sine_rows else None, ws['Xf_b'], None,
-                        V, h, w, self.depth_num, self.post_range_h64)
+                        V, h, w, self.depth_num, self.pe_range_h64, ld=self._pe_ld())
             tk('pe_fused')
             # only what the path reads is written: S: pe (RoIAlign reads it; its keys are RoI-aligned rows), T: Xk (nothing reads pe);
             # a keep_stages run writes both
@@ -762,33 +773,38 @@ class HeadEngine:
             # (training route: it also reads the key16 rows and the sine rows)
             o.pe_inputs(ws['s2pos'], md, P, featcl, T['img2lidar'], T['coords_w'], T['coords_h'], T['coords_d'], T['embeds'],
                         self.const['dim_t'], ws['A1'], ws['A2'], ws['Xf_b'], None, V, h, w, self.depth_num,
-                        self.post_range_h64, A_frustum_f32=ws['xa1'], A_sine_f32=ws['xa2'])
+                        self.pe_range_h64, A_frustum_f32=ws['xa1'], A_sine_f32=ws['xa2'], ld=self._pe_ld())
         else:
             # the unrounded frustum rows alone (round 5: 156 -> ~50 us per 141 k positions; the feature rows are read from the map by the PE kernel)
             o.pe_frustum_f32(ws['s2pos'], md, P, T['img2lidar'], T['coords_w'], T['coords_h'], T['coords_d'], ws['xa1'], V, h, w, self.depth_num,
-                             self.post_range_h64)
+                             self.pe_range_h64, ld=self._pe_ld())
         sh = ws['shared']
         rows = self.kind == 'T'
         dbg = getattr(self, '_stage_outputs', False)
         at_pos = self._pe_at_pos(ws)
         (o.pe_fused_x3b if self.pe_rows_in_waves else o.pe_fused_x3)(
             ws['xa1'], featcl, md, W_['pe_x3'], sh['sine_tab'], sh['sine_period'], pe=(ws['pe_pos'] if at_pos else ws['pe']) if (not rows or dbg) else None,
-            Xk=(ws['Xk'], ws['xk_lo']) if rows else None, Xv=(ws['Xf_b'], ws['xv_lo']) if rows else None, M=P, row_index=ws['s2pos'], pe_at_index=at_pos, lo8_flag=ws['lo8_flag'] if (rows and self._lo8()) else None)
+            Xk=(ws['Xk'], ws['xk_lo']) if rows else None, Xv=(ws['Xf_b'], ws['xv_lo']) if rows else None, M=P, row_index=ws['s2pos'], pe_at_index=at_pos, lo8_flag=ws['lo8_flag'] if (rows and self._lo8()) else None,
+            **({} if self.depth_num == 64 else dict(Kp=self.pe_kp)))            # (64 bins: the entries without a size argument, as before)
+
+    def _pe_ld(self):
+        """Row pitch argument of the frustum-row producers: None (the entries without a pitch, rows of 3 * depth_num columns) unless the rows are padded."""
+        return None if self.pe_kp == 3 * self.depth_num else self.pe_kp
 
     def pe_input_rows(self, ws, positions, V, h, w, f32=False):
-        """PE input rows (frustum [n,192], sine [n,384]; key16, or unrounded fp32 with f32=True) at the given map positions (int32, device)
+        """PE input rows (frustum [n,Kp] = 3 * depth_num columns + zero pad, 192 at 64 bins; sine [n,384]; key16, or unrounded fp32 with f32=True) at the given map positions (int32, device)
         with the calibration tables of the workspace's current frame: the training route needs them for a key position no RoI lists
         (RH/mv2d_t_head.py:80-82)."""
         n = int(positions.numel())
         T, d = ws['tab'], self.dev
-        a1 = torch.empty((n, 3 * self.depth_num), device=d, dtype=self.K16)
+        a1 = torch.empty((n, self.pe_kp), device=d, dtype=self.K16)
         a2 = torch.empty((n, 384), device=d, dtype=self.K16)
         xb = torch.empty((n, C), device=d, dtype=self.K16)
-        a1f = torch.empty((n, 3 * self.depth_num), device=d, dtype=F32) if f32 else None
+        a1f = torch.empty((n, self.pe_kp), device=d, dtype=F32) if f32 else None
         a2f = torch.empty((n, 384), device=d, dtype=F32) if f32 else None
         ops.pe_inputs(positions.contiguous(), torch.tensor([n], dtype=torch.int32, device=d), n, ws['featcl'], T['img2lidar'], T['coords_w'],
-                      T['coords_h'], T['coords_d'], T['embeds'], self.const['dim_t'], a1, a2, xb, None, V, h, w, self.depth_num, self.post_range_h64,
-                      A_frustum_f32=a1f, A_sine_f32=a2f)
+                      T['coords_h'], T['coords_d'], T['embeds'], self.const['dim_t'], a1, a2, xb, None, V, h, w, self.depth_num, self.pe_range_h64,
+                      A_frustum_f32=a1f, A_sine_f32=a2f, ld=self._pe_ld())
         return (a1f, a2f) if f32 else (a1, a2)
 
     def _enqueue_qg(self, ws, R):
@@ -968,6 +984,10 @@ class HeadEngine:
         ops.map_format(map_dtype)                         # ValueError for anything but fp32 / fp16 / bf16
         if any(f.dtype != map_dtype for f in fl):
             raise ValueError(f'mv2d engine: the feature maps of a batch must share one dtype, got {sorted({str(f.dtype) for f in fl})}')
+        if self.depth_num != 64 and not (self.exact and 'pe' not in self.exact_skip):
+            raise ValueError(f'mv2d engine: the key16 mode\'s PE kernel (csrc/pe_tab96.hip) is built for depth_num = 64 only; run the index-exact route (exact=True, the default) with depth_num = {self.depth_num}')
+        if self.depth_num != 64 and self.pe_rows_in_waves:
+            raise ValueError(f'mv2d engine: pe_rows_in_waves (csrc/pe_x3b.hip) is built for depth_num = 64 only; unset it for depth_num = {self.depth_num}')
         if map_dtype != F32 and self.pe_rows_in_waves and self.exact and 'pe' not in self.exact_skip:
             raise ValueError('mv2d engine: pe_rows_in_waves (csrc/pe_x3b.hip) reads fp32 feature maps only; unset it for a torch.float16 / torch.bfloat16 map')
         if stacked or B == 1:

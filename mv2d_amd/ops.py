@@ -498,9 +498,59 @@ def pe_fused_tab(A1, Xfb, Xf32, m_dev, wp, sine_tab, tab_period, pe, Xk, M=None,
     return pe, Xk
 
 
+PE_DEPTHS = tuple(range(8, 81, 8))      # depth_num the fused PE kernel (csrc/pe_x3.hip) has instances for
+
+
+def pe_kp(depth_num):
+    """Columns (= row pitch) of the frustum rows and K of position_encoder.0 as every consumer takes them: 3 * depth_num zero-padded to a multiple of 32."""
+    return 32 * ((3 * int(depth_num) + 31) // 32)
+
+
+def check_pe_depth(depth_num, who):
+    if isinstance(depth_num, bool) or int(depth_num) != depth_num or int(depth_num) not in PE_DEPTHS:
+        raise ValueError(f'{who}: depth_num must be a multiple of 8 in [8, 80], got {depth_num!r}')
+    return int(depth_num)
+
+
+def check_pe_range(depth_start, position_range, who):
+    """(depth_start, position_range) as floats, or ValueError: position_range = six floats with hi > lo per axis, 0 < depth_start < position_range[3]."""
+    try:
+        pr = tuple(float(v) for v in position_range)
+    except TypeError:
+        pr = ()
+    if len(pr) != 6 or not all(math.isfinite(v) for v in pr) or not all(pr[i + 3] > pr[i] for i in range(3)):
+        raise ValueError(f'{who}: position_range must be six finite floats (x0, y0, z0, x1, y1, z1) with x1 > x0, y1 > y0, z1 > z0, got {position_range!r}')
+    try:
+        ds = float(depth_start)
+    except (TypeError, ValueError):
+        ds = float('nan')
+    if not 0.0 < ds < pr[3]:
+        raise ValueError(f'{who}: depth_start must be a float with 0 < depth_start < position_range[3] = {pr[3]}, got {depth_start!r}')
+    return ds, pr
+
+
+def pad_pe_w1a(W, depth_num=None):
+    """position_encoder.0.weight [1024, 3 D] (or [1024, 3 D, 1, 1]) -> [1024, Kp] with zero pad columns (what pack_x3 / pack_key16 / the training
+    route's K-concatenated copies are built from); the tensor itself when 3 D is a multiple of 32.  With depth_num, W may also arrive with Kp
+    columns already: whatever its columns 3 D .. Kp - 1 hold is DROPPED and replaced by zeros."""
+    W = W.flatten(1)
+    K = W.shape[1]
+    if depth_num is not None:
+        if K not in (3 * depth_num, pe_kp(depth_num)):
+            raise ValueError(f'position_encoder.0.weight has {K} input channels, 3 * depth_num = {3 * depth_num}')
+        W, K = W[:, :3 * depth_num], 3 * depth_num
+    Kp = 32 * ((K + 31) // 32)
+    if Kp == K:
+        return W.contiguous()
+    Wp = W.new_zeros((W.shape[0], Kp))
+    Wp[:, :K] = W
+    return Wp
+
+
 def pe_fused_x3(A1, Xmap, m_dev, wx, sine_tab, tab_period, pe=None, Xk=None, Xv=None, M=None, row_index=None, pe_at_index=False, lo8_flag=None,
-                map_fmt=None):
-    """The PE block in split precision on unrounded inputs (index-exact route, csrc/pe_x3.hip).  A1 [M,192] fp32; Xmap feature rows, fp32, fp16 or
+                map_fmt=None, Kp=None):
+    """The PE block in split precision on unrounded inputs (index-exact route, csrc/pe_x3.hip).  A1 [M,Kp] fp32 (Kp = pe_kp(depth_num): frustum rows with zero
+    pad columns, wx['w1a'] packed from pad_pe_w1a(weight); Kp=None: the 192 columns of 64 bins through the entries that have no size argument); Xmap feature rows, fp32, fp16 or
     bf16 (widened in the kernel; indexed by row_index when given); wx: dict 'w1a','w1b','wr','we' = pack_x3(weight) pairs + fp32 biases 'b1a','b1b','br','be'; pe [M,256]
     fp32 and / or Xk = (hi, lo), Xv = (hi, lo) key16 [M,256] pairs (key rows pe + feat, value rows feat).  pe_at_index: pe row m goes to row
     row_index[m] of `pe` (a position-indexed map for roi_align without map1_index)."""
@@ -515,6 +565,15 @@ def pe_fused_x3(A1, Xmap, m_dev, wx, sine_tab, tab_period, pe=None, Xk=None, Xv=
         _req(wx[k][0], q16_dtype(), k); _req(wx[k][1], q16_dtype(), k)
     M = A1.shape[0] if M is None else M
     xk, xv = Xk or (None, None), Xv or (None, None)
+    if Kp is not None:
+        if A1.dim() != 2 or A1.shape[1] != Kp or wx['w1a'][0].numel() != 1024 * Kp:
+            raise _lib.Mv2dHipError(f'pe_fused_x3: A1 {tuple(A1.shape)} / w1a ({wx["w1a"][0].numel()} elements) do not have Kp = {Kp} columns')
+        check(_lib.load().mv2d_pe_fused_x3_k(_p(A1), _p(Xmap), _p(row_index), _p(m_dev), M, _p(wx['w1a'][0]), _p(wx['w1a'][1]), _p(wx['b1a']),
+                                             _p(wx['w1b'][0]), _p(wx['w1b'][1]), _p(wx['b1b']), _p(wx['wr'][0]), _p(wx['wr'][1]), _p(wx['br']),
+                                             _p(wx['we'][0]), _p(wx['we'][1]), _p(wx['be']), _p(sine_tab), int(tab_period), _p(pe), _p(xk[0]), _p(xk[1]),
+                                             _p(xv[0]), _p(xv[1]), lo_fmt, 1 if (pe_at_index and row_index is not None) else 0, _p(lo8_flag), fmt, int(Kp),
+                                             _stream()), 'mv2d_pe_fused_x3_k')
+        return pe
     if fmt:
         check(_lib.load().mv2d_pe_fused_x3_fmt(_p(A1), _p(Xmap), _p(row_index), _p(m_dev), M, _p(wx['w1a'][0]), _p(wx['w1a'][1]), _p(wx['b1a']),
                                                _p(wx['w1b'][0]), _p(wx['w1b'][1]), _p(wx['b1b']), _p(wx['wr'][0]), _p(wx['wr'][1]), _p(wx['br']),
@@ -1031,12 +1090,21 @@ def csr_from_corr(match, row_ptr, col_idx, nnz_out, R, V, topk, roi_size=7):
 
 
 def pe_inputs(s2pos, S_dev, S_max, featcl, img2lidar, coords_w, coords_h, coords_d, embeds, dim_t, A_frustum, A_sine, Xf_k16,
-              Xf_f32, V, h, w, depth_num, position_range_host, A_frustum_f32=None, A_sine_f32=None, map_fmt=None):
+              Xf_f32, V, h, w, depth_num, position_range_host, A_frustum_f32=None, A_sine_f32=None, map_fmt=None, ld=None):
     """A_frustum [S,3D], A_sine [S,384] (may be None), Xf_k16 [S,256]: key16 rows; *_f32: the same rows unrounded (optional).  featcl: the
-    position-major feature map, fp32, fp16 or bf16 (widened in the kernel)."""
+    position-major feature map, fp32, fp16 or bf16 (widened in the kernel).  ld: row pitch of A_frustum / A_frustum_f32 ([S,ld], a multiple of 8 >= 3D;
+    the kernel zeroes the pad columns); None = 3D."""
     _req16(A_frustum, 'A_frustum'); _req16(A_sine, 'A_sine'); _req16(Xf_k16, 'Xf_k16')
     _req(A_frustum_f32, torch.float32, 'A_frustum_f32'); _req(A_sine_f32, torch.float32, 'A_sine_f32'); _req(Xf_f32, torch.float32, 'Xf_f32')
     fmt = _req_map(featcl, 'featcl', map_fmt)
+    for t in (A_frustum, A_frustum_f32):
+        if t is not None and (t.dim() != 2 or t.shape[1] != (3 * depth_num if ld is None else ld)):
+            raise _lib.Mv2dHipError(f'pe_inputs: frustum rows {tuple(t.shape)} do not have {3 * depth_num if ld is None else ld} columns')
+    if ld is not None:
+        check(_lib.load().mv2d_pe_inputs_ld(_p(s2pos), _p(S_dev), S_max, _p(featcl), _p(img2lidar), _p(coords_w), _p(coords_h), _p(coords_d),
+                                            _p(embeds), _p(dim_t), _p(A_frustum), _p(A_sine), _p(Xf_k16), _p(Xf_f32), _p(A_frustum_f32),
+                                            _p(A_sine_f32), V, h, w, depth_num, position_range_host.data_ptr(), fmt, int(ld), _stream()), 'mv2d_pe_inputs_ld')
+        return
     if fmt:
         check(_lib.load().mv2d_pe_inputs_fmt(_p(s2pos), _p(S_dev), S_max, _p(featcl), _p(img2lidar), _p(coords_w), _p(coords_h), _p(coords_d),
                                              _p(embeds), _p(dim_t), _p(A_frustum), _p(A_sine), _p(Xf_k16), _p(Xf_f32), _p(A_frustum_f32),
@@ -1047,11 +1115,18 @@ def pe_inputs(s2pos, S_dev, S_max, featcl, img2lidar, coords_w, coords_h, coords
                                      _p(A_sine_f32), V, h, w, depth_num, position_range_host.data_ptr(), _stream()), 'mv2d_pe_inputs')
 
 
-def pe_frustum_f32(s2pos, S_dev, S_max, img2lidar, coords_w, coords_h, coords_d, out, V, h, w, depth_num, position_range_host):
-    """out [S, 3 D] fp32: the unrounded frustum rows of the PE block at the listed positions (index-exact route; fp64 arithmetic, fast form)."""
+def pe_frustum_f32(s2pos, S_dev, S_max, img2lidar, coords_w, coords_h, coords_d, out, V, h, w, depth_num, position_range_host, ld=None):
+    """out [S, 3 D] fp32: the unrounded frustum rows of the PE block at the listed positions (index-exact route; fp64 arithmetic, fast form).
+    ld: row pitch (out [S, ld], ld >= 3 D; the kernel zeroes the pad columns); None = 3 D."""
     _req(s2pos, torch.int32, 's2pos'); _req(S_dev, torch.int32, 'S_dev'); _req(out, torch.float32, 'out')
     for t, n_ in ((img2lidar, 'img2lidar'), (coords_w, 'coords_w'), (coords_h, 'coords_h'), (coords_d, 'coords_d')):
         _req(t, torch.float64, n_)
+    if out.dim() != 2 or out.shape[1] != (3 * depth_num if ld is None else ld):
+        raise _lib.Mv2dHipError(f'pe_frustum_f32: out {tuple(out.shape)} does not have {3 * depth_num if ld is None else ld} columns')
+    if ld is not None:
+        check(_lib.load().mv2d_pe_frustum_f32_ld(_p(s2pos), _p(S_dev), S_max, _p(img2lidar), _p(coords_w), _p(coords_h), _p(coords_d), _p(out), V, h, w,
+                                                 depth_num, position_range_host.data_ptr(), int(ld), _stream()), 'mv2d_pe_frustum_f32_ld')
+        return out
     check(_lib.load().mv2d_pe_frustum_f32(_p(s2pos), _p(S_dev), S_max, _p(img2lidar), _p(coords_w), _p(coords_h), _p(coords_d), _p(out), V, h, w,
                                           depth_num, position_range_host.data_ptr(), _stream()), 'mv2d_pe_frustum_f32')
     return out

@@ -268,7 +268,8 @@ class MV2DHead(nn.Module):
             self._engine = HeadEngine(sd, self.KIND, device, num_views=self._engine_num_views(img_metas), topk=bc.topk,
                                       expand_stride=bc.expand_stride, num_layers=self.bbox_head.num_pred, max_num=coder.max_num,
                                       pc_range=tuple(self.pc_range), post_range=tuple(coder.post_center_range),
-                                      depth_num=self.position_encoding.depth_num, stride=self.strides[self.feat_lvl],
+                                      depth_num=self.position_encoding.depth_num, depth_start=self.position_encoding.depth_start,
+                                      position_range=tuple(self.position_encoding.position_range), stride=self.strides[self.feat_lvl],
                                       iou_thr=bc.iou_thr, ratio=bc.ratio, num_classes=self.bbox_head.num_classes, roi_size=self.roi_cells,
                                       use_reg_layer=getattr(self.bbox_head, 'use_reg_layer', False),
                                       group_reg_dims=getattr(self.bbox_head, 'group_reg_dims', (2, 2, 1, 1, 2, 2)),

@@ -162,6 +162,9 @@ class PE(nn.Module):
                  with_fpe=False, adapt_pos3d=True, no_sin_enc=False):
         super().__init__()
         assert LID and with_fpe and adapt_pos3d and not no_sin_enc and embed_dims == C, 'kernel path implements the shipped config'
+        # the three keys the fused engine takes at any supported value (depth_num: one instance of the fused PE kernel per 32 frustum columns)
+        depth_num = ops.check_pe_depth(depth_num, 'PE')
+        ops.check_pe_range(depth_start, position_range, 'PE')
         self.strides, self.position_range, self.depth_num, self.depth_start = strides, position_range, depth_num, depth_start
         self.embed_dims, self.with_fpe = embed_dims, with_fpe
         self.position_encoder = nn.Sequential(nn.Conv2d(3 * depth_num, 4 * C, 1), nn.ReLU(), nn.Conv2d(4 * C, C, 1))

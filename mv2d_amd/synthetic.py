@@ -220,6 +220,15 @@ def with_reg_layer_state(sd, seed=0, group_reg_dims=(2, 2, 1, 1, 2, 2)):
     return out
 
 
+def with_pe_depth_state(sd, seed=0, depth_num=DEPTH_NUM):
+    """A copy of a make_head_state dict whose position_encoding.position_encoder.0.weight is a Xavier [1024, 3 * depth_num, 1, 1] tensor (the PE's
+    ``depth_num`` key); its own stream of draws, make_head_state is untouched."""
+    g = _rng(seed + 104729)
+    out = OrderedDict(sd.items())
+    out['position_encoding.position_encoder.0.weight'] = _xavier(g, (4 * EMBED, 3 * int(depth_num), 1, 1))
+    return out
+
+
 WORKLOADS = {
     # name: (head kind, views/frame, frames, img_h, img_w, pad_w, boxes/view)
     'micro_t': ('T', 2, 1, 128, 192, None, 6),
