@@ -21,7 +21,7 @@ import os
 import numpy as np
 import torch
 
-from . import calib, ops
+from . import calib, ops, route
 
 BF16 = torch.bfloat16
 F32 = torch.float32
@@ -93,92 +93,14 @@ class HeadEngine:
         self._ws = {}
         self._ws_base = {}
         self._shape_cache = {}
-        self.prof = None              # dict name -> [events] when stage timing is on (bench.py)
-        self.fork_qg = True           # T path: query-generator chain on a second stream
-        # ---- route options (round 4: the retired A/B routes left the engine; what remains are ATTRIBUTES a caller may set before the first
-        # run, every one of them part of the hipGraph key -- DESIGN.md "switches" table).  The only environment variable the engine reads is
-        # MV2D_EXACT.
+        # ---- route options: plain attributes, settable on a live engine (the next call follows them: its workspace and its graph are keyed by
+        # the route they resolve to).  Names, defaults and what each one does: mv2d_amd/route.py.  The only other environment variable the engine
+        # reads is MV2D_EXACT (route.Route.exact).
+        self.__dict__.update(route.default_options())
         # adapt_pos3d(sine) (MU/pe.py:164-166) depends only on the weights and on the padding geometry of the rig, not on features, boxes
         # or calibration: it is constant-folded into a per-(weights version, geometry) table that the fused PE kernel adds in its epilogue
         self._weights_version = 0     # bumped by every load_state(): invalidates whatever was folded from the weights
-        self.stop_before_decoder = False   # the autograd training route only needs geometry, RoI features, PE inputs and reference points of a run
-        self.keep_sine_rows = False   # the training route reads the per-key sine rows (ws['A2']) although the inference kernel does not
-        self.force_nc = None          # bench only (S path): overwrite the correlation lists so that every query reads n_c RoIs
-        # tests only (eager runs): keep the pre-softmax per-head logits of every layer's cross attention (out['stages']['dbg_logits']
-        # [L,8,col_cap] in CSR order, WITHOUT the per-(query, head) constant q_h . bk_h that cancels in the softmax) and the scaled,
-        # projected queries ('dbg_q' [L,R,256]) they were computed from
-        self.debug_attn = False
-        # The per-head query / context maps of the tile cross attention run inside the neighbouring row kernels (mv2d_attn_out_qmap_x3 /
-        # _zmap_x3: 6 instead of 8 launches per layer, bitwise the same results) for SMALL launches (<= 512 query rows, i.e. one sample per
-        # call: the two saved launches per layer count there) and as separate kernels for batches (a row kernel is bound by streaming its
-        # weights through ONE CU per 32 rows; the fused ones stream twice as much).  None: by the row count; True / False forces it.
-        self.fuse_maps = {'0': False, '1': True}.get(os.environ.get('MV2D_FUSE_MAPS', ''), None)      # (the variable: A/B runs)
-        # OPT-IN: evaluate the cls / reg branches of the last decoder layer only (what decoding reads).  Not the default: out['cls'] / out['reg']
-        # then carry stale rows for the other layers, and the reference's forward does evaluate all six.
-        self.last_stage_heads = False
-        # T path: the blocks of the per-query tile kernel run in the order of the queries' SMALLEST KEY (mv2d_xattn_query_order): neighbouring
-        # blocks of an XCD then read overlapping key sets from its L2 (cfg3_t 54.8 -> 47.6 us per layer; bitwise the same results)
-        # S path (round 4): the queries ranked by the smallest RoI they list (own or matched; computed from the correlation lists inside the
-        # launch that builds the CSR) -- matched RoIs of different views then run side by side; a no-op for queries that read only their own RoI
-        self.q_order = True
-        # waves per query of the tile kernel: the kernel alone takes the same time with 1, 2 or 4 (it is bound by what the memory system
-        # delivers), but a launch with fewer waves leaves more of the chip to the other streams' kernels: cfg2_s 8067 / 8043 / 7869
-        # samples/s for 1 / 2 / 4, cfg3_t (rows of ~200 keys) 5803 / 5868 / 5758
-        self.xattn_waves = int(os.environ.get('MV2D_XATTN_WAVES', '2'))       # (the variable: A/B runs)
-        # S path (rows of similar length): query map -> tile attention -> context map as ONE launch per layer (csrc/xattn_fused.hip, round 5: blocks
-        # of 8 queries, Qt / z stay on chip; bitwise the three kernels with one wave per query).  None: on the S path when no debug output is asked
-        # for; False / True forces it.  In the graph key.
-        self.fuse_xattn = None
-        # Round 6, OPT-IN: key tiles SHARED between the queries of a group (csrc/xattn_group.hip: one block per 8 queries that are neighbours in the
-        # launch order walks the union of their key lists once through an LDS-DMA ring; wave = head, query / context maps in the same launch).  It
-        # reads what it should (1.34-1.68 x the distinct rows instead of 2.99 x at cfg3_t) and is SLOWER than the per-query kernels (242-326 us
-        # against 158 + 33 us per cfg3_t layer): eight heads x every union tile is 2.7 x the (wave, tile) steps of the per-query walk, and the
-        # 32 KB tiles of the hi + lo route leave the 160 KB of LDS no room to run the queries' own walks side by side (LOG.md, round 6).  None /
-        # False: off; True forces it.  In the graph key.
-        self.group_xattn = None
-        # Layer 0 of the decoder starts from target = 0 (RH/bbox_heads/cross_attention_head.py:32): the VALUE rows of its self attention are
-        # in_proj_v(0) + b_v = b_v for every query, the softmax weights of a row sum to 1, so its context is b_v whatever the queries are
-        # (MU/petr_transformer.py:317-370: value = key before the positional embedding = target).  The engine feeds rows of b_v to the
-        # out-projection kernel instead of launching the in-projection and the attention core of layer 0 (the reference's own sum of
-        # probabilities is 1 +- 1e-7; a NaN query position still poisons the frame one layer later, through its cross attention).  In the
-        # graph key; the training forward (denoising mask) keeps the launches.
-        self.fold_sa0 = True
-        # transpose only the map rows inside some RoI's rectangle (see _enqueue); in the graph key
-        self.masked_transpose = True
-        # INDEX-EXACT ROUTE = THE DEFAULT since round 5 (exact=None -> True; exact=False / MV2D_EXACT=0 / test_cfg.index_exact=False selects the
-        # opt-in "key16" mode with ONE fp16 rounding of the key side: ~1.3 x faster, 4-22 of 300 ranked indices differ from the reference's).
-        # Every 16-bit rounding of the key side is replaced by fp32-class arithmetic -- the PE block in one split-precision kernel on unrounded inputs (csrc/pe_x3.hip), the key / value
-        # rows of the tile attention (and, without exact_skip={'conv'}, the query generator's conv) as key16 hi + lo pairs -- so that the INTEGER outputs (labels, bbox_index)
-        # can be compared bit for bit with the reference's (tests/test_gpu_golden.py).  Enqueue-only and hipGraph-replayable like the
-        # default route (bench.py: samples_s_index_exact).
         self.exact = (os.environ.get('MV2D_EXACT', '1') != '0') if exact is None else bool(exact)
-        # Stages of the index-exact route that run with the default route's single key16 rounding -- any of 'attn' (hi rows only in the tile
-        # attention), 'pe' (fused key16 PE kernel), 'conv' (single-precision RoI conv); in the graph key.  Round 4 (tools/ablate_exact.py,
-        # profiles/r04_ablate_exact.txt): with fp16 cells the query generator's conv in SINGLE precision leaves the ranked indices and the
-        # class-logit error of the index-exact route where they are (cfg2_s 2 -> 2, cfg3_t 4 -> 4, cfg5_t 2 -> 0 of 300; cls 5.0e-6 -> 6.2e-6 /
-        # 5.1e-6 -> 4.9e-6 / 5.8e-6 -> 5.7e-6): its 2304-term dot products average the 2^-12 roundings down, and the 3 x MFMA-bound split-
-        # precision kernel (362 vs 123 us per 2400 RoIs) leaves the route.  Attention rows and PE stay hi + lo: dropping either costs ranks.
-        self.exact_skip = frozenset({'conv'})
-        # Round 6: the lo halves of the key / value rows as 8-BIT floats (csrc/common.h "lo8": OCP e4m3 of lo * 2^12, 256-byte rows) -- a (query, key)
-        # pair of the cross attention gathers 1.5 KB instead of 2 KB and the row producers write a quarter less.  The lo part carries 2^-12 of a
-        # product, its e4m3 rounding 2^-16: all 17 reference parity cases keep their ranked indices (class logits 6.2e-7 .. 1.1e-6 of their range
-        # against 6.3e-7 .. 8.0e-7 with key16 lo rows, bound 3e-6; an e5m2 lo half or a missing one moves ranks: profiles/r06_ablate_exact.txt).
-        # The kernels decode the bytes to key16 in registers: results are bitwise those of key16 lo rows holding the decoded values.  False: key16 lo
-        # rows (rounds 3-5).  The shared-tile kernel (group_xattn) reads key16 lo rows only.  In the graph key.
-        self.lo8_rows = True
-        # Round 6, S path: the PE rows are written AT THEIR MAP POSITIONS (a position-indexed fp32 map, zero-filled once) instead of compacted in key-list
-        # order, so that RoIAlign reads its second map without the position -> row table: one dependent load less in front of every bilinear tap of the
-        # PE map (the kernel is a chain of such round trips).  Same values, same arithmetic.  Off for keep_stages runs (they expose the
-        # compact rows) and in key16 mode; MV2D_PE_AT_POS=0 turns it off (A/B runs).  In the graph key.
-        self.pe_at_positions = os.environ.get('MV2D_PE_AT_POS', '1') != '0'
-        # experiments only (tools/ablate_exact.py; needs lo8_rows = False): zero the lo halves of the value / key rows after they were written -- what a route with hi-only value
-        # (or key) rows would compute, at the full route's cost
-        self.ablate_zero_lo = frozenset()
-        # Round 6, OPT-IN: the split-precision PE block on the second shape of its kernel (csrc/pe_x3b.hip: a wave owns 32 rows through both layers of
-        # each MLP, the hidden layer stays in registers, the weights go through an LDS-DMA ring shared by the block's 4 waves; BITWISE the outputs of
-        # csrc/pe_x3.hip).  Measured no faster (1213 vs 1165-1244 us per 250 k rows; 8 waves x 16 rows: 1056 us, bound by 8 x 32 KB of LDS reads per
-        # k-step): LOG.md round 6.  In the graph key.
-        self.pe_rows_in_waves = False
         self.K16 = ops.key16_dtype()  # dtype of the key side's 16-bit buffers (csrc/common.h "key16": fp16 since round 4)
         self.load_state(state_dict)
 
@@ -322,19 +244,19 @@ class HeadEngine:
         return self.w[k]
 
     # ------------------------------------------------------------------------------------------ workspace
-    def _workspace(self, V, h, w, R, Vg=None, map_dtype=F32):
+    def _workspace(self, V, h, w, R, Vg, map_dtype, st):
         """Buffers of one (map shape, R) problem.  The number of RoIs changes from frame to frame in real use, so the STORAGE is
         allocated once per (map shape, R rounded up to a multiple of 32, at least 64) and every exact R only gets a dict of dense views into it
         (kernels index [*, R, *] tensors densely) plus its own hipGraph; staging buffers, calibration cache and the stream-order
-        guard are shared by all R of a bucket."""
-        Vg = V if Vg is None else Vg                     # views per sample; V = all views of the batch
+        guard are shared by all R of a bucket.  Vg = views per sample, V = all views of the batch; st = the route's storage part (route.Storage):
+        routes that store their rows differently never share buffers."""
         # (the dtype of the feature map is part of both keys: ws['featcl'] has it, and a captured graph holds the launches of ONE element format)
-        key = (V, h, w, R, Vg, self.num_classes, self.roi_size, map_dtype)
+        key = (V, h, w, R, Vg, self.num_classes, self.roi_size, map_dtype, st)
         ws = self._ws.get(key)
         if ws is not None:
             return ws
         cap = max(64, -(-R // 32) * 32)
-        bkey = (V, h, w, cap, Vg, self.num_classes, self.roi_size, map_dtype)
+        bkey = (V, h, w, cap, Vg, self.num_classes, self.roi_size, map_dtype, st)
         base = self._ws_base.get(bkey)
         if base is None:
             store = []
@@ -346,7 +268,7 @@ class HeadEngine:
                     t = t.pin_memory()
                 store.append(t)
                 return t
-            self._build_ws(V, h, w, cap, alloc, Vg, map_dtype)
+            self._build_ws(V, h, w, cap, alloc, Vg, map_dtype, st)
             base = self._ws_base[bkey] = dict(store=store, shared={})
         it = iter(base['store'])
 
@@ -358,12 +280,12 @@ class HeadEngine:
             t = next(it)
             assert t.dtype == dt and t.numel() >= n
             return t.view(-1)[:n].view(shape)
-        ws = self._build_ws(V, h, w, R, view, Vg, map_dtype)
+        ws = self._build_ws(V, h, w, R, view, Vg, map_dtype, st)
         ws['shared'] = base['shared']
         self._ws[key] = ws
         return ws
 
-    def _build_ws(self, V, h, w, R, alloc, Vg, map_dtype=F32):
+    def _build_ws(self, V, h, w, R, alloc, Vg, map_dtype, st):
         d, L = self.dev, self.L
         P = V * h * w
         B = V // Vg                                      # samples sharing every launch
@@ -408,11 +330,12 @@ class HeadEngine:
         ws['qt_ctl'] = ws['zbuf'][Pp + 8:Pp + 16].view(torch.int32)      # query-order flags (zeroed with zbuf)
         ws['grp_ctl'] = ws['zbuf'][Pp + 16:Pp + 24].view(torch.int32)    # shared-tile cross attention: union entries allocated | capacity flag
         ws['lo8_flag'] = ws['zbuf'][Pp + 24:Pp + 28].view(torch.int32)   # e4m3 lo rows: a remainder left the format's range in this frame (csrc/common.h lo8_pack4_flag)
+        ws['ctl'] = ws['zbuf'][Pp:Pp + 32].view(torch.int32)             # the eight words above as one array (_check_capacity: one copy to the host)
         ws['zero_mask'] = z(P, torch.uint8)
         ws['rect'] = e((R, 5), torch.int32); ws['pos2s'] = e(P, torch.int32); ws['s2pos'] = e(P, torch.int32)
         ws['S_dev'] = z(1, torch.int32)
         ws['row_ptr'] = e(R + 1, torch.int32)
-        if self.kind == 'T':
+        if st.kind == 'T':
             ws['bits'] = e(max(ops.csr_workspace_bytes(R, Vg, h, w) // 4, 1), torch.int32)
             ws['row_count'] = e(R, torch.int32)
             ws['col_cap'] = R * self.col_cap_per_query
@@ -421,37 +344,40 @@ class HeadEngine:
             ws['col_cap'] = R * (1 + Vg * self.topk) * NC
             ws['S_kv'] = R * NC
             ws['roi_sum'] = e((R, NC, C), K16)
-        ws['q_order'] = alloc(R, torch.int32, zero=True) if self.q_order else None
+        ws['q_order'] = alloc(R, torch.int32, zero=True) if st.q_order else None
         ws['col_idx'] = e(ws['col_cap'], torch.int32)
         # group tables of the shared-tile cross attention (csrc/xattn_group.hip): g_slot | g_cnt | g_ptr | g_len per group, the groups' union key lists
-        ng = ops.xattn_group_max(R, B)
-        ucap = ws['col_cap'] + 16 * ng
-        ws['grp_tab'] = dict(ng=ng, g=alloc((4, ng), torch.int32, zero=True), ucol=alloc(ucap, torch.int32, zero=True),
-                             umask=alloc(ucap, torch.uint8, zero=True), ucap=ucap, ctl=ws['grp_ctl'])
+        ws['grp_tab'] = None
+        if st.group_tab:
+            ng = ops.xattn_group_max(R, B)
+            ucap = ws['col_cap'] + 16 * ng
+            ws['grp_tab'] = dict(ng=ng, g=alloc((4, ng), torch.int32, zero=True), ucol=alloc(ucap, torch.int32, zero=True),
+                                 umask=alloc(ucap, torch.uint8, zero=True), ucap=ucap, ctl=ws['grp_ctl'])
         # key16 rows of the PE block's inputs: frustum [.,192], sine [.,384] (training route only: the inference kernel reads the folded
         # table), feature rows [.,256] (the SE gate's input; the value rows of the T path)
         ws['A1'] = e((P, self.pe_kp), K16); ws['A2'] = e((P, 384), K16)
         ws['Xf_b'] = e((P, C), K16)
-        if self.exact:
+        if st.exact:
             # index-exact route: the unrounded fp32 frustum rows of the PE block (the feature rows are read from the map), the lo halves of the
             # key / value rows and RoI cells -- all pre-allocated (no per-frame allocation, no host synchronisation: the route is
             # graph-replayable like the default one)
             ws['xa1'] = e((P, self.pe_kp)); ws['xa2'] = e((P, 384))
-            lo8 = self._lo8()
-            LO = torch.uint8 if lo8 else K16
-            if self.kind == 'T':
+            lo8, LO = st.lo8, torch.uint8 if st.lo8 else K16
+            if st.kind == 'T':
                 ws['xk_lo'] = z((P, C), LO); ws['xv_lo'] = z((P, C), LO)
                 ws['roi_lo'] = e((R, NC, C), K16)                 # lo halves of the RoI cells (conv input)
             else:
                 ws['xk_lo'] = z((R * NC, C), LO); ws['xv_lo'] = z((R * NC, C), LO)
                 # S path: the value rows ARE the RoI cells (key16 lo rows: one array for both; lo8 rows: the split-precision conv, when it runs, reads its own key16 lo cells)
                 ws['roi_lo'] = e((R, NC, C), K16) if lo8 else ws['xv_lo'].view(R, NC, C)
+            # (the launches take the lo rows' format from the route, the kernels' binding from the buffers: they have to agree)
+            assert ws['xk_lo'].dtype == ws['xv_lo'].dtype == LO
         ws['pe'] = e((P, C)); ws['Xk'] = e((P, C), K16)
-        ws['pe_pos'] = z((P, C)) if (self.kind == 'S' and self.exact and self.pe_at_positions) else None      # never-listed rows stay 0 (they only ever meet weight 0)
+        ws['pe_pos'] = z((P, C)) if st.pe_pos else None      # never-listed rows stay 0 (they only ever meet weight 0)
         # cross attention in the raw key space: per-query operand Qt (key16 hi | lo rows of the 8 per-head maps), per-head context sums z
         ws['Qt'] = e((R, 16 * C), K16); ws['zh'] = e((R, 8 * C))
         # unprojected key / value input rows of the cross attention (key + key_pos, key): shared by all layers
-        if self.kind == 'T':
+        if st.kind == 'T':
             ws['xk_rows'], ws['xv_rows'] = ws['Xk'], ws['Xf_b']
         else:
             ws['xk_rows'], ws['xv_rows'] = ws['roi_sum'].view(R * NC, C), ws['roi_feat'].view(R * NC, C)
@@ -479,7 +405,7 @@ class HeadEngine:
             self._shape_cache[skey] = sht
         return skey, sht
 
-    def _host_prepare(self, proposals_list, metas_list, V, h, w, map_dtype=F32):
+    def _host_prepare(self, proposals_list, metas_list, V, h, w, rt):
         """Host side of one batch of samples: RoI lists + calibration tables into the workspace's pinned staging buffers.
         The camera matrices are compared with the previous frame's and, when they differ (every frame on the two-frame path: ego motion),
         the derived tables are rebuilt with batched calls and uploaded; the tables of the padding geometry only when the shapes change."""
@@ -501,7 +427,7 @@ class HeadEngine:
         # rows R..cap-1 are copies of the last RoI that belong to no sample (not in view_start / grp_start), so nothing attends to them,
         # nothing decodes them and the key set is unchanged; every R of a bucket shares one workspace and ONE captured graph.
         cap = max(64, -(-R // 32) * 32)
-        ws = self._workspace(V, h, w, cap, Vg, map_dtype)
+        ws = self._workspace(V, h, w, cap, Vg, rt.map_dtype, rt.storage)
         sh = ws['shared']
         if 'done_ev' in sh:
             sh['done_ev'].synchronize()      # the previous frame on this workspace must have consumed the pinned staging buffers (its uploads have run)
@@ -611,7 +537,7 @@ class HeadEngine:
 
     def _enqueue(self, ws, feat, R, V, h, w, sc):
         """Device side of one frame: everything below is enqueued on the current stream, no host sync."""
-        o, W_ = ops, self.w
+        o, W_, rt = ops, self.w, ws['route']
         P, L, T = ws['P'], self.L, ws['tab']
         B, Vg = ws['B'], ws['Vg']
         grp = ws['grp_start']                             # first query row of every sample (device): sample-local self attention / top-k; the rows behind the last sample are bucket padding
@@ -621,11 +547,10 @@ class HeadEngine:
         # position-major feature map.  Round 5: only the rows somebody reads are transposed (roi_mask: the RoIAlign taps, the key positions and the
         # rows the PE block gates all lie inside some RoI's rectangle), so the transposition runs BEHIND the kernels that build the position list;
         # the whole map is transposed for the training route, for keep_stages runs and when the query-generator chain is forked (key16 mode, T path)
-        forked = self.kind == 'T' and self.prof is None and self.fork_qg and not self.exact
+        forked = rt.forked
         # (T path: roi_mask = the correlation rectangles, which contain every RoIAlign tap only when expand_stride >= 1 -- with the default 0 of
         #  BoxCorrelation a bilinear tap can lie one cell outside its RoI's rectangle; the S path marks the exact tap range.  ADVICE r5)
-        masked = (self.masked_transpose and not forked and not self.keep_sine_rows and not getattr(self, '_stage_outputs', False) and
-                  (self.kind == 'S' or self.expand >= 1.0) and (h * w) % 4 == 0 and not (torch.is_tensor(feat) and feat.is_contiguous(memory_format=torch.channels_last) and not feat.is_contiguous()))
+        masked = (rt.masked and (rt.kind == 'S' or self.expand >= 1.0) and (h * w) % 4 == 0 and not (torch.is_tensor(feat) and feat.is_contiguous(memory_format=torch.channels_last) and not feat.is_contiguous()))
 
         def transpose(mask):
             if isinstance(feat, (list, tuple)):
@@ -650,39 +575,31 @@ class HeadEngine:
         # T path: the query-generator chain (RoIAlign -> conv -> fcs -> ref points -> query_pos) only needs the feature map and
         # the per-RoI cameras, the key chain (correlation -> key list -> PE -> K/V) only the boxes: run them on two streams
         if forked:
-            main = torch.cuda.current_stream()
             side = ws.get('side_stream')
             if side is None:
                 side = ws['side_stream'] = torch.cuda.Stream(device=self.dev)
-            side.wait_stream(main)
+            side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
                 o.roi_align(featcl, rois, h, w, out0=ws['roi_feat'], R=R, roi_size=self.roi_size)
                 self._enqueue_qg(ws, R)
-        if self.kind == 'T':
-            # a11/a12: key list + CSR, then a4 RoIAlign of the feature half only
+        order = ws['q_order']                             # (None unless the route orders the attention blocks)
+        if rt.kind == 'T':
+            # a11/a12: key list + CSR
             o.mask_compact(rois, ws['match'], T['pad_mask'], ws['roi_mask'], ws['rect'], ws['pos2s'], ws['s2pos'], ws['S_dev'],
                            ws['bits'], ws['row_count'], ws['row_ptr'], ws['col_idx'], ws['nnz'], R, Vg, h, w, self.topk,
                            self.stride, self.expand, col_cap=ws['col_cap'], n_samples=B)
-            if self.q_order and ws.get('q_order') is not None:
-                o.xattn_query_order(ws['row_ptr'], ws['col_idx'], grp, R, ws['q_order'], ws['qt_ctl'][1:])
-            if self._grouped(ws):
-                o.xattn_group_tables(ws['row_ptr'], ws['col_idx'], grp, R, ws['grp_tab'], order=ws.get('q_order') if self.q_order else None)
-            if masked:
-                transpose(ws['roi_mask'])
-            if not forked:
-                tk('roi_align')
-                o.roi_align(featcl, rois, h, w, out0=ws['roi_feat'],
-                            out0_lo=ws.get('roi_lo') if (self.exact and 'conv' not in self.exact_skip) else None, R=R, roi_size=self.roi_size)
+            if rt.q_order:
+                o.xattn_query_order(ws['row_ptr'], ws['col_idx'], grp, R, order, ws['qt_ctl'][1:])
         else:
-            if self.force_nc is not None:
+            if rt.force_nc is not None:
                 # the synthetic rig barely correlates RoIs across views, so the S-path sweep over n_c
                 # (RoIs per query) substitutes a synthetic correlation list: own RoI + (n_c - 1) others
                 fm = ws.get('forced_match')
                 if fm is None or fm.shape != ws['match'].shape:
-                    assert self.force_nc - 1 <= Vg * self.topk, 'raise corr_topk for this n_c'
+                    assert rt.force_nc - 1 <= Vg * self.topk, 'raise corr_topk for this n_c'
                     fmh = torch.full((R, Vg * self.topk), -1, dtype=torch.int32)
                     ar = torch.arange(R, dtype=torch.int32)
-                    for j in range(1, self.force_nc):
+                    for j in range(1, rt.force_nc):
                         fmh[:, j - 1] = (ar + 37 * j) % R
                     fm = ws['forced_match'] = fmh.view(R, Vg, self.topk).to(self.dev)
                 ws['match'].copy_(fm)
@@ -690,64 +607,60 @@ class HeadEngine:
             # the attention blocks (queries ranked by the smallest RoI they list)
             o.roi_positions_csr(rois, ws['zero_mask'], ws['roi_mask'], ws['rect'], ws['pos2s'], ws['s2pos'], ws['S_dev'], R, V, h, w, ws['match'],
                                 ws['row_ptr'], ws['col_idx'], ws['nnz'], Vg, self.topk, stride=self.stride, expand_stride=-1.0, grp_start=grp,
-                                order=ws.get('q_order') if self.q_order else None, order_flags=ws['qt_ctl'][1:] if self.q_order else None,
-                                roi_size=self.roi_size)
-            if self._grouped(ws):
-                o.xattn_group_tables(ws['row_ptr'], ws['col_idx'], grp, R, ws['grp_tab'], order=ws.get('q_order') if self.q_order else None)
-            if masked:
-                transpose(ws['roi_mask'])
+                                order=order, order_flags=ws['qt_ctl'][1:] if rt.q_order else None, roi_size=self.roi_size)
+        if rt.grouped:
+            o.xattn_group_tables(ws['row_ptr'], ws['col_idx'], grp, R, ws['grp_tab'], order=order)
+        if masked:
+            transpose(ws['roi_mask'])
+        if rt.kind == 'T' and not forked:
+            tk('roi_align')                               # a4: RoIAlign of the feature half only
+            o.roi_align(featcl, rois, h, w, out0=ws['roi_feat'], out0_lo=ws['roi_lo'] if rt.conv_x3 else None, R=R, roi_size=self.roi_size)
         md = ws['S_dev']
         # a2: PE at the listed positions only
-        if self.exact and 'pe' not in self.exact_skip:
+        if rt.pe_x3:
             tk('pe_inputs'); tk('pe_fused')
             self._exact_pe(ws, featcl, P, V, h, w)
         else:
             tk('pe_inputs')
             o.pe_inputs(ws['s2pos'], md, P, featcl, T['img2lidar'], T['coords_w'], T['coords_h'], T['coords_d'], T['embeds'],
-                        self.const['dim_t'], ws['A1'], ws['A2'] if self.keep_sine_rows else None, ws['Xf_b'], None,
+                        self.const['dim_t'], ws['A1'], ws['A2'] if rt.keep_sine_rows else None, ws['Xf_b'], None,
                         V, h, w, self.depth_num, self.pe_range_h64, ld=self._pe_ld())
             tk('pe_fused')
             # only what the path reads is written: S: pe (RoIAlign reads it; its keys are RoI-aligned rows), T: Xk (nothing reads pe);
             # a keep_stages run writes both
-            dbg = getattr(self, '_stage_outputs', False) or self.exact
+            dbg = rt.stages or rt.exact
             o.pe_fused_tab(ws['A1'], ws['Xf_b'], featcl, md, W_['pe_pack'], ws['shared']['sine_tab'], ws['shared']['sine_period'],
-                           ws['pe'] if (self.kind == 'S' or dbg) else None, ws['Xk'] if (self.kind == 'T' or dbg) else None, M=P,
+                           ws['pe'] if (rt.kind == 'S' or dbg) else None, ws['Xk'] if (rt.kind == 'T' or dbg) else None, M=P,
                            row_index=ws['s2pos'])
-        if self.kind == 'S':
+        if rt.kind == 'S':
             tk('roi_align')
             # key rows = RoIAlign(feat) + RoIAlign(pe), value rows = RoIAlign(feat) (index-exact route: both as key16 hi + lo pairs)
-            at_pos = self._pe_at_pos(ws)
-            pe_map, pe_idx = (ws['pe_pos'], None) if at_pos else (ws['pe'], ws['pos2s'])
-            if self.exact and self._lo8():
-                o.roi_align(featcl, rois, h, w, map1=pe_map, out0=ws['roi_feat'], out1=ws['roi_sum'], map1_index=pe_idx, out1_is_sum=True,
-                            out0_lo=ws.get('roi_lo') if 'conv' not in self.exact_skip else None, out0_lo8=ws['xv_lo'], out1_lo8=ws['xk_lo'], lo8_flag=ws['lo8_flag'], R=R,
-                            roi_size=self.roi_size)
+            pe_map, pe_idx = (ws['pe_pos'], None) if rt.pe_at_pos else (ws['pe'], ws['pos2s'])
+            if rt.lo8:
+                lo = dict(out0_lo=ws['roi_lo'] if rt.conv_x3 else None, out0_lo8=ws['xv_lo'], out1_lo8=ws['xk_lo'], lo8_flag=ws['lo8_flag'])
             else:
-                o.roi_align(featcl, rois, h, w, map1=pe_map, out0=ws['roi_feat'], out1=ws['roi_sum'], map1_index=pe_idx, out1_is_sum=True,
-                            out0_lo=ws['xv_lo'] if self.exact else None, out1_lo=ws['xk_lo'] if self.exact else None, R=R, roi_size=self.roi_size)
-        if self.ablate_zero_lo and self.exact:
-            if self._lo8():
-                raise ValueError('ablate_zero_lo works on key16 lo rows: set lo8_rows = False')
-            if 'v' in self.ablate_zero_lo and ws.get('xv_lo') is not None:
-                ws['xv_lo'].zero_()
-            if 'k' in self.ablate_zero_lo and ws.get('xk_lo') is not None:
-                ws['xk_lo'].zero_()
-            if '8' in self.ablate_zero_lo:                   # the lo halves rounded to 8-bit floats: what 256-byte lo rows would carry.  '8f': OCP e4m3 under the
-                for nm in ('xk_lo', 'xv_lo'):                # FIXED scale 2^12 (|lo| <= 2^-12 |x|: the format a kernel can write without a reduction); '8z': e4m3fnuz, '8': e5m2fnuz, per-tensor scale
-                    t = ws.get(nm)
-                    if t is not None:
-                        if '8f' in self.ablate_zero_lo:
-                            t.copy_(((t.float() * 4096.0).clamp(-448.0, 448.0).to(torch.float8_e4m3fn).float() / 4096.0).to(t.dtype))
-                            continue
-                        f8 = torch.float8_e4m3fnuz if '8z' in self.ablate_zero_lo else torch.float8_e5m2fnuz
-                        m = t.float().abs().max().clamp_min(1e-30)
-                        q8 = torch.exp2(torch.floor(torch.log2((100.0 if f8 == torch.float8_e4m3fnuz else 16000.0) / m)))
-                        t.copy_(((t.float() * q8).to(f8).float() / q8).to(t.dtype))
-        if not forked:
-            self._enqueue_qg(ws, R)
+                lo = dict(out0_lo=ws['xv_lo'], out1_lo=ws['xk_lo']) if rt.exact else {}
+            o.roi_align(featcl, rois, h, w, map1=pe_map, out0=ws['roi_feat'], out1=ws['roi_sum'], map1_index=pe_idx, out1_is_sum=True, R=R,
+                        roi_size=self.roi_size, **lo)
+        if rt.ablate_zero_lo:                                # (key16 lo rows: route.resolve refuses it on lo8 rows)
+            zero = rt.ablate_zero_lo
+            for c_ in 'vk':
+                if c_ in zero:
+                    ws[f'x{c_}_lo'].zero_()
+            if '8' in zero:                   # the lo halves rounded to 8-bit floats: what 256-byte lo rows would carry.  '8f': OCP e4m3 under the
+                for t in (ws['xk_lo'], ws['xv_lo']):         # FIXED scale 2^12 (|lo| <= 2^-12 |x|: the format a kernel can write without a reduction); '8z': e4m3fnuz, '8': e5m2fnuz, per-tensor scale
+                    if '8f' in zero:
+                        t.copy_(((t.float() * 4096.0).clamp(-448.0, 448.0).to(torch.float8_e4m3fn).float() / 4096.0).to(t.dtype))
+                        continue
+                    f8 = torch.float8_e4m3fnuz if '8z' in zero else torch.float8_e5m2fnuz
+                    m = t.float().abs().max().clamp_min(1e-30)
+                    q8 = torch.exp2(torch.floor(torch.log2((100.0 if f8 == torch.float8_e4m3fnuz else 16000.0) / m)))
+                    t.copy_(((t.float() * q8).to(f8).float() / q8).to(t.dtype))
         if forked:
             torch.cuda.current_stream().wait_stream(side)
-        if self.stop_before_decoder:
+        else:
+            self._enqueue_qg(ws, R)
+        if rt.stop_before_decoder:
             tk('end')
             return
         # a16-a19: decoder
@@ -767,9 +680,9 @@ class HeadEngine:
         product and sine-table sum in its epilogue; device-side row count S): pe rows into ws['pe'] (S path), key / value rows as key16 hi +
         lo pairs (T path).  Round 3 ran it as four K-concatenated products on the tile GEMM (hidden layer through HBM) + four split passes:
         1.09 ms (S) / 2.17 ms (T) per 16-sample launch.  No host synchronisation, no allocation: graph-replayable."""
-        o, W_, T = ops, self.w, ws['tab']
+        o, W_, T, rt = ops, self.w, ws['tab'], ws['route']
         md = ws['S_dev']
-        if self.keep_sine_rows:
+        if rt.keep_sine_rows:
             # (training route: it also reads the key16 rows and the sine rows)
             o.pe_inputs(ws['s2pos'], md, P, featcl, T['img2lidar'], T['coords_w'], T['coords_h'], T['coords_d'], T['embeds'],
                         self.const['dim_t'], ws['A1'], ws['A2'], ws['Xf_b'], None, V, h, w, self.depth_num,
@@ -779,12 +692,11 @@ class HeadEngine:
             o.pe_frustum_f32(ws['s2pos'], md, P, T['img2lidar'], T['coords_w'], T['coords_h'], T['coords_d'], ws['xa1'], V, h, w, self.depth_num,
                              self.pe_range_h64, ld=self._pe_ld())
         sh = ws['shared']
-        rows = self.kind == 'T'
-        dbg = getattr(self, '_stage_outputs', False)
-        at_pos = self._pe_at_pos(ws)
-        (o.pe_fused_x3b if self.pe_rows_in_waves else o.pe_fused_x3)(
-            ws['xa1'], featcl, md, W_['pe_x3'], sh['sine_tab'], sh['sine_period'], pe=(ws['pe_pos'] if at_pos else ws['pe']) if (not rows or dbg) else None,
-            Xk=(ws['Xk'], ws['xk_lo']) if rows else None, Xv=(ws['Xf_b'], ws['xv_lo']) if rows else None, M=P, row_index=ws['s2pos'], pe_at_index=at_pos, lo8_flag=ws['lo8_flag'] if (rows and self._lo8()) else None,
+        rows = rt.kind == 'T'
+        at_pos = rt.pe_at_pos
+        (o.pe_fused_x3b if rt.pe_rows_in_waves else o.pe_fused_x3)(
+            ws['xa1'], featcl, md, W_['pe_x3'], sh['sine_tab'], sh['sine_period'], pe=(ws['pe_pos'] if at_pos else ws['pe']) if (not rows or rt.stages) else None,
+            Xk=(ws['Xk'], ws['xk_lo']) if rows else None, Xv=(ws['Xf_b'], ws['xv_lo']) if rows else None, M=P, row_index=ws['s2pos'], pe_at_index=at_pos, lo8_flag=ws['lo8_flag'] if (rows and rt.lo8) else None,
             **({} if self.depth_num == 64 else dict(Kp=self.pe_kp)))            # (64 bins: the entries without a size argument, as before)
 
     def _pe_ld(self):
@@ -812,7 +724,7 @@ class HeadEngine:
         o, W_, tk = ops, self.w, self._tick
         # a6: QueryGenerator: conv3x3 + ReLU + AvgPool2d(s) fused, one block per RoI (index-exact route: in split precision on the hi + lo cells)
         tk('qg_conv_gemm')
-        if self.exact and 'conv' not in self.exact_skip:
+        if ws['route'].conv_x3:
             o.qg_conv_pool_x3(ws['roi_feat'], ws['roi_lo'], W_['qg_conv_wx3'], W_['qg_conv_b'], ws['x2'], R=R, roi_size=self.roi_size)
         else:
             o.qg_conv_pool(ws['roi_feat'], W_['qg_conv_wp'], W_['qg_conv_b'], ws['x2'], R=R, roi_size=self.roi_size)
@@ -829,28 +741,26 @@ class HeadEngine:
         the "decoder ms/iter" half of the headline metric.  Per layer: self attention (bf16x3 MFMA, K / V through LDS), out_proj + LN +
         cross-attention q projection (row-fused, bf16x3), cross attention in the raw key space (query map, tile kernel, context map), out_proj
         + LN, fused FFN (bf16x3) and its tail (slab sum + LN + post_norm + the next layer's in_proj)."""
-        o, W_, L = ops, self.w, self.L
+        o, W_, L, rt = ops, self.w, self.L, ws['route']
         x = ws['x']
+        dn = ws.get('dn')                                 # the training forward's own workspace (its route: Route.denoising)
+        dbg = ws['dbg_logits'] if rt.debug_attn else None
+        maps_fused = not (rt.grouped or rt.xattn_fused) and rt.maps_fused(R)
+        # the cross attention's rows, shared by all layers (raw key space): key16 hi rows, their lo halves on the index-exact route, launch order
         xk_rows, xv_rows = ws['xk_rows'], ws['xv_rows']
-        dbg = ws.get('dbg_logits')
-        maps_fused = ((R <= 512) if self.fuse_maps is None else self.fuse_maps) and dbg is None
-        xattn_fused = ((self.kind == 'S' and not ws.get('dn')) if self.fuse_xattn is None else self.fuse_xattn) and dbg is None
-        xattn_group = self._grouped(ws) and dbg is None
-        lo_k = None if 'attn' in self.exact_skip else ws.get('xk_lo')
-        lo_v = None if 'attn' in self.exact_skip else ws.get('xv_lo')
+        lo_k, lo_v = (ws['xk_lo'], ws['xv_lo']) if rt.attn_lo else (None, None)
+        rows = dict(Xk_lo=lo_k, Xv_lo=lo_v, empty_nan=self.empty_nan, order=ws['q_order'] if rt.q_order else None)
 
         def tile_attn(i):
             if dbg is not None:
                 ws['dbg_q'][i].copy_(ws['q'])
-            o.xattn_tile(ws['Qt'], xk_rows, xv_rows, ws['row_ptr'], ws['col_idx'], ws['zh'], R, empty_nan=self.empty_nan, waves=self.xattn_waves,
-                         Xk_lo=None if 'attn' in self.exact_skip else ws.get('xk_lo'), Xv_lo=None if 'attn' in self.exact_skip else ws.get('xv_lo'),
-                         dbg_logits=None if dbg is None else dbg[i],
-                         order=ws.get('q_order') if self.q_order else None)
+            o.xattn_tile(ws['Qt'], xk_rows, xv_rows, ws['row_ptr'], ws['col_idx'], ws['zh'], R, waves=rt.xattn_waves,
+                         dbg_logits=None if dbg is None else dbg[i], **rows)
 
         # the decoder starts from target = 0 (cross_attention_head.py:32): layer 0 reads a constant zero buffer and qpos directly, from
         # layer 1 on x / xq are the buffers the fused FFN tail writes
         x_in, xq_in = ws['zero_rows'], ws['qpos']
-        fold0 = self.fold_sa0 and not ws.get('dn') and ws.get('sa0_ctx') is not None
+        fold0 = rt.fold_sa0
         if fold0 and ws.get('sa0_ver') != self._weights_version:
             # (first run on this workspace after the weights changed: the eager warm-up in front of a graph capture comes through here)
             ws['sa0_ctx'].copy_(W_['sa_in_b0'][2 * C:].expand(ws['sa0_ctx'].shape[0], C))
@@ -864,33 +774,29 @@ class HeadEngine:
             else:
                 if i == 0:
                     o.linear_x3(xq_in, W_['sa_in_wx0'], W_['sa_in_b0'], N=3 * C, K=C, A2=x_in, n_split=2 * C, out=ws['qkv'], M=R)
-                if ws.get('dn'):
-                    o.self_attn_dn(ws['qkv'], ws['dn'][0], ws['dn'][1], out=ws['ctx'])      # training: denoising rows first (train_forward)
+                if dn:
+                    o.self_attn_dn(ws['qkv'], dn[0], dn[1], out=ws['ctx'])      # training: denoising rows first (train_forward)
                 else:
                     o.self_attn(ws['qkv'], ws['ctx'], R, grp_start=ws['grp_start'], max_grp_rows=ws.get('max_rows', 0))
             sa_args = (sa_ctx, x_in, W_[f'sa_out_wx{i}'], W_[f'sa_out_b{i}'], (W_[f'ln0_w{i}'], W_[f'ln0_b{i}']), ws['x1'])
             q_args = dict(qpos=ws['qpos'], Wq_x3=W_[f'ca_q_wx{i}'], bq=W_[f'ca_q_b{i}'], qscale=ops.SCALE_Q, M=R)
-            if xattn_group:
-                o.attn_out_fused_x3(*sa_args, q_out=ws['q'], **q_args)
-                o.xattn_group(ws['q'], W_[f'ca_mapA{i}'], W_[f'ca_mapB{i}'], W_[f'ca_v_b{i}'], xk_rows, xv_rows, ws['row_ptr'], ws['grp_tab'], out=ws['ctx'], R=R,
-                              empty_nan=self.empty_nan, Xk_lo=lo_k, Xv_lo=lo_v, order=ws.get('q_order') if self.q_order else None)
-                o.attn_out_fused_x3(ws['ctx'], ws['x1'], W_[f'ca_out_wx{i}'], W_[f'ca_out_b{i}'], (W_[f'ln1_w{i}'], W_[f'ln1_b{i}']), ws['x2'], M=R)
-            elif xattn_fused:
-                o.attn_out_fused_x3(*sa_args, q_out=ws['q'], **q_args)
-                o.xattn_fused(ws['q'], W_[f'ca_mapA{i}'], W_[f'ca_mapB{i}'], W_[f'ca_v_b{i}'], xk_rows, xv_rows, ws['row_ptr'], ws['col_idx'], out=ws['ctx'], R=R,
-                              empty_nan=self.empty_nan, Xk_lo=lo_k, Xv_lo=lo_v, order=ws.get('q_order') if self.q_order else None)
-                o.attn_out_fused_x3(ws['ctx'], ws['x1'], W_[f'ca_out_wx{i}'], W_[f'ca_out_b{i}'], (W_[f'ln1_w{i}'], W_[f'ln1_b{i}']), ws['x2'], M=R)
-            elif maps_fused:
-                o.attn_out_qmap_x3(*sa_args, WA=W_[f'ca_mapA{i}'], Qt=ws['Qt'], **q_args)
+            out_args = (ws['x1'], W_[f'ca_out_wx{i}'], W_[f'ca_out_b{i}'], (W_[f'ln1_w{i}'], W_[f'ln1_b{i}']), ws['x2'])
+            mapA, mapB, bv = W_[f'ca_mapA{i}'], W_[f'ca_mapB{i}'], W_[f'ca_v_b{i}']
+            if maps_fused:
+                o.attn_out_qmap_x3(*sa_args, WA=mapA, Qt=ws['Qt'], **q_args)
                 tile_attn(i)
-                o.attn_out_zmap_x3(ws['zh'], W_[f'ca_mapB{i}'], W_[f'ca_v_b{i}'], ws['row_ptr'], ws['x1'], W_[f'ca_out_wx{i}'], W_[f'ca_out_b{i}'],
-                                   (W_[f'ln1_w{i}'], W_[f'ln1_b{i}']), ws['x2'], empty_nan=self.empty_nan, M=R)
+                o.attn_out_zmap_x3(ws['zh'], mapB, bv, ws['row_ptr'], *out_args, empty_nan=self.empty_nan, M=R)
             else:
                 o.attn_out_fused_x3(*sa_args, q_out=ws['q'], **q_args)
-                o.xattn_qmap(ws['q'], W_[f'ca_mapA{i}'], ws['Qt'], R=R)
-                tile_attn(i)
-                o.xattn_ctxmap(ws['zh'], W_[f'ca_mapB{i}'], W_[f'ca_v_b{i}'], ws['row_ptr'], ws['ctx'], R, empty_nan=self.empty_nan)
-                o.attn_out_fused_x3(ws['ctx'], ws['x1'], W_[f'ca_out_wx{i}'], W_[f'ca_out_b{i}'], (W_[f'ln1_w{i}'], W_[f'ln1_b{i}']), ws['x2'], M=R)
+                if rt.grouped:
+                    o.xattn_group(ws['q'], mapA, mapB, bv, xk_rows, xv_rows, ws['row_ptr'], ws['grp_tab'], out=ws['ctx'], R=R, **rows)
+                elif rt.xattn_fused:
+                    o.xattn_fused(ws['q'], mapA, mapB, bv, xk_rows, xv_rows, ws['row_ptr'], ws['col_idx'], out=ws['ctx'], R=R, **rows)
+                else:
+                    o.xattn_qmap(ws['q'], mapA, ws['Qt'], R=R)
+                    tile_attn(i)
+                    o.xattn_ctxmap(ws['zh'], mapB, bv, ws['row_ptr'], ws['ctx'], R, empty_nan=self.empty_nan)
+                o.attn_out_fused_x3(ws['ctx'], *out_args, M=R)
             # eight hidden slices accumulated per block: 4 slabs to write and re-read instead of 32 (round 3: 8371 vs 8289 samples/s for
             # 8 vs 4 slices, and half the slab traffic).  It fixes the summation order, so it is NOT chosen by the row count: a sample's
             # result must not depend on the batch it is in.
@@ -902,47 +808,27 @@ class HeadEngine:
                                x, ws['qpos'], None, outs=ws['outs'][i], Win_x3=W_[f'sa_in_wx{i + 1}'] if nxt else None,
                                b_in=W_[f'sa_in_b{i + 1}'] if nxt else None, qkv=ws['qkv'] if nxt else None, M=R)
 
-    def _pe_at_pos(self, ws):
-        """S path, index-exact route: are the PE rows written at their map positions (ws['pe_pos']) rather than compacted (ws['pe'])?"""
-        return (self.kind == 'S' and self.exact and 'pe' not in self.exact_skip and bool(self.pe_at_positions) and ws.get('pe_pos') is not None and
-                not getattr(self, '_stage_outputs', False))
-
-    def _lo8(self):
-        """Are the lo halves of the key / value rows e4m3 bytes (csrc/common.h "lo8")?  Not with the shared-tile kernel (its LDS-DMA tiles are key16 rows)."""
-        return bool(self.lo8_rows) and self.exact and not self.group_xattn
-
-    def _grouped(self, ws):
-        """Does this frame's cross attention run on shared key tiles (csrc/xattn_group.hip)?  Needs the group tables of the workspace (the training
-        forward's own decoder workspace has none) and no debug output."""
-        on = bool(self.group_xattn)
-        return on and ws.get('grp_tab') is not None and not self.debug_attn and not ws.get('dn')
-
     def _enqueue_heads(self, ws, R, dt):
-        # a14: every per-layer cls / reg branch + the reference-point tail in ONE launch (row-block fused, bf16x3)
+        # a14: every per-layer cls / reg branch + the reference-point tail in ONE launch (row-block fused, bf16x3).  Route.last_stage_heads: the
+        # branches of the LAST decoder layer only (the reference evaluates all six and reads [-1], cross_attention_head.py:202-242 /
+        # RH/mv2d_head.py:170-194); cls / reg of the other layers are then not written
         dt_rows = ws['dt_rows'] if self.kind == 'T' else None
+        last = ws['route'].last_stage_heads
+        ll, n = (self.L - 1, 1) if last else (0, self.L)
+        cls_p, reg_p = (self.cls_ptrs_x3_last, self.reg_ptrs_x3_last) if last else (self.cls_ptrs_x3, self.reg_ptrs_x3)
+        outs, cls, reg = ws['outs'][ll:], ws['cls'][ll:], ws['reg'][ll:]
         if self.use_reg_layer:
             # RegLayer regression branches: the class branch alone through the fused kernel, the regression branch + tail through its own
-            last = self.last_stage_heads and not getattr(self, '_stage_outputs', False)
-            ll, n = (self.L - 1, 1) if last else (0, self.L)
-            ops.heads_cls_x3(ws['outs'][ll:], self.cls_ptrs_x3_last if last else self.cls_ptrs_x3, ws['cls'][ll:], R, n, num_classes=self.num_classes)
-            ops.reg_layer_x3(ws['outs'][ll:], self.reg_ptrs_x3_last if last else self.reg_ptrs_x3, ws['ref'], ws['reg'][ll:], R, n,
-                             self.group_reg_dims, self.pc_range_h, dt, dt_rows=dt_rows)
-            return
-        if self.last_stage_heads and not getattr(self, '_stage_outputs', False):
-            # inference needs the branches of the LAST decoder layer only (the reference evaluates all six and reads [-1],
-            # cross_attention_head.py:202-242 / RH/mv2d_head.py:170-194); cls / reg of the other layers are then not written
-            ll = self.L - 1
-            ops.heads_fused_x3(ws['outs'][ll:], self.cls_ptrs_x3_last, self.reg_ptrs_x3_last, ws['ref'], ws['cls'][ll:], ws['reg'][ll:], R, 1,
-                               self.pc_range_h, dt, dt_rows=dt_rows, num_classes=self.num_classes)
+            ops.heads_cls_x3(outs, cls_p, cls, R, n, num_classes=self.num_classes)
+            ops.reg_layer_x3(outs, reg_p, ws['ref'], reg, R, n, self.group_reg_dims, self.pc_range_h, dt, dt_rows=dt_rows)
         else:
-            ops.heads_fused_x3(ws['outs'], self.cls_ptrs_x3, self.reg_ptrs_x3, ws['ref'], ws['cls'], ws['reg'], R, self.L, self.pc_range_h, dt,
-                               dt_rows=dt_rows, num_classes=self.num_classes)
+            ops.heads_fused_x3(outs, cls_p, reg_p, ws['ref'], cls, reg, R, n, self.pc_range_h, dt, dt_rows=dt_rows, num_classes=self.num_classes)
 
-    def _result(self, ws, R, keep_stages=False, batch=False):
+    def _result(self, ws, R, batch=False):
         sel = (lambda t: t) if batch else (lambda t: t[0])
         out = dict(R=R, ws=ws, cls=ws['cls'][:, :R], reg=ws['reg'][:, :R], boxes=sel(ws['boxes']), scores=sel(ws['scores']), labels=sel(ws['labels']),
                    bbox_index=sel(ws['bbox_index']), count=ws['count'] if batch else ws['count'][:1], grp_start=ws['grp_start_h'].clone())
-        if keep_stages:
+        if ws['route'].stages:
             # copies of the intermediate buffers restricted to the REAL rows (the launches run on the bucket size, see _host_prepare)
             rows0 = ('rois', 'minv', 'enc', 'roi_feat', 'center', 'xyz', 'ref', 'posemb', 'qpos', 'match')
             st = {}
@@ -984,12 +870,7 @@ class HeadEngine:
         ops.map_format(map_dtype)                         # ValueError for anything but fp32 / fp16 / bf16
         if any(f.dtype != map_dtype for f in fl):
             raise ValueError(f'mv2d engine: the feature maps of a batch must share one dtype, got {sorted({str(f.dtype) for f in fl})}')
-        if self.depth_num != 64 and not (self.exact and 'pe' not in self.exact_skip):
-            raise ValueError(f'mv2d engine: the key16 mode\'s PE kernel (csrc/pe_tab96.hip) is built for depth_num = 64 only; run the index-exact route (exact=True, the default) with depth_num = {self.depth_num}')
-        if self.depth_num != 64 and self.pe_rows_in_waves:
-            raise ValueError(f'mv2d engine: pe_rows_in_waves (csrc/pe_x3b.hip) is built for depth_num = 64 only; unset it for depth_num = {self.depth_num}')
-        if map_dtype != F32 and self.pe_rows_in_waves and self.exact and 'pe' not in self.exact_skip:
-            raise ValueError('mv2d engine: pe_rows_in_waves (csrc/pe_x3b.hip) reads fp32 feature maps only; unset it for a torch.float16 / torch.bfloat16 map')
+        rt = route.resolve(self, self.kind, self.exact, self.depth_num, map_dtype, keep_stages, use_graph)     # (ValueError for impossible combinations)
         if stacked or B == 1:
             feat = fl[0]
             if not (feat.is_contiguous(memory_format=torch.channels_last) and not feat.is_contiguous()):
@@ -1004,17 +885,15 @@ class HeadEngine:
             V = Vg * B
             ptrs = tuple(f.data_ptr() for f in feat)
         assert V % B == 0
-        ws, R, sc = self._host_prepare(proposals_list, metas_list, V, h, w, map_dtype)
+        ws, R, sc = self._host_prepare(proposals_list, metas_list, V, h, w, rt)
         # upload of the per-frame tables (RoI list, view / sample offsets, time steps): stream-ordered before the frame, outside the captured graph.
         # The "staging consumed" event stays at the END of the frame: recording it right behind this copy would let the host run a frame ahead on every
         # stream; measured in round 3: +1 % in long runs but 7400-7900 instead of 8300 samples/s in short ones -- without the host's wait the four
         # streams drift into phase and their wide kernels collide (LOG.md section 8)
         ws['dyn_d'].copy_(ws['dyn_h'], non_blocking=True)
-        ws['payload_out'] = payload
-        self._stage_outputs = bool(keep_stages)          # intermediate buffers nothing downstream reads (pe on the T path, Xk on the S path)
+        ws['payload_out'], ws['route'] = payload, rt
         Rc = sc['cap']                     # launches run on the bucket size; R = the real rows
-        if self.debug_attn:
-            assert not use_graph, 'debug_attn: eager runs only'
+        if rt.debug_attn:
             ws['dbg_logits'] = torch.zeros((self.L, 8, ws['col_cap']), device=self.dev, dtype=F32)
             ws['dbg_q'] = torch.zeros((self.L, Rc, C), device=self.dev, dtype=F32)
         else:
@@ -1022,12 +901,12 @@ class HeadEngine:
         if not use_graph:
             self._enqueue(ws, feat, Rc, V, h, w, sc)
             self._mark_done(ws)
-            return dict(self._result(ws, R, keep_stages, batch), dt=sc['dt'])
+            return dict(self._result(ws, R, batch), dt=sc['dt'])
         # the graph bakes in the input pointers (the producer's output buffers are static under graph replay) and the
-        # frame scalars; anything else changing (RoI boxes, calibration tables, feature values) is data.
-        gkey = (ptrs, map_dtype, 0 if payload is None else payload.data_ptr(), sc['pad_h'], sc['pad_w'], sc['max_rows'], self.num_classes, self.roi_size, self.use_reg_layer, self.group_reg_dims, self._weights_version, self._stage_outputs, self.last_stage_heads,
-                self.xattn_waves, self.fuse_maps, self.fuse_xattn, self.group_xattn, self.lo8_rows, self.pe_at_positions, self.pe_rows_in_waves, self.fold_sa0, self.masked_transpose, self.keep_sine_rows, self.force_nc, self.q_order,
-                self.fork_qg, self.exact_skip, self.ablate_zero_lo, self.stop_before_decoder)   # load_state() re-allocates the weights; every route option of __init__ is in the key
+        # frame scalars; anything else changing (RoI boxes, calibration tables, feature values) is data.  The route carries every option;
+        # load_state() re-allocates the weights.
+        gkey = (ptrs, 0 if payload is None else payload.data_ptr(), sc['pad_h'], sc['pad_w'], sc['max_rows'], self.num_classes, self.roi_size,
+                self.use_reg_layer, self.group_reg_dims, self._weights_version, rt)
         graphs = ws.setdefault('graphs', {})             # one graph per (input buffers, frame scalars): a producer that alternates between
         g = graphs.get(gkey)                             # a few static output buffers replays a few graphs, it does not re-capture
         if ws.pop('graph_stale', False):
@@ -1053,7 +932,7 @@ class HeadEngine:
             g = g[0]
         g.replay()
         self._mark_done(ws)
-        return dict(self._result(ws, R, keep_stages, batch), dt=sc['dt'])
+        return dict(self._result(ws, R, batch), dt=sc['dt'])
 
     def train_forward(self, out, dn_ref=None, dn_single=0):
         """Training forward of the decoder + heads on top of a finished ``run`` of ONE sample: the decoder runs again
@@ -1113,7 +992,7 @@ class HeadEngine:
         posemb = o.posemb3d(dn_ref.to(F32).contiguous(), self.const['dim_t'])
         q1 = o.linear_x3(posemb, W_['qe_w0x'], W_['qe_b0'], N=C, K=384, act=1)
         qdn = o.linear_x3(q1, W_['qe_w2x'], W_['qe_b2'], N=C, K=C)
-        tws = dict(B=1, Vg=ws['Vg'], dn=(pad, max(int(dn_single), 1)), grp_start=None, xk_rows=ws['xk_rows'], xv_rows=ws['xv_rows'],
+        tws = dict(B=1, Vg=ws['Vg'], dn=(pad, max(int(dn_single), 1)), route=ws['route'].denoising(), grp_start=None, xk_rows=ws['xk_rows'], xv_rows=ws['xv_rows'],
                    Qt=torch.empty((T, 16 * C), device=d, dtype=self.K16), zh=e(T, 8 * C),
                    row_ptr=torch.cat([torch.arange(pad, device=d, dtype=torch.int32) * nk, row_ptr + pad * nk]),
                    col_idx=torch.cat([keys.repeat(pad), col]).contiguous(),
@@ -1146,11 +1025,12 @@ class HeadEngine:
 
     @staticmethod
     def _check_capacity(ws):
-        if int(ws['nnz'][1].item()) != 0:
+        _, nnz_over, _, _, _, grp_over, lo8_sat, _ = ws['ctl'].tolist()       # nnz[2] | qt_ctl[2] | grp_ctl[2] | lo8_flag: one copy to the host
+        if nnz_over != 0:
             raise RuntimeError('mv2d engine: CSR capacity exceeded (raise col_cap_per_query)')
-        if ws.get('grp_ctl') is not None and int(ws['grp_ctl'][1].item()) != 0:
+        if grp_over != 0:
             raise RuntimeError('mv2d engine: union-list capacity of the shared-tile cross attention exceeded (a CSR row lists a key twice?)')
-        if ws.get('lo8_flag') is not None and int(ws['lo8_flag'][0].item()) != 0:
+        if lo8_sat != 0:
             import warnings
             warnings.warn('mv2d engine: key / value rows beyond +-224 in this frame: their 8-bit lo halves saturated (those elements keep key16 precision); '
                           'set HeadEngine.lo8_rows = False for fp16 lo rows', RuntimeWarning, stacklevel=3)

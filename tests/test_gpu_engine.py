@@ -357,6 +357,7 @@ def test_engine_map_kernels_fused_or_separate_bitwise_equal(kind, name):
     if grouped is not None:
         for k in ('cls', 'reg'):
             err = float((grouped[k] - out[k]).abs().max()) / float(out[k].abs().max())
+            print(f'[shared-tile cross attention on fp16 lo rows vs the default route on lo8 rows] {name} {k}: {err:.2e}')
             assert err < 2e-5, (k, err)
     ref = {k: out[k].clone() for k in ('cls', 'reg')}
     for forced in (False, True):
@@ -465,6 +466,83 @@ def test_round6_storage_options(kind, name):
         print(f'[lo8 rows vs fp16 lo rows] {name} frame {i}: cls {e:.2e}, ranked indices equal: {bool(torch.equal(ra[i]["bbox_index"][:n], rc[i]["bbox_index"][:n]))}')
         assert e < 1e-6, e
         assert int(ra[i]['count'].item()) == n and torch.equal(ra[i]['bbox_index'][:n], rc[i]['bbox_index'][:n]) and torch.equal(ra[i]['labels'][:n], rc[i]['labels'][:n])
+
+
+SNAP = ('cls', 'reg', 'boxes', 'scores', 'labels', 'bbox_index', 'count')
+
+
+def _frames(eng, feat, props, metas):
+    """one frame eager, then the same frame through a captured graph"""
+    outs = []
+    for use_graph in (False, True):
+        o = eng.run(feat, props, metas, use_graph=use_graph)
+        torch.cuda.synchronize()
+        outs.append({k: o[k].clone() for k in SNAP})
+    return outs
+
+
+def _assert_frames_equal(got, want, what):
+    for g, w, mode in zip(got, want, ('eager', 'graph')):
+        for k in SNAP:
+            assert torch.equal(g[k], w[k]), (what, mode, k)
+
+
+@pytest.mark.parametrize('kind,name,option,value', [('S', 'cfg1_s', 'lo8_rows', False), ('T', 'cfg1_t', 'lo8_rows', False), ('S', 'cfg1_s', 'pe_at_positions', False),
+                                                    ('T', 'cfg1_t', 'group_xattn', True), ('T', 'cfg1_t', 'q_order', False)])
+def test_option_set_on_a_live_engine_equals_a_fresh_engine(kind, name, option, value):
+    """The options that choose how a workspace STORES its rows (mv2d_amd/route.py, Route.storage), set on an engine that has already run a
+    frame: the next frame (eager and graph replay) is bit for bit what a fresh engine with the option set before its first frame computes --
+    also a frame with fewer proposals that falls into the same 32-row bucket -- and setting the option back gives the first frame again."""
+    from mv2d_amd import route
+    from mv2d_amd.engine import HeadEngine
+    prob = synthetic.make_problem(name, seed=0)
+    sd = synthetic.make_head_state(seed=0)
+    dev = torch.device('cuda:0')
+    feat = torch.from_numpy(prob['feat']).to(dev)
+    full = [torch.from_numpy(p) for p in prob['proposals']]
+    fewer = [p[:max(1, p.shape[0] - 2 - i)] for i, p in enumerate(full)]        # (variants[1] of test_engine_varying_roi_count_shares_one_storage)
+    mk = lambda: HeadEngine(sd, kind, dev, num_views=prob['views_per_frame'])  # noqa: E731
+    eng = mk()
+    default = getattr(eng, option)
+    assert default == route.default_options()[option] and bool(default) != bool(value)
+    first = _frames(eng, feat, full, prob['img_metas'])
+    setattr(eng, option, value)
+    toggled = _frames(eng, feat, full, prob['img_metas'])
+    fresh = mk()
+    setattr(fresh, option, value)
+    _assert_frames_equal(toggled, _frames(fresh, feat, full, prob['img_metas']), 'option set on the live engine')
+    assert len(eng._ws_base) == 2 and len(fresh._ws_base) == 1                  # its rows are stored differently: buffers of their own
+    fresh = mk()
+    setattr(fresh, option, value)
+    _assert_frames_equal(_frames(eng, feat, fewer, prob['img_metas']), _frames(fresh, feat, fewer, prob['img_metas']), 'fewer proposals, same bucket')
+    assert len(eng._ws_base) == 2
+    setattr(eng, option, default)
+    _assert_frames_equal(_frames(eng, feat, full, prob['img_metas']), first, 'option set back')
+    assert len(eng._ws_base) == 2
+
+
+@pytest.mark.parametrize('kind,name', [('S', 'cfg1_s'), ('T', 'cfg1_t')])
+def test_launch_only_switches_share_one_storage(kind, name):
+    """Options that only choose launches (not how rows are stored) run on the buffers of the frames before them: one storage, one workspace."""
+    from mv2d_amd.engine import HeadEngine
+    prob = synthetic.make_problem(name, seed=0)
+    dev = torch.device('cuda:0')
+    feat = torch.from_numpy(prob['feat']).to(dev)
+    props = [torch.from_numpy(p) for p in prob['proposals']]
+    eng = HeadEngine(synthetic.make_head_state(seed=0), kind, dev, num_views=prob['views_per_frame'])
+    first = _frames(eng, feat, props, prob['img_metas'])
+    eng.last_stage_heads = True
+    last = _frames(eng, feat, props, prob['img_metas'])
+    eng.fuse_maps = False
+    sep = _frames(eng, feat, props, prob['img_metas'])
+    eng.xattn_waves = 4
+    _frames(eng, feat, props, prob['img_metas'])
+    assert len(eng._ws_base) == 1 and len(eng._ws) == 1
+    assert len(next(iter(eng._ws.values()))['graphs']) == 4                    # (every one of them is in the graph key)
+    for got in (last, sep):                                                   # decoded boxes of the last layer: untouched by the first two switches
+        for g, w in zip(got, first):
+            for k in SNAP[2:]:
+                assert torch.equal(g[k], w[k]), k
 
 
 @pytest.mark.parametrize('kind,name', [('S', 'cfg1_s'), ('T', 'cfg1_t')])
