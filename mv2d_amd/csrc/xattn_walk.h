@@ -1,7 +1,10 @@
 // Building blocks of the cross-attention kernels (xattn_tile.hip, xattn_fused.hip, xattn_group.hip): the fragment types and split helpers of all
 // three, and XattnWalk -- what ONE WAVE does with ONE 16-key tile of a query's CSR row.  xattn_tile_kernel and phase B of xattn_fused_kernel are
 // this walk with their own loop around it, which is why the fused kernel is bit for bit the three kernels with one wave per query
-// (tests/test_gpu_kernels.py::test_xattn_fused_equals_the_three_kernels).  xattn_group.hip takes only the small helpers.
+// (tests/test_gpu_kernels.py::test_xattn_fused_equals_the_three_kernels -- one piece of code against itself, no evidence for the walk).
+// The walk's reference check is tests/test_gpu_xattn_lo.py: logits, z and ctx of every row against fp64 with hi rows alone, key16 lo and e4m3 lo
+// rows, on rows of 0 .. 613 keys at the edges of the tile and of 1, 2, 4, 8 waves, and on rows whose hi halves are identical, where the
+// lo terms carry all of the result (tests/xattn_cases.py).  xattn_group.hip takes only the small helpers; its own walk is held there too.
 #pragma once
 #include "common.h"
 #include <type_traits>
