@@ -195,6 +195,20 @@ int mv2d_query_embed_fused_x3(const float* enc2, const float* Wc, const float* b
                               const void* W2_lo, const float* b2, float* center, float* xyz, float* ref, float* posemb,
                               float* qpos, int R, void* stream);
 
+/* The query generator's MLP tail and mv2d_query_embed_fused_x3 in ONE launch, bitwise the chain it replaces:
+ *   mv2d_linear_x3(x2 [R,256] -> enc[:, :1024], ReLU, clamp 5e3), mv2d_linear_x3(enc [R,1056] -> enc1 [R,512], ReLU),
+ *   mv2d_linear_x3(enc1 -> enc2 [R,256], ReLU), mv2d_query_embed_fused_x3(enc2 -> center, xyz, ref, posemb, qpos)
+ * (RH/utils/query_generator.py:359-381,404 with the shipped dimensions only: 256 -> 1024, 1024 + 32 intrinsics columns -> 512 -> 256,
+ * 384 -> 256 -> 256).  enc: rows of ld_enc floats of which only columns 1024..1055 (the intrinsics, written by mv2d_frame_geometry) are
+ * read; enc[:, :1024], enc1 and enc2 stay on chip and are NOT written.  The weights are the (hi, lo) fragment-major pairs the four
+ * entries take (fc [1024,256], e0 [512,1056], e2 [256,512], W0 [256,384], W2 [256,256]); Wc [3,256], bc [3], minv [R,16], dim_t [128]
+ * fp32; pc_range: host array of 6.  Rows >= R of the outputs are not touched. */
+int mv2d_qg_tail_x3(const float* x2, const float* enc, int ld_enc, const void* fc_hi, const void* fc_lo, const float* fc_b,
+                    const void* e0_hi, const void* e0_lo, const float* e0_b, const void* e2_hi, const void* e2_lo, const float* e2_b,
+                    const float* Wc, const float* bc, const float* minv, const float* dim_t, const float* pc_range, const void* W0_hi,
+                    const void* W0_lo, const float* b0, const void* W2_hi, const void* W2_lo, const float* b2, float* center, float* xyz,
+                    float* ref, float* posemb, float* qpos, int R, void* stream);
+
 /* FFN tail + the next layer's self-attention in_proj, row-fused: y = LN(sum_z parts[z] + b2 + resid); x_out = y; xq_out = y + qpos (may be NULL);
  * outs = post_norm(y) (optional); qkv [M,768] = [xq.Wq^T + bq | xq.Wk^T + bk | y.Wv^T + bv] in bf16x3 split precision (optional:
  * Win_hi = null for the last layer).  Win_hi / Win_lo: nn.MultiheadAttention in_proj_weight [768,256] as a bf16 hi/lo pair

@@ -56,6 +56,7 @@ SIGNATURES = {
     'mv2d_attn_out_fused': (I, [P, P, P, P, P, P, P, P, P, P, F, P, I, F, P]),
     'mv2d_sa_block_fused_x3': (I, [P, P, P, P, P, P, P, P, P, P, P, P, F, P, I, F, P]),
     'mv2d_query_embed_fused_x3': (I, [P] * 17 + [I, P]),
+    'mv2d_qg_tail_x3': (I, [P, P, I] + [P] * 25 + [I, P]),
     'mv2d_ffn_out_fused_x3': (I, [P, I, LL, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I, F, P]),
     'mv2d_attn_out_fused_x3': (I, [P, P, P, P, P, P, P, P, P, P, P, P, F, P, I, F, P]),
     'mv2d_pack_wfrag_f32': (I, [P, P, I, I, I, P]),

@@ -173,6 +173,12 @@ class HeadEngine:
         w['qg_c_w'], w['qg_c_b'] = g(q + 'fc_center.weight'), g(q + 'fc_center.bias')
         # LDS-tiled bf16x3 linears (mv2d_linear_x3)
         w['qg_fc_wx'], w['qg_e0_wx'], w['qg_e2_wx'] = ops.pack_x3(g(q + 'shared_fcs.0.weight')), ops.pack_x3(e0p), ops.pack_x3(g(q + 'extra_enc.2.weight'))
+        # the one-launch tail (mv2d_qg_tail_x3) is built for the shipped dimensions: 256 -> 1024, + 16 intrinsics columns (32 with the pad) -> 512 -> 256,
+        # query_embedding 384 -> 256 -> 256; anything else keeps the four launches
+        shp = lambda k: tuple(sd[k].shape)
+        self._qg_tail_dims = (shp(q + 'shared_fcs.0.weight') == (1024, C) and shp(q + 'extra_enc.0.weight') == (512, 1040)
+                              and shp(q + 'extra_enc.2.weight') == (C, 512) and shp(q + 'fc_center.weight') == (3, C)
+                              and shp('bbox_head.query_embedding.0.weight') == (C, 384) and shp('bbox_head.query_embedding.2.weight') == (C, C))
         pe = 'position_encoding.'
         # (position_encoder.0.weight with its K zero-padded to Kp: the padded frustum rows meet zero columns)
         c1 = lambda k: ops.pad_pe_w1a(g(pe + k)) if k == 'position_encoder.0.weight' else g(pe + k).flatten(1).contiguous()
@@ -729,6 +735,13 @@ class HeadEngine:
         else:
             o.qg_conv_pool(ws['roi_feat'], W_['qg_conv_wp'], W_['qg_conv_b'], ws['x2'], R=R, roi_size=self.roi_size)
         tk('qg_rest')
+        rt = ws['route']
+        if rt.qg_tail_fused and self._qg_tail_dims and not rt.keep_sine_rows:
+            # the three linears and the query-embedding kernel below as one launch (bitwise the same outputs; enc[:, :1024], enc1, enc2 are not written)
+            o.qg_tail_x3(ws['x2'], ws['enc'], W_['qg_fc_wx'], W_['qg_fc_b'], W_['qg_e0_wx'], W_['qg_e0_b'], W_['qg_e2_wx'], W_['qg_e2_b'],
+                         W_['qg_c_w'], W_['qg_c_b'], ws['minv'], self.const['dim_t'], self.pc_range_h, W_['qe_w0x'], W_['qe_b0'], W_['qe_w2x'],
+                         W_['qe_b2'], ws['center'], ws['xyz'], ws['ref'], ws['posemb'], ws['qpos'], R=R)
+            return
         o.linear_x3(ws['x2'], W_['qg_fc_wx'], W_['qg_fc_b'], N=1024, K=256, act=1, clamp=5e3, out=ws['enc'], ldc=1056, M=R)
         o.linear_x3(ws['enc'], W_['qg_e0_wx'], W_['qg_e0_b'], N=512, K=1056, act=1, out=ws['enc1'], M=R)
         o.linear_x3(ws['enc1'], W_['qg_e2_wx'], W_['qg_e2_b'], N=256, K=512, act=1, out=ws['enc2'], M=R)

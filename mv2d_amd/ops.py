@@ -249,6 +249,19 @@ def query_embed_fused_x3(enc2, Wc, bc, minv, dim_t, pc_range_host, W0_x3, b0, W2
     return qpos
 
 
+def qg_tail_x3(x2, enc, fc_x3, fc_b, e0_x3, e0_b, e2_x3, e2_b, Wc, bc, minv, dim_t, pc_range_host, W0_x3, b0, W2_x3, b2, center, xyz, ref,
+               posemb, qpos, R=None):
+    """linear_x3 (256 -> 1024, ReLU, clamp 5e3) -> linear_x3 (1056 -> 512, ReLU) -> linear_x3 (512 -> 256, ReLU) -> query_embed_fused_x3 in one
+    launch, bitwise the four; ``enc`` [R, >= 1056]: only its columns 1024..1055 are read, the hidden layers are not written."""
+    _req(x2, torch.float32, 'x2'); _req(enc, torch.float32, 'enc')
+    R = x2.shape[0] if R is None else R
+    check(_lib.load().mv2d_qg_tail_x3(_p(x2), _p(enc), enc.stride(0), _p(fc_x3[0]), _p(fc_x3[1]), _p(fc_b), _p(e0_x3[0]), _p(e0_x3[1]), _p(e0_b),
+                                      _p(e2_x3[0]), _p(e2_x3[1]), _p(e2_b), _p(Wc), _p(bc), _p(minv), _p(dim_t), pc_range_host.data_ptr(),
+                                      _p(W0_x3[0]), _p(W0_x3[1]), _p(b0), _p(W2_x3[0]), _p(W2_x3[1]), _p(b2), _p(center), _p(xyz), _p(ref),
+                                      _p(posemb), _p(qpos), R, _stream()), 'mv2d_qg_tail_x3')
+    return qpos
+
+
 def ffn_out_fused_x3(parts, b2, resid, ln, post, x_out, qpos, xq_out, outs=None, Win_x3=None, b_in=None, qkv=None, M=None, eps=1e-5):
     """y = LN(sum(parts) + b2 + resid) -> x_out, xq_out = y + qpos, outs = post_norm(y); qkv = in_proj(xq, xq, y) (bf16x3)."""
     M = x_out.shape[0] if M is None else M

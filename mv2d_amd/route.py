@@ -16,7 +16,8 @@ def default_options():
         fork_qg=True, fuse_maps={'0': False, '1': True}.get(env('MV2D_FUSE_MAPS', ''), None), fuse_xattn=None, group_xattn=None,
         xattn_waves=int(env('MV2D_XATTN_WAVES', '2')), q_order=True, fold_sa0=True, masked_transpose=True, last_stage_heads=False,
         exact_skip=frozenset({'conv'}), lo8_rows=True, pe_at_positions=env('MV2D_PE_AT_POS', '1') != '0', pe_rows_in_waves=False,
-        ablate_zero_lo=frozenset(), keep_sine_rows=False, stop_before_decoder=False, force_nc=None, debug_attn=False)
+        ablate_zero_lo=frozenset(), keep_sine_rows=False, stop_before_decoder=False, force_nc=None, debug_attn=False,
+        fuse_qg_tail=env('MV2D_QG_TAIL', '1') != '0')
 
 
 OPTIONS = tuple(default_options())
@@ -118,6 +119,11 @@ class Route(NamedTuple):
     # experiments only (tools/ablate_exact.py; needs lo8_rows = False): zero the lo halves of the value / key rows after they were written --
     # what a route with hi-only value (or key) rows would compute, at the full route's cost
     ablate_zero_lo: frozenset
+    # option fuse_qg_tail: the query generator's MLP tail (shared_fcs.0 -> extra_enc.0 -> extra_enc.2) and the query-embedding kernel run as ONE
+    # launch (csrc/qg_tail.hip: the hidden layers stay in LDS, the weights stream through a register ring; BITWISE the four launches it
+    # replaces).  Not for keep_stages runs (they expose enc, which the launch does not write); the engine also keeps the four launches for
+    # the training route and for weights of other than the shipped dimensions.  MV2D_QG_TAIL=0 turns it off (A/B runs).
+    qg_tail_fused: bool
 
     @property
     def storage(self):
@@ -160,4 +166,5 @@ def resolve(opts, kind, exact, depth_num, map_dtype=torch.float32, keep_stages=F
         fuse_maps=o.fuse_maps, xattn_waves=int(o.xattn_waves), fold_sa0=bool(o.fold_sa0), forked=forked,
         masked=bool(o.masked_transpose) and not forked and not o.keep_sine_rows and not stages,
         last_stage_heads=bool(o.last_stage_heads) and not stages, debug_attn=debug, stop_before_decoder=bool(o.stop_before_decoder),
-        force_nc=o.force_nc, ablate_zero_lo=frozenset(o.ablate_zero_lo) if exact else frozenset())
+        force_nc=o.force_nc, ablate_zero_lo=frozenset(o.ablate_zero_lo) if exact else frozenset(),
+        qg_tail_fused=bool(o.fuse_qg_tail) and not stages)
