@@ -172,6 +172,18 @@ int mv2d_qg_conv_pool_s(const void* roi_feat, const void* W, const float* bias, 
 int mv2d_qg_conv_pool_x3_s(const void* roi_feat_hi, const void* roi_feat_lo, const void* W_hi, const void* W_lo, const float* bias, float* out,
                            int ld_out, int R, int roi_size, void* stream);
 
+/* Query-generator trunks other than the shipped one (csrc/roiconv_cells.hip).  The same conv3x3 + bias + ReLU on the s x s cells of R RoIs,
+ * 1 <= roi_size <= 14, that WRITES the cells instead of pooling them: out_hi (+ out_lo: x ~ hi + lo) key16 [R, s*s, 256] for a following conv,
+ * and / or out_f32 [R, s*s, 256] fp32 (the cell-major flattening the first fc of an un-pooled trunk reads).  Each output may be null, not all of
+ * them; out_lo needs out_hi.  Operands as for mv2d_qg_conv_pool_s / mv2d_qg_conv_pool_x3_s. */
+int mv2d_qg_conv_cells(const void* roi_feat, const void* W, const float* bias, void* out_hi, void* out_lo, float* out_f32, int R, int roi_size,
+                       void* stream);
+int mv2d_qg_conv_cells_x3(const void* roi_feat_hi, const void* roi_feat_lo, const void* W_hi, const void* W_lo, const float* bias, void* out_hi,
+                          void* out_lo, float* out_f32, int R, int roi_size, void* stream);
+/* out[r * ld_out + c] (fp32, ld_out >= 256) = mean over the key16 rows r * cells .. r * cells + cells - 1 of hi (+ lo unless null), 256 channels,
+ * 1 <= cells <= 196: AvgPool2d(s) of RoI cells (cells = s * s), or their fp32 copy (cells = 1, R = all rows). */
+int mv2d_avgpool_cells(const void* hi, const void* lo, float* out, int ld_out, int R, int cells, void* stream);
+
 /* The same chain in split precision (bf16x3, ~1e-5 relative): Wo / Wq as bf16 hi/lo pairs (mv2d_split_bf16x2), each in the
  * fragment-major order of mv2d_pack_wfrag_bf16. */
 int mv2d_attn_out_fused_x3(const float* ctx, const float* resid, const void* Wo_hi, const void* Wo_lo, const float* bo,

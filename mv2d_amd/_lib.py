@@ -51,6 +51,9 @@ SIGNATURES = {
     'mv2d_qg_conv_pool_x3': (I, [P, P, P, P, P, P, I, I, P]),
     'mv2d_qg_conv_pool_s': (I, [P, P, P, P, I, I, I, P]),
     'mv2d_qg_conv_pool_x3_s': (I, [P, P, P, P, P, P, I, I, I, P]),
+    'mv2d_qg_conv_cells': (I, [P, P, P, P, P, P, I, I, P]),
+    'mv2d_qg_conv_cells_x3': (I, [P, P, P, P, P, P, P, P, I, I, P]),
+    'mv2d_avgpool_cells': (I, [P, P, P, I, I, I, P]),
     'mv2d_pack_wfrag_bf16': (I, [P, P, I, I, P]),
     'mv2d_gemm_f32': (I, [P, P, I, P, P, I, I, I, I, I, I, I, F, F, P, I, I, LL, I, LL, LL, LL, LL, P]),
     'mv2d_attn_out_fused': (I, [P, P, P, P, P, P, P, P, P, P, F, P, I, F, P]),

@@ -103,6 +103,14 @@ def _set_pe_depth(d, depth_num, depth_start, position_range):
     return d
 
 
+def _set_query_generator(d, query_generator):
+    # keys of the reference QueryGenerator (RH/utils/query_generator.py:20-67) laid over the shipped subtree: num_shared_convs, num_shared_fcs,
+    # num_center_fcs, fc_out_channels, with_avg_pool, extra_encoding (replaced as a whole).  None leaves the shipped subtree as it is
+    if query_generator:
+        d['query_generator'].update(copy.deepcopy(dict(query_generator)))
+    return d
+
+
 def _set_reg_layer(d, group_reg_dims):
     # ``bbox_head.use_reg_layer`` / ``group_reg_dims`` of the reference head; None leaves the shipped Sequential regression branches (no key added)
     if group_reg_dims is not None:
@@ -110,25 +118,26 @@ def _set_reg_layer(d, group_reg_dims):
     return d
 
 
-def roi_head_cfg_s(num_classes=10, roi_size=ROI_SIZE, reg_layer_dims=None, depth_num=64, depth_start=1, position_range=None):
+def roi_head_cfg_s(num_classes=10, roi_size=ROI_SIZE, reg_layer_dims=None, depth_num=64, depth_start=1, position_range=None, query_generator=None):
     """CFG-S:40-121 (MV2D-S single frame); ``num_classes`` sets ``bbox_head.num_classes`` and ``bbox_head.bbox_coder.num_classes``,
     ``roi_size`` sets ``bbox_roi_extractor.roi_layer.output_size`` and ``query_generator.roi_feat_size``; ``reg_layer_dims`` (a tuple of
     group widths) sets ``bbox_head.use_reg_layer=True`` with that ``group_reg_dims``; ``depth_num`` (a multiple of 8 in [8, 80]), ``depth_start``
-    and ``position_range`` (None: the shipped POST_RANGE) set the keys of the same names in ``pe``."""
+    and ``position_range`` (None: the shipped POST_RANGE) set the keys of the same names in ``pe``; ``query_generator`` (a dict of the reference
+    QueryGenerator's own keys: mv2d_amd/qg_shape.py lists the accepted values) is laid over the ``query_generator`` subtree."""
     d = dict(type='MV2DSHead', use_denoise=False)
     d.update(_common(with_cp=False))
     d['box_correlation'] = dict(correlation_mode='topk_matched:1:0.0:0.0')
-    d = _set_pe_depth(d, depth_num, depth_start, position_range)
+    d = _set_query_generator(_set_pe_depth(d, depth_num, depth_start, position_range), query_generator)
     return copy.deepcopy(_set_reg_layer(_set_roi_size(_set_num_classes(d, num_classes), roi_size), reg_layer_dims))
 
 
-def roi_head_cfg_t(num_classes=10, roi_size=ROI_SIZE, reg_layer_dims=None, depth_num=64, depth_start=1, position_range=None):
-    """CFG-T:40-125 (MV2D-T two frames); ``num_classes``, ``roi_size``, ``reg_layer_dims`` and the three ``pe`` keys as in ``roi_head_cfg_s``."""
+def roi_head_cfg_t(num_classes=10, roi_size=ROI_SIZE, reg_layer_dims=None, depth_num=64, depth_start=1, position_range=None, query_generator=None):
+    """CFG-T:40-125 (MV2D-T two frames); ``num_classes``, ``roi_size``, ``reg_layer_dims``, the three ``pe`` keys and ``query_generator`` as in ``roi_head_cfg_s``."""
     d = dict(type='MV2DTHead', use_denoise=True, neg_bbox_loss=True,
              denoise_noise_scale=1.25, denoise_split=0.6)
     d.update(_common(with_cp=True))
     d['box_correlation'] = dict(expand_stride=2, correlation_mode='topk_matched:20:0.0:0.0')
-    d = _set_pe_depth(d, depth_num, depth_start, position_range)
+    d = _set_query_generator(_set_pe_depth(d, depth_num, depth_start, position_range), query_generator)
     return copy.deepcopy(_set_reg_layer(_set_roi_size(_set_num_classes(d, num_classes), roi_size), reg_layer_dims))
 
 

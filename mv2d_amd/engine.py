@@ -21,7 +21,7 @@ import os
 import numpy as np
 import torch
 
-from . import calib, ops, route
+from . import calib, ops, qg_shape, route
 
 BF16 = torch.bfloat16
 F32 = torch.float32
@@ -49,7 +49,7 @@ class HeadEngine:
                  max_num=300, pc_range=(-51.2, -51.2, -5.0, 51.2, 51.2, 3.0),
                  post_range=(-61.2, -61.2, -10.0, 61.2, 61.2, 10.0), depth_num=64, stride=16, col_cap_per_query=2048,
                  iou_thr=0.0, ratio=0.0, masked_row='nan', exact=None, num_classes=10, roi_size=7, use_reg_layer=False,
-                 group_reg_dims=(2, 2, 1, 1, 2, 2), depth_start=1, position_range=None):
+                 group_reg_dims=(2, 2, 1, 1, 2, 2), depth_start=1, position_range=None, query_generator=None):
         assert kind in ('S', 'T')
         self.kind = kind
         self.dev = torch.device(device)
@@ -66,6 +66,9 @@ class HeadEngine:
         if self.roi_size != roi_size or not 1 <= self.roi_size <= 14:
             raise ValueError(f'HeadEngine: roi_size must be an int in [1, 14], got {roi_size}')
         self.cells = self.roi_size * self.roi_size
+        # the query generator's shape: a dict of the reference QueryGenerator's own config keys (mv2d_amd/qg_shape.py lists what is accepted; None =
+        # the shipped shape, which allocates and launches exactly what it always did).  Fixed per engine: the state dict has to agree (load_state).
+        self.qg = qg_shape.parse(query_generator, 'HeadEngine')
         # the regression branches as the reference's RegLayer (CrossAttentionBoxHead(use_reg_layer=True): two shared linears, one task head per
         # entry of group_reg_dims) -- mv2d_reg_layer_x3 next to the class-only launch of the fused branches.  Fixed per engine: the state dict's
         # key layout has to agree (load_state), and it is part of the graph key.
@@ -97,6 +100,10 @@ class HeadEngine:
         # the route they resolve to).  Names, defaults and what each one does: mv2d_amd/route.py.  The only other environment variable the engine
         # reads is MV2D_EXACT (route.Route.exact).
         self.__dict__.update(route.default_options())
+        if not self.qg.is_default:
+            # other query-generator shapes chain their convs cell to cell: on the index-exact route they run in split precision (the shipped shape
+            # keeps its key16 conv there by default: exact_skip = {'conv'}); with 'conv' put back into exact_skip the engine refuses the frame
+            self.exact_skip = self.exact_skip - {'conv'}
         # adapt_pos3d(sine) (MU/pe.py:164-166) depends only on the weights and on the padding geometry of the rig, not on features, boxes
         # or calibration: it is constant-folded into a per-(weights version, geometry) table that the fused PE kernel adds in its epilogue
         self._weights_version = 0     # bumped by every load_state(): invalidates whatever was folded from the weights
@@ -162,23 +169,28 @@ class HeadEngine:
             for n in ('0', '2', '4'):
                 w[f'reg_w{n}'], w[f'reg_b{n}'] = st(rb + '{}.' + n + '.weight'), st(rb + '{}.' + n + '.bias')
         q = 'query_generator.'
-        conv = g(q + 'shared_convs.0.conv.weight').permute(0, 2, 3, 1).reshape(C, 9 * C).contiguous()       # [256,256,3,3] -> [out][tap][cin]
-        w['qg_conv_wp'] = k16(conv)                                                   # key16, fragment-major: the fused conv kernel
-        w['qg_conv_b'] = g(q + 'shared_convs.0.conv.bias')
-        w['qg_fc_b'] = g(q + 'shared_fcs.0.bias')
-        e0 = g(q + 'extra_enc.0.weight')                                              # [512,1040] -> K padded to 1056
-        e0p = torch.zeros((e0.shape[0], 1056), device=d, dtype=F32)
-        e0p[:, :e0.shape[1]] = e0
-        w['qg_e0_b'], w['qg_e2_b'] = g(q + 'extra_enc.0.bias'), g(q + 'extra_enc.2.bias')
-        w['qg_c_w'], w['qg_c_b'] = g(q + 'fc_center.weight'), g(q + 'fc_center.bias')
-        # LDS-tiled bf16x3 linears (mv2d_linear_x3)
-        w['qg_fc_wx'], w['qg_e0_wx'], w['qg_e2_wx'] = ops.pack_x3(g(q + 'shared_fcs.0.weight')), ops.pack_x3(e0p), ops.pack_x3(g(q + 'extra_enc.2.weight'))
-        # the one-launch tail (mv2d_qg_tail_x3) is built for the shipped dimensions: 256 -> 1024, + 16 intrinsics columns (32 with the pad) -> 512 -> 256,
-        # query_embedding 384 -> 256 -> 256; anything else keeps the four launches
-        shp = lambda k: tuple(sd[k].shape)
-        self._qg_tail_dims = (shp(q + 'shared_fcs.0.weight') == (1024, C) and shp(q + 'extra_enc.0.weight') == (512, 1040)
-                              and shp(q + 'extra_enc.2.weight') == (C, 512) and shp(q + 'fc_center.weight') == (3, C)
-                              and shp('bbox_head.query_embedding.0.weight') == (C, 384) and shp('bbox_head.query_embedding.2.weight') == (C, C))
+        self.qg.check_state(sd, self.roi_size, 'HeadEngine')
+        if not self.qg.is_default:
+            self._qg_tail_dims = False
+            self._load_qg_shape(g, w)
+        else:
+            conv = g(q + 'shared_convs.0.conv.weight').permute(0, 2, 3, 1).reshape(C, 9 * C).contiguous()       # [256,256,3,3] -> [out][tap][cin]
+            w['qg_conv_wp'] = k16(conv)                                                   # key16, fragment-major: the fused conv kernel
+            w['qg_conv_b'] = g(q + 'shared_convs.0.conv.bias')
+            w['qg_fc_b'] = g(q + 'shared_fcs.0.bias')
+            e0 = g(q + 'extra_enc.0.weight')                                              # [512,1040] -> K padded to 1056
+            e0p = torch.zeros((e0.shape[0], 1056), device=d, dtype=F32)
+            e0p[:, :e0.shape[1]] = e0
+            w['qg_e0_b'], w['qg_e2_b'] = g(q + 'extra_enc.0.bias'), g(q + 'extra_enc.2.bias')
+            w['qg_c_w'], w['qg_c_b'] = g(q + 'fc_center.weight'), g(q + 'fc_center.bias')
+            # LDS-tiled bf16x3 linears (mv2d_linear_x3)
+            w['qg_fc_wx'], w['qg_e0_wx'], w['qg_e2_wx'] = ops.pack_x3(g(q + 'shared_fcs.0.weight')), ops.pack_x3(e0p), ops.pack_x3(g(q + 'extra_enc.2.weight'))
+            # the one-launch tail (mv2d_qg_tail_x3) is built for the shipped dimensions: 256 -> 1024, + 16 intrinsics columns (32 with the pad) -> 512 -> 256,
+            # query_embedding 384 -> 256 -> 256; anything else keeps the four launches
+            shp = lambda k: tuple(sd[k].shape)
+            self._qg_tail_dims = (shp(q + 'shared_fcs.0.weight') == (1024, C) and shp(q + 'extra_enc.0.weight') == (512, 1040)
+                                  and shp(q + 'extra_enc.2.weight') == (C, 512) and shp(q + 'fc_center.weight') == (3, C)
+                                  and shp('bbox_head.query_embedding.0.weight') == (C, 384) and shp('bbox_head.query_embedding.2.weight') == (C, C))
         pe = 'position_encoding.'
         # (position_encoder.0.weight with its K zero-padded to Kp: the padded frustum rows meet zero columns)
         c1 = lambda k: ops.pad_pe_w1a(g(pe + k)) if k == 'position_encoder.0.weight' else g(pe + k).flatten(1).contiguous()
@@ -205,7 +217,8 @@ class HeadEngine:
             # first-layer weights with their rows in the order csrc/pe_x3b.hip chains the two layers in registers with
             w['pe_x3']['w1a_p'] = ops.pack_x3_rowperm(c1('position_encoder.0.weight'))
             w['pe_x3']['wr_p'] = ops.pack_x3_rowperm(c1('fpe.conv_reduce.weight'))
-            w['qg_conv_wx3'] = ops.pack_key16_x3(conv)
+            if self.qg.is_default:
+                w['qg_conv_wx3'] = ops.pack_key16_x3(conv)
         self.w = w
         for k in ('cls_w0', 'cls_w3') + (() if self.use_reg_layer else ('reg_w0', 'reg_w2')):   # [L,256,256] -> bf16x3, fragment-major, stacked over L
             w[k + 'x'] = ops.pack_x3_stack(w[k])
@@ -219,6 +232,41 @@ class HeadEngine:
         ll = self.L - 1
         self._last_cls, self._last_reg = [t[ll:] for t in cls_t], [t[ll:] for t in reg_t]
         self.cls_ptrs_x3_last, self.reg_ptrs_x3_last = ops.make_ptr_array(self._last_cls), ops.make_ptr_array(self._last_reg)
+
+    def _load_qg_shape(self, g, w):
+        """Packed weights and the launch plan of a query generator of other than the shipped shape (self.qg): w['qg_convs'] = [(key16 hi / lo
+        fragment-major weight pair, bias)] per shared conv, w['qg_lin'] = the linears up to fc_center in execution order, each a dict(wx, b, N, K,
+        src, dst, ldc, clamp) over workspace buffer names.  K is zero-padded to a multiple of 32 (every activation buffer has that many zeroed
+        columns), the first fc of an un-pooled trunk gets its columns in the engine's cell-major order."""
+        qs, q, s, d = self.qg, 'query_generator.', self.roi_size, self.dev
+        p32 = qg_shape.pad32
+        w['qg_convs'] = []
+        for i in range(qs.convs):
+            cw = g(q + f'shared_convs.{i}.conv.weight').permute(0, 2, 3, 1).reshape(C, 9 * C).contiguous()          # [out][tap][cin]
+            w['qg_convs'].append((ops.pack_key16_x3(cw), g(q + f'shared_convs.{i}.conv.bias')))
+
+        def padded(W, n_to=None):
+            Wp = torch.zeros((n_to or W.shape[0], p32(W.shape[1])), device=d, dtype=F32)
+            Wp[:W.shape[0], :W.shape[1]] = W
+            return Wp
+        lin, src, bufs = [], 'x2' if qs.pooled else 'qg_flat', {}
+        for name, n, k, _ in qs.linears(s)[:-1]:
+            W = g(q + name + '.weight')
+            if name == 'shared_fcs.0' and not qs.pooled:
+                W = W[:, qg_shape.flatten_perm(s, d)].contiguous()
+            last_fc = name == f'shared_fcs.{qs.fcs - 1}'
+            dst = 'enc' if last_fc else 'qg_' + name.replace('.', '_')
+            width = p32(qs.enc_in) if last_fc else p32(n)
+            bufs[dst] = width
+            lin.append(dict(wx=ops.pack_x3(padded(W)), b=g(q + name + '.bias'), N=n, K=p32(k), src=src, dst=dst, ldc=width, clamp=5e3 if last_fc else 0.0))
+            src = dst
+        w['qg_lin'], w['qg_bufs'], w['qg_last'] = lin, bufs, src
+        w['qg_c_w'], w['qg_c_b'] = g(q + 'fc_center.weight'), g(q + 'fc_center.bias')
+        if qs.center_in != C:
+            # fc_center on the tile linear: 3 output rows padded to one column tile of 16
+            w['qg_c_wx'] = ops.pack_x3(padded(w['qg_c_w'], 16))
+            w['qg_c_b16'] = torch.zeros(16, device=d, dtype=F32)
+            w['qg_c_b16'][:3] = w['qg_c_b']
 
     @staticmethod
     def check_reg_layout(sd, use_reg_layer, group_reg_dims):
@@ -324,9 +372,30 @@ class HeadEngine:
         K16 = self.K16
         NC = self.cells                                  # RoI cells (s x s)
         ws['featcl'] = e((P, C), map_dtype)               # position-major feature map in the INPUT's dtype (fp32 / fp16 / bf16): its readers widen in registers
-        ws['enc'] = z((R, 1056)); ws['minv'] = e((R, 16))
+        qs = self.qg
+        ws['enc'] = z((R, 1056 if qs.is_default else qg_shape.pad32(qs.enc_in))); ws['minv'] = e((R, 16))
         ws['roi_feat'] = e((R, NC, C), K16)
-        ws['enc1'] = e((R, 512)); ws['enc2'] = e((R, C)); ws['center'] = e((R, 3))
+        if qs.is_default:
+            ws['enc1'] = e((R, 512)); ws['enc2'] = e((R, C)); ws['center'] = e((R, 3))
+            ws['intr'], ws['ld_intr'] = ws['enc'][:, 1024:], 1056
+        else:
+            # buffers of the shape's launch plan (_load_qg_shape): zeroed, so that the pad columns behind a width that is no multiple of 32 stay 0
+            for name, width in self.w['qg_bufs'].items():
+                if name != 'enc':
+                    ws[name] = z((R, width))
+            for i in range(min(max(qs.convs - 1, 0), 2)):                  # cells between two convs: key16 hi + lo, ping-pong
+                ws[f'qg_cells_hi{i}'] = e((R, NC, C), K16); ws[f'qg_cells_lo{i}'] = e((R, NC, C), K16)
+            if not qs.pooled:
+                ws['qg_flat'] = e((R, NC * C))                              # the cell-major flattening the first fc reads
+            if qs.center_in != C:
+                ws['qg_center16'] = e((R, 16))
+                ws['center'] = ws['qg_center16'][:, :3]
+            else:
+                ws['center'] = e((R, 3))
+            if qs.intrinsic:
+                ws['intr'], ws['ld_intr'] = ws['enc'][:, qs.fc_out:], ws['enc'].shape[1]
+            else:
+                ws['intr'], ws['ld_intr'] = e((R, 16)), 16                  # the per-RoI camera kernel writes them; nothing reads them
         ws['xyz'] = e((R, 3)); ws['ref'] = e((R, 3)); ws['posemb'] = e((R, 384)); ws['qe1'] = e((R, C)); ws['qpos'] = e((R, C))
         ws['match'] = e((R, Vg, self.topk), torch.int32)
         Pp = (P + 15) // 16 * 16
@@ -574,7 +643,7 @@ class HeadEngine:
         tk('box_params'); tk('box_corr')
         # a3/a5/a7 per-RoI camera + a9 epipolar correlation (both independent of the features) + the clearing of the frame's mask / flag
         # bytes: one launch (round 4; a one-sample frame is bound by its NUMBER of kernels)
-        o.frame_geometry(rois, T['viewK'], T['viewE'], ws['enc'][:, 1024:], 1056, ws['minv'], ws['view_start'], T['trans'], self.const['lin'],
+        o.frame_geometry(rois, T['viewK'], T['viewE'], ws['intr'], ws['ld_intr'], ws['minv'], ws['view_start'], T['trans'], self.const['lin'],
                          self.const['depths'], ws['match'], Vg, self.topk, sc['pad_h'], sc['pad_w'], sc['max_per_view'], iou_thr=self.iou_thr,
                          ratio=self.ratio, zero=ws['zbuf'], roi_size=float(self.roi_size))
         tk('csr')
@@ -728,6 +797,8 @@ class HeadEngine:
     def _enqueue_qg(self, ws, R):
         """a6-a8, a13: QueryGenerator on the RoI features -> reference points -> query positional embedding."""
         o, W_, tk = ops, self.w, self._tick
+        if not self.qg.is_default:
+            return self._enqueue_qg_shape(ws, R)
         # a6: QueryGenerator: conv3x3 + ReLU + AvgPool2d(s) fused, one block per RoI (index-exact route: in split precision on the hi + lo cells)
         tk('qg_conv_gemm')
         if ws['route'].conv_x3:
@@ -748,6 +819,42 @@ class HeadEngine:
         # fc_center + reference points (a7/a8) + pos2posemb3d + query_embedding (a13) in one row-fused kernel
         o.query_embed_fused_x3(ws['enc2'], W_['qg_c_w'], W_['qg_c_b'], ws['minv'], self.const['dim_t'], self.pc_range_h, W_['qe_w0x'],
                                W_['qe_b0'], W_['qe_w2x'], W_['qe_b2'], ws['center'], ws['xyz'], ws['ref'], ws['posemb'], ws['qpos'], R=R)
+
+    def _enqueue_qg_shape(self, ws, R):
+        """_enqueue_qg for a query generator of other than the shipped shape (index-exact route: the cells are key16 hi + lo pairs).  Trunk: every
+        shared conv but the last writes its cells for the next one (mv2d_qg_conv_cells_x3); the last one is the fused conv + AvgPool launch of the
+        shipped shape, or writes the fp32 cell-major rows the first fc reads (with_avg_pool=False); without convs the RoI cells are pooled /
+        widened by mv2d_avgpool_cells.  Then the plan's linears on mv2d_linear_x3, and fc_center + reference points + query embedding: the row-fused
+        kernel when fc_center reads 256 columns, the tile linear + mv2d_refpoint_posemb + two linears otherwise."""
+        o, W_, tk, qs, s = ops, self.w, self._tick, self.qg, self.roi_size
+        tk('qg_conv_gemm')
+        hi, lo = ws['roi_feat'], ws['roi_lo']
+        for i, (wx3, b) in enumerate(W_['qg_convs']):
+            if i < qs.convs - 1:
+                nh, nl = ws[f'qg_cells_hi{i & 1}'], ws[f'qg_cells_lo{i & 1}']
+                o.qg_conv_cells(hi, lo, wx3, b, out_hi=nh, out_lo=nl, R=R, roi_size=s)
+                hi, lo = nh, nl
+            elif qs.pooled:
+                o.qg_conv_pool_x3(hi, lo, wx3, b, ws['x2'], R=R, roi_size=s)
+            else:
+                o.qg_conv_cells(hi, lo, wx3, b, out_f32=ws['qg_flat'], R=R, roi_size=s)
+        if qs.convs == 0:
+            if qs.pooled:
+                o.avgpool_cells(hi, lo, ws['x2'], R, self.cells)
+            else:
+                o.avgpool_cells(hi, lo, ws['qg_flat'].view(R * self.cells, C), R * self.cells, 1)
+        tk('qg_rest')
+        for l in W_['qg_lin']:
+            o.linear_x3(ws[l['src']], l['wx'], l['b'], N=l['N'], K=l['K'], act=1, clamp=l['clamp'], out=ws[l['dst']], ldc=l['ldc'], M=R)
+        last = ws[W_['qg_last']]
+        if qs.center_in == C:
+            o.query_embed_fused_x3(last, W_['qg_c_w'], W_['qg_c_b'], ws['minv'], self.const['dim_t'], self.pc_range_h, W_['qe_w0x'],
+                                   W_['qe_b0'], W_['qe_w2x'], W_['qe_b2'], ws['center'], ws['xyz'], ws['ref'], ws['posemb'], ws['qpos'], R=R)
+            return
+        o.linear_x3(last, W_['qg_c_wx'], W_['qg_c_b16'], N=16, K=last.shape[1], out=ws['qg_center16'], M=R)
+        o.refpoint_posemb(ws['qg_center16'], 16, ws['minv'], self.const['dim_t'], ws['xyz'], ws['ref'], ws['posemb'], R, self.pc_range_h)
+        o.linear_x3(ws['posemb'], W_['qe_w0x'], W_['qe_b0'], N=C, K=384, act=1, out=ws['qe1'], M=R)
+        o.linear_x3(ws['qe1'], W_['qe_w2x'], W_['qe_b2'], N=C, K=C, out=ws['qpos'], M=R)
 
     def _enqueue_decoder(self, ws, R):
         """CrossAttentionBoxHead.forward's transformer call on already-prepared inputs (qpos, key / value rows, CSR):
@@ -884,6 +991,9 @@ class HeadEngine:
         if any(f.dtype != map_dtype for f in fl):
             raise ValueError(f'mv2d engine: the feature maps of a batch must share one dtype, got {sorted({str(f.dtype) for f in fl})}')
         rt = route.resolve(self, self.kind, self.exact, self.depth_num, map_dtype, keep_stages, use_graph)     # (ValueError for impossible combinations)
+        if not self.qg.is_default and not rt.conv_x3:
+            raise ValueError('mv2d engine: a query generator of other than the shipped shape runs on the index-exact route only (exact=True, the default, '
+                             "without 'conv' in exact_skip): the engine has no key16-mode plan for " + repr(tuple(self.qg)))
         if stacked or B == 1:
             feat = fl[0]
             if not (feat.is_contiguous(memory_format=torch.channels_last) and not feat.is_contiguous()):

@@ -667,6 +667,53 @@ def qg_conv_pool_x3(roi_hi, roi_lo, W_x3, bias, out, R=None, ld_out=None, roi_si
     return out
 
 
+def qg_conv_cells(roi_hi, roi_lo, W, bias, out_hi=None, out_lo=None, out_f32=None, R=None, roi_size=7):
+    """conv3x3 + bias + ReLU per RoI that writes its cells (csrc/roiconv_cells.hip): roi_hi [R,s*s,256] key16 (+ roi_lo: the split-precision form,
+    W = pack_key16_x3(conv weight [256,2304]); roi_lo None: the key16 form, W = pack_key16(...)).  Outputs: out_hi / out_lo key16 [R,s*s,256] and / or
+    out_f32 [R,s*s,256]."""
+    _req16(roi_hi, 'roi_hi'); _req16(roi_lo, 'roi_lo'); _req(bias, torch.float32, 'bias')
+    _req16(out_hi, 'out_hi'); _req16(out_lo, 'out_lo'); _req(out_f32, torch.float32, 'out_f32')
+    for w_, n_ in ((W, 'W'),) if roi_lo is None else ((W[0], 'W_hi'), (W[1], 'W_lo')):
+        _req16(w_, n_)
+    R = roi_hi.shape[0] if R is None else R
+    s = _roi_size(roi_size)
+    n = R * s * s * 256
+    ins = [t for t in (roi_hi, roi_lo) if t is not None]
+    for t in ins:
+        if not t.is_contiguous() or t.numel() < n:
+            raise ValueError('qg_conv_cells: the RoI cells are contiguous [R, s*s, 256] key16 tensors')
+    if bias.numel() < 256:
+        raise ValueError('qg_conv_cells: bias holds 256 values')
+    for t in (out_hi, out_lo, out_f32):
+        if t is None:
+            continue
+        if not t.is_contiguous() or t.numel() < n:
+            raise ValueError('qg_conv_cells: outputs are contiguous [R, s*s, 256] tensors, key16 (out_hi, out_lo) / fp32 (out_f32)')
+        # a block reads its neighbours' input cells while it writes its own: an output may not share storage with an input
+        if any(t.untyped_storage().data_ptr() == i.untyped_storage().data_ptr() for i in ins):
+            raise ValueError('qg_conv_cells: an output may not share storage with the input cells')
+    if roi_lo is None:
+        check(_lib.load().mv2d_qg_conv_cells(_p(roi_hi), _p(W), _p(bias), _p(out_hi), _p(out_lo), _p(out_f32), R, s, _stream()), 'mv2d_qg_conv_cells')
+    else:
+        check(_lib.load().mv2d_qg_conv_cells_x3(_p(roi_hi), _p(roi_lo), _p(W[0]), _p(W[1]), _p(bias), _p(out_hi), _p(out_lo), _p(out_f32), R, s, _stream()),
+              'mv2d_qg_conv_cells_x3')
+
+
+def avgpool_cells(hi, lo, out, R, cells, ld_out=None):
+    """out[r] (fp32 [R, >= 256]) = mean over the key16 rows r * cells .. of hi (+ lo unless None): AvgPool2d(s) of [R,s*s,256] RoI cells; cells = 1:
+    the fp32 copy of the rows."""
+    _req16(hi, 'hi'); _req16(lo, 'lo'); _req(out, torch.float32, 'out')
+    if not hi.is_contiguous() or (lo is not None and not lo.is_contiguous()):
+        raise ValueError('avgpool_cells: hi / lo are contiguous key16 rows')
+    if hi.numel() < R * cells * 256 or (lo is not None and lo.numel() < R * cells * 256):
+        raise ValueError('avgpool_cells: hi / lo hold R * cells rows of 256 channels')
+    ld = out.stride(0) if ld_out is None else ld_out
+    if out.dtype != torch.float32 or out.numel() < (R - 1) * ld + 256:
+        raise ValueError('avgpool_cells: out is an fp32 [R, ld_out >= 256] tensor')
+    check(_lib.load().mv2d_avgpool_cells(_p(hi), 0 if lo is None else _p(lo), _p(out), ld, R, cells, _stream()), 'mv2d_avgpool_cells')
+    return out
+
+
 def avgpool49(x, out, ld_out, R):
     check(_lib.load().mv2d_avgpool49(_p(x), _p(out), ld_out, R, _stream()), 'mv2d_avgpool49')
     return out

@@ -274,6 +274,7 @@ class MV2DHead(nn.Module):
                                       use_reg_layer=getattr(self.bbox_head, 'use_reg_layer', False),
                                       group_reg_dims=getattr(self.bbox_head, 'group_reg_dims', (2, 2, 1, 1, 2, 2)),
                                       masked_row=(self.test_cfg or {}).get('masked_row', 'nan'),
+                                      query_generator=self.query_generator.shape,
                                       exact=(self.test_cfg or {}).get('index_exact', None))      # None: MV2D_EXACT decides
             if 'lo8_rows' in (self.test_cfg or {}):                              # test_cfg.lo8_rows=False: fp16 lo halves of the key / value rows (engine.py; default: e4m3 bytes)
                 self._engine.lo8_rows = bool(self.test_cfg['lo8_rows'])
@@ -328,7 +329,7 @@ class MV2DHead(nn.Module):
         bbox_feats = ops.RoIAlignRows.apply(fm, None, rois, h, w, None, s)                          # [R,s*s,256]
         # reference points with the gradient of the query generator (issued before the first host read-back below: the host keeps
         # launching while the engine's kernels run)
-        ref = train.query_generator_autograd(self, bbox_feats, ws['enc'][:R, 1024:1040].clone(), ws['minv'][:R].clone())
+        ref = train.query_generator_autograd(self, bbox_feats, ws['intr'][:R, :16].clone(), ws['minv'][:R].clone())
         # ONE read-back for the data-dependent sizes: allowed pairs, listed positions, (T) whether a RoI has no key, (T) the key of position 0
         empty = (row_ptr[1:] == row_ptr[:-1]).any().to(torch.int32) if self.KIND == 'T' else row_ptr.new_zeros(())
         nnz, S, any_empty, s0 = (int(v) for v in torch.stack([row_ptr[R], ws['S_dev'].reshape(()).to(torch.int32), empty, ws['pos2s'][0].to(torch.int32)]).tolist())

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .. import calib, ops
+from .. import calib, ops, qg_shape
 from ..registry import (ATTENTION, BBOX_CODERS, FEEDFORWARD_NETWORK, HEADS, LOSSES, POSITIONAL_ENCODING, ROI_EXTRACTORS,
                         TRANSFORMER, TRANSFORMER_LAYER, TRANSFORMER_LAYER_SEQUENCE, build_attention,
                         build_positional_encoding, build_transformer_layer_sequence)
@@ -636,8 +636,10 @@ class _ConvModule(nn.Module):
 
 @HEADS.register_module()
 class QueryGenerator(nn.Module):
-    """RH/utils/query_generator.py:18-405 in the shipped configuration (1 shared 3x3 conv, avg-pool, 1 shared fc, 2-layer
-    extra encoding of the 16 scaled intrinsics, fc_center only)."""
+    """RH/utils/query_generator.py:18-405: the shipped configuration (1 shared 3x3 conv, avg-pool, 1 shared fc, 2-layer extra encoding of the 16
+    scaled intrinsics, fc_center only) and every shape mv2d_amd/qg_shape.py accepts: 0 .. 3 shared convs, 1 .. 3 shared fcs, 0 .. 2 centre fcs, 1 .. 3
+    extra-encoding layers with or without the intrinsics columns, any width that is a multiple of 16, ``with_avg_pool=False``.  The parameters carry
+    the reference module's names and shapes; anything else raises ``ValueError`` naming the key."""
 
     def __init__(self, return_cfg=dict(), wich_cp=False, with_avg_pool=True, with_cls=False, with_size=False, with_center=True,
                  with_heading=False, with_attr=False, attr_dim=2, roi_feat_size=7, in_channels=256, num_classes=10,
@@ -646,19 +648,31 @@ class QueryGenerator(nn.Module):
                  num_shared_convs=1, num_shared_fcs=1, conv_out_channels=256, fc_out_channels=1024, loss_cls=None, conv_cfg=None,
                  norm_cfg=None, init_cfg=None, **kwargs):
         super().__init__()
-        assert with_center and with_avg_pool and not (with_cls or with_size or with_heading or with_attr)
-        assert num_shared_convs == 1 and num_shared_fcs == 1 and in_channels == C and conv_out_channels == C
+        shape = qg_shape.parse(dict(kwargs, with_avg_pool=with_avg_pool, with_cls=with_cls, with_size=with_size, with_center=with_center,
+                                    with_heading=with_heading, with_attr=with_attr, in_channels=in_channels, extra_encoding=extra_encoding,
+                                    num_shared_convs=num_shared_convs, num_shared_fcs=num_shared_fcs, conv_out_channels=conv_out_channels,
+                                    fc_out_channels=fc_out_channels, conv_cfg=conv_cfg, norm_cfg=norm_cfg), 'QueryGenerator')
+        self.shape = shape
         self.roi_feat_size = roi_size_of(roi_feat_size, 'query_generator.roi_feat_size')
-        assert all(kwargs.get(k, 0) == 0 for k in kwargs if k.startswith('num_')), 'branch convs/fcs are 0 in the shipped configs'
-        fc = extra_encoding['feat_channels']
-        assert extra_encoding['num_layers'] == 2 and len(extra_encoding['features']) == 1 and extra_encoding['features'][0]['in_channels'] == 16
+        self.with_avg_pool, self.with_intrinsic = shape.pooled, shape.intrinsic
         self.return_cfg = return_cfg
-        self.shared_convs = nn.ModuleList([_ConvModule(in_channels, conv_out_channels)])
-        self.shared_fcs = nn.ModuleList([nn.Linear(conv_out_channels, fc_out_channels)])
-        self.extra_enc = nn.Sequential(nn.Linear(fc_out_channels + 16, fc[0]), nn.ReLU(inplace=True), nn.Linear(fc[0], fc[1]), nn.ReLU(inplace=True))
-        self.fc_center = nn.Linear(fc[1], 3)
-        self.fc_out_channels = fc_out_channels
+        lin = {p: nn.Linear(k, n) for p, n, k, _ in shape.linears(self.roi_feat_size)}
+        self.shared_convs = nn.ModuleList([_ConvModule(C, C) for _ in range(shape.convs)])
+        self.shared_fcs = nn.ModuleList([lin[f'shared_fcs.{i}'] for i in range(shape.fcs)])
+        enc = []
+        for i in range(len(shape.enc)):
+            enc += [lin[f'extra_enc.{2 * i}'], nn.ReLU(inplace=True)]
+        self.extra_enc = nn.Sequential(*enc)
+        self.center_fcs = nn.ModuleList([lin[f'center_fcs.{i}'] for i in range(shape.center_fcs)])      # (empty: no parameters, as in the reference)
+        self.fc_center = lin['fc_center']
+        self.fc_out_channels = shape.fc_out
         self._b = _Bf16Cache()
+
+    def _load_from_state_dict(self, state_dict, prefix, *a, **kw):
+        # a parameter that is present with another shape than the configured one is refused by name (the head's load_state_dict arrives here too);
+        # missing and unexpected keys stay with torch's own strict / non-strict handling
+        self.shape.check_state(state_dict, self.roi_feat_size, 'QueryGenerator', prefix=prefix, shapes_only=True)
+        return super()._load_from_state_dict(state_dict, prefix, *a, **kw)
 
     def forward(self, x, intrinsics, extrinsics, extra_feats=dict()):
         """x [R,256,s,s] (s = roi_feat_size); intrinsics/extrinsics [R,4,4] fp64 (per-RoI); extra_feats['intrinsic'] [R,16] -> (xyz [R,3], {})."""
@@ -668,6 +682,8 @@ class QueryGenerator(nn.Module):
         s = self.roi_feat_size
         if tuple(x.shape[2:]) != (s, s):
             raise ValueError(f'QueryGenerator: RoI features of {tuple(x.shape[2:])} cells, roi_feat_size = {s}')
+        if not self.shape.is_default:
+            return self._forward_shape(x, intrinsics, extrinsics, extra_feats)
         conv = self.shared_convs[0].conv
         K1 = self.fc_out_channels + 16
         Kp = (K1 + 31) // 32 * 32
@@ -693,6 +709,53 @@ class QueryGenerator(nn.Module):
         h1 = ops.gemm_f32(enc, w0, _f(e0.bias), act=1)
         h2 = ops.gemm_f32(h1, _f(e2.weight), _f(e2.bias), act=1)
         center = ops.gemm_f32(h2, _f(self.fc_center.weight), _f(self.fc_center.bias))
+        minv = ops.lidar2img_inverse(intrinsics.double().reshape(R, 16).contiguous(), extrinsics.double().reshape(R, 16).contiguous())
+        xyz = torch.empty((R, 3), device=dev); ref = torch.empty((R, 3), device=dev); pos = torch.empty((R, 384), device=dev)
+        ct = calib.constant_tables()
+        ops.refpoint_posemb(center, 3, minv, ct['dim_t'].to(dev), xyz, ref, pos, R, torch.tensor([0., 0., 0., 1., 1., 1.]))
+        return xyz, dict()
+
+    def _forward_shape(self, x, intrinsics, extrinsics, extra_feats):
+        """forward for a shape other than the shipped one, on the engine's index-exact kernels: the cells as key16 hi + lo pairs, every conv in split
+        precision (cell-writing launches, the last one fused with the pool or writing the flattened fp32 rows), fp32 linears."""
+        dev, R, s, sh = x.device, x.shape[0], self.roi_feat_size, self.shape
+        k16 = ops.key16_dtype()
+        hi, lo = ops.f32_to_key16(x.float().flatten(2).transpose(1, 2).contiguous(), with_lo=True)     # [R,s*s,256] cell-major
+        feat = torch.empty((R, C if sh.pooled else s * s * C), device=dev)
+        for i, m in enumerate(self.shared_convs):
+            wx3 = self._b.get(f'conv{i}_x3', m.conv.weight, lambda w: ops.pack_key16_x3(w.permute(0, 2, 3, 1).reshape(C, 9 * C).contiguous()))
+            b = _f(m.conv.bias).contiguous()
+            if i < sh.convs - 1:
+                nh, nl = torch.empty((R, s * s, C), device=dev, dtype=k16), torch.empty((R, s * s, C), device=dev, dtype=k16)
+                ops.qg_conv_cells(hi, lo, wx3, b, out_hi=nh, out_lo=nl, R=R, roi_size=s)
+                hi, lo = nh, nl
+            elif sh.pooled:
+                ops.qg_conv_pool_x3(hi, lo, wx3, b, feat, R=R, roi_size=s)
+            else:
+                ops.qg_conv_cells(hi, lo, wx3, b, out_f32=feat, R=R, roi_size=s)
+        if sh.convs == 0:
+            if sh.pooled:
+                ops.avgpool_cells(hi, lo, feat, R, s * s)
+            else:
+                ops.avgpool_cells(hi, lo, feat.view(R * s * s, C), R * s * s, 1)
+
+        def lin(h, W, fc, act=1, clamp=0.0):
+            # (the fp32 GEMM takes K in multiples of 32: zero columns behind a width that is none)
+            pad = -h.shape[1] % 32
+            if pad:
+                h, W = torch.nn.functional.pad(h, (0, pad)), torch.nn.functional.pad(W, (0, pad))
+            return ops.gemm_f32(h.contiguous(), W.contiguous(), _f(fc.bias), act=act, clamp=clamp)
+        h = feat
+        for i, fc in enumerate(self.shared_fcs):
+            W = _f(fc.weight)
+            if i == 0 and not sh.pooled:
+                W = W[:, qg_shape.flatten_perm(s, dev)]                      # (channel, y, x) columns -> the cell-major rows above
+            h = lin(h, W, fc, clamp=5e3 if i == sh.fcs - 1 else 0.0)
+        if sh.intrinsic:
+            h = torch.cat([h, extra_feats['intrinsic'].float().clamp(-5e3, 5e3)], 1)
+        for fc in list(self.extra_enc)[::2] + list(self.center_fcs):
+            h = lin(h, _f(fc.weight), fc)
+        center = lin(h, _f(self.fc_center.weight), self.fc_center, act=0)
         minv = ops.lidar2img_inverse(intrinsics.double().reshape(R, 16).contiguous(), extrinsics.double().reshape(R, 16).contiguous())
         xyz = torch.empty((R, 3), device=dev); ref = torch.empty((R, 3), device=dev); pos = torch.empty((R, 384), device=dev)
         ct = calib.constant_tables()

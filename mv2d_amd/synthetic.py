@@ -229,6 +229,28 @@ def with_pe_depth_state(sd, seed=0, depth_num=DEPTH_NUM):
     return out
 
 
+def with_qg_shape_state(sd, seed=0, query_generator=None, roi_size=7):
+    """A copy of a make_head_state dict whose ``query_generator.*`` entries are those of the reference module built with the given
+    ``query_generator=dict(...)`` keys (mv2d_amd/qg_shape.py) at ``roi_size``: Xavier matrices, small biases, fc_center scaled and centred like
+    make_head_state's; its own stream of draws, make_head_state is untouched."""
+    from . import qg_shape
+    shape = qg_shape.parse(query_generator, 'with_qg_shape_state')
+    g = _rng(seed + 15485863)
+    q = 'query_generator.'
+    out = OrderedDict((k, v) for k, v in sd.items() if not k.startswith(q))
+    for k, shp in shape.param_shapes(int(roi_size)).items():
+        if k == 'fc_center.weight':
+            wc = _xavier(g, shp)
+            wc[:2] *= 4.0
+            wc[2] *= 24.0
+            out[q + k] = wc
+        elif k == 'fc_center.bias':
+            out[q + k] = np.array([3.5, 3.5, 25.0], np.float32)
+        else:
+            out[q + k] = _xavier(g, shp) if len(shp) > 1 else _bias(g, shp[0])
+    return out
+
+
 WORKLOADS = {
     # name: (head kind, views/frame, frames, img_h, img_w, pad_w, boxes/view)
     'micro_t': ('T', 2, 1, 128, 192, None, 6),

@@ -489,13 +489,27 @@ def query_generator_autograd(roi_head, roi_feat, intr_feat, minv):
     from .autograd_ops import Im2Col3x3Fn
     assert Cc == 256
     s = getattr(qg, 'roi_feat_size', 7)                 # s x s cells (roi_feat [R,s*s,256])
-    cols = Im2Col3x3Fn.apply(roi_feat.float().reshape(R, s * s, Cc), s)
-    conv = qg.shared_convs[0].conv
-    x = linear(cols, conv.weight.permute(0, 2, 3, 1).reshape(conv.weight.shape[0], 9 * Cc), conv.bias, 1).view(R, s * s, -1).mean(1)   # ReLU, AvgPool2d(s)
-    x = linear(x, qg.shared_fcs[0].weight, qg.shared_fcs[0].bias, 1)
-    x = torch.cat([x, intr_feat.detach().float()], 1).clamp(min=-5e3, max=5e3)
-    x = linear(x, qg.extra_enc[0].weight, qg.extra_enc[0].bias, 1)
-    x = linear(x, qg.extra_enc[2].weight, qg.extra_enc[2].bias, 1)
+    # the trunk the module was built with (mv2d_amd/qg_shape.py): every shared conv the module holds, AvgPool2d(s) or the reference's flatten(1),
+    # every shared fc, the extra-encoding layers, every centre fc
+    x = roi_feat.float().reshape(R, s * s, Cc)
+    for m in qg.shared_convs:
+        conv = m.conv
+        cols = Im2Col3x3Fn.apply(x, s)
+        x = linear(cols, conv.weight.permute(0, 2, 3, 1).reshape(conv.weight.shape[0], 9 * Cc), conv.bias, 1).view(R, s * s, -1)   # ReLU
+    if getattr(qg, 'with_avg_pool', True):
+        x = x.mean(1)                                   # AvgPool2d(s)
+    else:
+        x = x.transpose(1, 2).reshape(R, -1)            # flatten(1) of [R,256,s,s]: (channel, y, x) columns
+    for fc in qg.shared_fcs:
+        x = linear(x, fc.weight, fc.bias, 1)
+    if getattr(qg, 'with_intrinsic', True):
+        x = torch.cat([x, intr_feat.detach().float()], 1)
+    x = x.clamp(min=-5e3, max=5e3)
+    for fc in qg.extra_enc:
+        if isinstance(fc, torch.nn.Linear):
+            x = linear(x, fc.weight, fc.bias, 1)
+    for fc in getattr(qg, 'center_fcs', ()):
+        x = linear(x, fc.weight, fc.bias, 1)
     c = linear(x, qg.fc_center.weight, qg.fc_center.bias)
     from .autograd_ops import Center2LidarFn
     return Center2LidarFn.apply(c, minv.detach().reshape(R, 16), [float(v) for v in roi_head.pc_range])      # one launch per direction (round 5)
