@@ -287,6 +287,25 @@ int mv2d_heads_cls_x3_nc(const float* outs, const void* const* cls_w, float* cls
 int mv2d_reg_layer_x3(const float* outs, const void* const* w, const float* ref, float* reg, int M, int L, int n_groups, const int* group_dims,
                       const float* pc_range, float dt, const float* dt_rows, void* stream);
 
+/* The prediction branches with n_fcs = 1, 2 or 3 hidden layers per branch (the reference head's num_reg_fcs; csrc/branch_depth.hip): the
+ * launches above with the hidden Linear(256,256) (+ LayerNorm on the class branch) + ReLU blocks as a loop over n_fcs.  Hidden layers in split
+ * precision, output layers in exact fp32, the same box-code tail.  Every table is stacked [L][n_fcs] (layer-major, then the block):
+ *   cls_w = {w_hi, w_lo, b, ln_w, ln_b, w_out, b_out}: w_hi / w_lo [L][n_fcs] per-matrix mv2d_split_q16x2 + mv2d_pack_wfrag_bf16 copies,
+ *           b / ln_w / ln_b [L,n_fcs,256], w_out [L,num_classes,256], b_out [L,num_classes]
+ *   reg_w = {w_hi, w_lo, b, w_out, b_out}: the same without LayerNorm, w_out [L,10,256], b_out [L,10]
+ * At n_fcs = 2 cls and reg are bit for bit those of mv2d_heads_fused_x3_nc on the same weights.  n_fcs outside [1, 3], num_classes outside
+ * [1, 64], L < 1, M < 0 or a null pointer return -1 before anything is launched. */
+int mv2d_heads_depth_x3(const float* outs, const void* const* cls_w, const void* const* reg_w, const float* ref, float* cls, float* reg,
+                        int M, int L, int n_fcs, int num_classes, float eps, const float* pc_range, float dt, const float* dt_rows, void* stream);
+/* The class branch of mv2d_heads_depth_x3 alone (cls bit for bit the same), next to mv2d_reg_layer_depth_x3. */
+int mv2d_heads_cls_depth_x3(const float* outs, const void* const* cls_w, float* cls, int M, int L, int n_fcs, int num_classes, float eps,
+                            void* stream);
+/* mv2d_reg_layer_x3 with n_fcs = 1, 2 or 3 shared layers (RegLayer's shared_reg_fcs = num_reg_fcs).
+ * w = {s_hi, s_lo, s_b, t1_hi, t1_lo, t1_b, t2_w, t2_b}: the shared layers stacked [L][n_fcs] (biases [L,n_fcs,256]), the task heads as in
+ * mv2d_reg_layer_x3.  At n_fcs = 2 reg is bit for bit that of mv2d_reg_layer_x3.  The same argument checks, plus n_fcs in [1, 3]. */
+int mv2d_reg_layer_depth_x3(const float* outs, const void* const* w, const float* ref, float* reg, int M, int L, int n_fcs, int n_groups,
+                            const int* group_dims, const float* pc_range, float dt, const float* dt_rows, void* stream);
+
 /* Fused FFN partial sums (mmcv FFN 256 -> hidden -> 256 of the decoder layer, configs/mv2d/exp/*:78-79):
  * slabs[s] = relu(X . W1[64s:64s+64]^T + b1[64s:64s+64]) . W2[:, 64s:64s+64]^T  for the hidden/64 slices s, exact fp32.
  * X [M,256], W1 [hidden,256], W2 [256,hidden], slabs [hidden/64, M, 256]; the caller sums the slabs + b2 + residual

@@ -70,6 +70,9 @@ SIGNATURES = {
     'mv2d_heads_fused_x3_nc': (I, [P, P, P, P, P, P, I, I, I, F, P, F, P, P]),
     'mv2d_heads_cls_x3_nc': (I, [P, P, P, I, I, I, F, P]),
     'mv2d_reg_layer_x3': (I, [P, P, P, P, I, I, I, P, P, F, P, P]),
+    'mv2d_heads_depth_x3': (I, [P, P, P, P, P, P, I, I, I, I, F, P, F, P, P]),
+    'mv2d_heads_cls_depth_x3': (I, [P, P, P, I, I, I, I, F, P]),
+    'mv2d_reg_layer_depth_x3': (I, [P, P, P, P, I, I, I, I, P, P, F, P, P]),
     'mv2d_ffn_fused': (I, [P, P, P, P, P, I, I, P]),
     'mv2d_ffn_pack_weights': (I, [P, P, P, P, I, P]),
     'mv2d_ffn_fused_x3': (I, [P, P, P, P, P, P, P, I, I, I, P]),

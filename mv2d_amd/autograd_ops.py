@@ -298,15 +298,27 @@ BRANCH_PARAMS = ('cls_branches.{l}.0.weight', 'cls_branches.{l}.0.bias', 'cls_br
                  'reg_branches.{l}.2.weight', 'reg_branches.{l}.2.bias', 'reg_branches.{l}.4.weight', 'reg_branches.{l}.4.bias')
 
 
-def reg_layer_params(group_reg_dims):
+def reg_layer_params(group_reg_dims, num_reg_fcs=2):
     """Parameter names of one layer's RegLayer regression branch (CrossAttentionBoxHead(use_reg_layer=True)), in module order."""
-    names = [f'reg_branches.{{l}}.reg_branch.{n}.{k}' for n in (0, 3) for k in ('weight', 'bias')]
+    names = [f'reg_branches.{{l}}.reg_branch.{3 * i}.{k}' for i in range(num_reg_fcs) for k in ('weight', 'bias')]
     return tuple(names + [f'reg_branches.{{l}}.task_heads.{g}.{n}.{k}' for g in range(len(group_reg_dims)) for n in (0, 2) for k in ('weight', 'bias')])
 
 
-def branch_params(use_reg_layer=False, group_reg_dims=()):
-    """BRANCH_PARAMS for a head: with use_reg_layer the three reg_branches linears give way to the RegLayer's parameters."""
-    return BRANCH_PARAMS if not use_reg_layer else BRANCH_PARAMS[:10] + reg_layer_params(group_reg_dims)
+def cls_branch_params(num_reg_fcs=2):
+    """Parameter names of one layer's class branch with num_reg_fcs hidden blocks (Linear at 3i, LayerNorm at 3i + 1), in module order."""
+    idx = [j for i in range(num_reg_fcs) for j in (3 * i, 3 * i + 1)] + [3 * num_reg_fcs]
+    return tuple(f'cls_branches.{{l}}.{j}.{k}' for j in idx for k in ('weight', 'bias'))
+
+
+def branch_params(use_reg_layer=False, group_reg_dims=(), num_reg_fcs=2):
+    """BRANCH_PARAMS for a head: with use_reg_layer the reg_branches linears give way to the RegLayer's parameters; num_reg_fcs hidden layers per
+    branch (2: exactly BRANCH_PARAMS, the order HeadsFn takes)."""
+    if num_reg_fcs == 2 and not use_reg_layer:
+        return BRANCH_PARAMS
+    cls = BRANCH_PARAMS[:10] if num_reg_fcs == 2 else cls_branch_params(num_reg_fcs)
+    if use_reg_layer:
+        return cls + reg_layer_params(group_reg_dims, num_reg_fcs)
+    return cls + tuple(f'reg_branches.{{l}}.{2 * i}.{k}' for i in range(num_reg_fcs + 1) for k in ('weight', 'bias'))
 
 
 def _flat_grads(params, dev):

@@ -118,27 +118,40 @@ def _set_reg_layer(d, group_reg_dims):
     return d
 
 
-def roi_head_cfg_s(num_classes=10, roi_size=ROI_SIZE, reg_layer_dims=None, depth_num=64, depth_start=1, position_range=None, query_generator=None):
+def _set_num_reg_fcs(d, num_reg_fcs):
+    # ``bbox_head.num_reg_fcs`` of the reference head (hidden layers per prediction branch, RegLayer's shared layers).  The shipped configs leave it
+    # at the head's default, 2 (no key): the default here gives exactly that dict
+    from . import ops
+    if ops.check_num_reg_fcs(num_reg_fcs, 'configs') != 2:
+        d['bbox_head']['num_reg_fcs'] = int(num_reg_fcs)
+    return d
+
+
+def roi_head_cfg_s(num_classes=10, roi_size=ROI_SIZE, reg_layer_dims=None, depth_num=64, depth_start=1, position_range=None, query_generator=None,
+                   num_reg_fcs=2):
     """CFG-S:40-121 (MV2D-S single frame); ``num_classes`` sets ``bbox_head.num_classes`` and ``bbox_head.bbox_coder.num_classes``,
     ``roi_size`` sets ``bbox_roi_extractor.roi_layer.output_size`` and ``query_generator.roi_feat_size``; ``reg_layer_dims`` (a tuple of
     group widths) sets ``bbox_head.use_reg_layer=True`` with that ``group_reg_dims``; ``depth_num`` (a multiple of 8 in [8, 80]), ``depth_start``
     and ``position_range`` (None: the shipped POST_RANGE) set the keys of the same names in ``pe``; ``query_generator`` (a dict of the reference
-    QueryGenerator's own keys: mv2d_amd/qg_shape.py lists the accepted values) is laid over the ``query_generator`` subtree."""
+    QueryGenerator's own keys: mv2d_amd/qg_shape.py lists the accepted values) is laid over the ``query_generator`` subtree; ``num_reg_fcs`` (1, 2
+    or 3) sets ``bbox_head.num_reg_fcs``, alone or together with ``reg_layer_dims`` (2, the head's default: no key)."""
     d = dict(type='MV2DSHead', use_denoise=False)
     d.update(_common(with_cp=False))
     d['box_correlation'] = dict(correlation_mode='topk_matched:1:0.0:0.0')
     d = _set_query_generator(_set_pe_depth(d, depth_num, depth_start, position_range), query_generator)
-    return copy.deepcopy(_set_reg_layer(_set_roi_size(_set_num_classes(d, num_classes), roi_size), reg_layer_dims))
+    return copy.deepcopy(_set_num_reg_fcs(_set_reg_layer(_set_roi_size(_set_num_classes(d, num_classes), roi_size), reg_layer_dims), num_reg_fcs))
 
 
-def roi_head_cfg_t(num_classes=10, roi_size=ROI_SIZE, reg_layer_dims=None, depth_num=64, depth_start=1, position_range=None, query_generator=None):
-    """CFG-T:40-125 (MV2D-T two frames); ``num_classes``, ``roi_size``, ``reg_layer_dims``, the three ``pe`` keys and ``query_generator`` as in ``roi_head_cfg_s``."""
+def roi_head_cfg_t(num_classes=10, roi_size=ROI_SIZE, reg_layer_dims=None, depth_num=64, depth_start=1, position_range=None, query_generator=None,
+                   num_reg_fcs=2):
+    """CFG-T:40-125 (MV2D-T two frames); ``num_classes``, ``roi_size``, ``reg_layer_dims``, the three ``pe`` keys, ``query_generator`` and ``num_reg_fcs``
+    as in ``roi_head_cfg_s``."""
     d = dict(type='MV2DTHead', use_denoise=True, neg_bbox_loss=True,
              denoise_noise_scale=1.25, denoise_split=0.6)
     d.update(_common(with_cp=True))
     d['box_correlation'] = dict(expand_stride=2, correlation_mode='topk_matched:20:0.0:0.0')
     d = _set_query_generator(_set_pe_depth(d, depth_num, depth_start, position_range), query_generator)
-    return copy.deepcopy(_set_reg_layer(_set_roi_size(_set_num_classes(d, num_classes), roi_size), reg_layer_dims))
+    return copy.deepcopy(_set_num_reg_fcs(_set_reg_layer(_set_roi_size(_set_num_classes(d, num_classes), roi_size), reg_layer_dims), num_reg_fcs))
 
 
 TEST_CFG_RCNN = dict(score_thr=0.0, nms=dict(nms_thr=1.0, use_rotate_nms=True), max_per_scene=300)  # CFG-T:154-158

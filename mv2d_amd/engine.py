@@ -49,7 +49,7 @@ class HeadEngine:
                  max_num=300, pc_range=(-51.2, -51.2, -5.0, 51.2, 51.2, 3.0),
                  post_range=(-61.2, -61.2, -10.0, 61.2, 61.2, 10.0), depth_num=64, stride=16, col_cap_per_query=2048,
                  iou_thr=0.0, ratio=0.0, masked_row='nan', exact=None, num_classes=10, roi_size=7, use_reg_layer=False,
-                 group_reg_dims=(2, 2, 1, 1, 2, 2), depth_start=1, position_range=None, query_generator=None):
+                 group_reg_dims=(2, 2, 1, 1, 2, 2), depth_start=1, position_range=None, query_generator=None, num_reg_fcs=2):
         assert kind in ('S', 'T')
         self.kind = kind
         self.dev = torch.device(device)
@@ -74,6 +74,9 @@ class HeadEngine:
         # key layout has to agree (load_state), and it is part of the graph key.
         self.use_reg_layer = bool(use_reg_layer)
         self.group_reg_dims = ops.check_group_reg_dims(group_reg_dims) if self.use_reg_layer else tuple(group_reg_dims)
+        # hidden layers per prediction branch (the head's num_reg_fcs; RegLayer's shared layers): 2 launches the shipped kernels with the shipped
+        # tables, 1 and 3 the depth-loop kernels of csrc/branch_depth.hip.  Fixed per engine: the state dict's branches have to have that depth.
+        self.num_reg_fcs = ops.check_num_reg_fcs(num_reg_fcs, 'HeadEngine')
         # the PE's depth_num / depth_start / position_range (MU/pe.py:52-63).  Every consumer of the frustum rows takes them with Kp = pe_kp(depth_num)
         # columns (3 * depth_num zero-padded to a multiple of 32) and position_encoder.0.weight zero-padded to [1024, Kp]: one instance of the fused PE
         # kernel per Kp / 32 (csrc/pe_x3_kernel.h).  position_range=None: the coder's post_range, as in the shipped configs; the decode's centre filter
@@ -113,10 +116,12 @@ class HeadEngine:
 
     # ------------------------------------------------------------------------------------------ weights
     def load_state(self, sd):
-        d, L = self.dev, self.L
-        nc = int(tuple(sd['bbox_head.cls_branches.0.6.weight'].shape)[0])
+        d, L, nf = self.dev, self.L, self.num_reg_fcs
+        self.check_reg_layout(sd, self.use_reg_layer, self.group_reg_dims)
+        self.check_branch_depth(sd, nf, self.use_reg_layer)
+        nc = int(tuple(sd[f'bbox_head.cls_branches.0.{3 * nf}.weight'].shape)[0])
         if nc != self.num_classes:
-            raise ValueError(f'HeadEngine: the state dict has {nc} classes (cls_branches.*.6.weight), num_classes={self.num_classes}')
+            raise ValueError(f'HeadEngine: the state dict has {nc} classes (cls_branches.*.{3 * nf}.weight), num_classes={self.num_classes}')
         k1 = int(tuple(sd['position_encoding.position_encoder.0.weight'].shape)[1])
         if k1 != 3 * self.depth_num:
             raise ValueError(f'HeadEngine: the state dict has {k1} frustum channels (position_encoder.0.weight), 3 * depth_num = {3 * self.depth_num}')
@@ -151,21 +156,36 @@ class HeadEngine:
         w['qe_b0'], w['qe_b2'] = g('bbox_head.query_embedding.0.bias'), g('bbox_head.query_embedding.2.bias')
         w['qe_w0x'], w['qe_w2x'] = ops.pack_x3(g('bbox_head.query_embedding.0.weight')), ops.pack_x3(g('bbox_head.query_embedding.2.weight'))
         st = lambda fmt: torch.stack([g(fmt.format(l)) for l in range(L)]).contiguous()
-        for n in ('0', '3'):
-            w[f'cls_w{n}'], w[f'cls_b{n}'] = st('bbox_head.cls_branches.{}.' + n + '.weight'), st('bbox_head.cls_branches.{}.' + n + '.bias')
-        for n in ('1', '4'):
-            w[f'cls_lnw{n}'], w[f'cls_lnb{n}'] = st('bbox_head.cls_branches.{}.' + n + '.weight'), st('bbox_head.cls_branches.{}.' + n + '.bias')
-        w['cls_w6'], w['cls_b6'] = st('bbox_head.cls_branches.{}.6.weight'), st('bbox_head.cls_branches.{}.6.bias')
         rb = 'bbox_head.reg_branches.'
-        self.check_reg_layout(sd, self.use_reg_layer, self.group_reg_dims)
+        if nf == 2:
+            for n in ('0', '3'):
+                w[f'cls_w{n}'], w[f'cls_b{n}'] = st('bbox_head.cls_branches.{}.' + n + '.weight'), st('bbox_head.cls_branches.{}.' + n + '.bias')
+            for n in ('1', '4'):
+                w[f'cls_lnw{n}'], w[f'cls_lnb{n}'] = st('bbox_head.cls_branches.{}.' + n + '.weight'), st('bbox_head.cls_branches.{}.' + n + '.bias')
+            w['cls_w6'], w['cls_b6'] = st('bbox_head.cls_branches.{}.6.weight'), st('bbox_head.cls_branches.{}.6.bias')
+        else:
+            # branches of another depth, stacked [L][nf]: class block i at {3i, 3i+1}, output at {3nf}; Sequential regression block i at {2i}, output
+            # at {2nf}; RegLayer shared block i at reg_branch.{3i}
+            stn = lambda fmt, idx: torch.stack([torch.stack([g(fmt.format(l, i)) for i in idx]) for l in range(L)]).contiguous()
+            cb = 'bbox_head.cls_branches.{}.{}.'
+            lin_i, ln_i = [3 * i for i in range(nf)], [3 * i + 1 for i in range(nf)]
+            w['clsd_w'], w['clsd_b'] = stn(cb + 'weight', lin_i), stn(cb + 'bias', lin_i)
+            w['clsd_lnw'], w['clsd_lnb'] = stn(cb + 'weight', ln_i), stn(cb + 'bias', ln_i)
+            w['clsd_wo'], w['clsd_bo'] = st('bbox_head.cls_branches.{}.' + str(3 * nf) + '.weight'), st('bbox_head.cls_branches.{}.' + str(3 * nf) + '.bias')
+            if self.use_reg_layer:
+                w['rld_s_w'], w['rld_s_b'] = stn(rb + '{}.reg_branch.{}.weight', lin_i), stn(rb + '{}.reg_branch.{}.bias', lin_i)
+            else:
+                w['regd_w'], w['regd_b'] = stn(rb + '{}.{}.weight', [2 * i for i in range(nf)]), stn(rb + '{}.{}.bias', [2 * i for i in range(nf)])
+                w['regd_wo'], w['regd_bo'] = st(rb + '{}.' + str(2 * nf) + '.weight'), st(rb + '{}.' + str(2 * nf) + '.bias')
         if self.use_reg_layer:
             G = len(self.group_reg_dims)
-            for n, k in (('s1', 'reg_branch.0'), ('s2', 'reg_branch.3')):
-                w[f'rl_{n}_w'], w[f'rl_{n}_b'] = st(rb + '{}.' + k + '.weight'), st(rb + '{}.' + k + '.bias')
+            if nf == 2:
+                for n, k in (('s1', 'reg_branch.0'), ('s2', 'reg_branch.3')):
+                    w[f'rl_{n}_w'], w[f'rl_{n}_b'] = st(rb + '{}.' + k + '.weight'), st(rb + '{}.' + k + '.bias')
             stg = lambda fmt, cat: torch.stack([cat([g(rb + fmt.format(l, g_)) for g_ in range(G)]) for l in range(L)]).contiguous()
             w['rl_t1_w'], w['rl_t1_b'] = stg('{}.task_heads.{}.0.weight', torch.stack), stg('{}.task_heads.{}.0.bias', torch.stack)
             w['rl_t2_w'], w['rl_t2_b'] = stg('{}.task_heads.{}.2.weight', torch.cat), stg('{}.task_heads.{}.2.bias', torch.cat)
-        else:
+        elif nf == 2:
             for n in ('0', '2', '4'):
                 w[f'reg_w{n}'], w[f'reg_b{n}'] = st(rb + '{}.' + n + '.weight'), st(rb + '{}.' + n + '.bias')
         q = 'query_generator.'
@@ -220,6 +240,24 @@ class HeadEngine:
             if self.qg.is_default:
                 w['qg_conv_wx3'] = ops.pack_key16_x3(conv)
         self.w = w
+        if nf != 2:
+            # the tables of mv2d_heads_depth_x3 / mv2d_heads_cls_depth_x3 / mv2d_reg_layer_depth_x3 (every tensor layer-major, like the shipped ones)
+            seq = () if self.use_reg_layer else (w['regd_w'], w['regd_b'], w['regd_wo'], w['regd_bo'])
+            cls_t, reg_t = ops.pack_heads_depth(w['clsd_w'], w['clsd_b'], w['clsd_lnw'], w['clsd_lnb'], w['clsd_wo'], w['clsd_bo'], *seq)
+            if self.use_reg_layer:
+                reg_t = ops.pack_reg_layer_depth(w['rld_s_w'], w['rld_s_b'], w['rl_t1_w'], w['rl_t1_b'], w['rl_t2_w'], w['rl_t2_b'])
+            cls_t, reg_t = tuple(cls_t), tuple(reg_t)
+            w['heads_depth_tables'] = (cls_t, reg_t)
+        else:
+            cls_t, reg_t = self._shipped_head_tables(w)
+        self.cls_ptrs_x3, self.reg_ptrs_x3 = ops.make_ptr_array(list(cls_t)), ops.make_ptr_array(list(reg_t))
+        # the same tensors from the last decoder layer on: the launch of the last_stage_heads option (every tensor is stacked over L)
+        ll = self.L - 1
+        self._last_cls, self._last_reg = [t[ll:] for t in cls_t], [t[ll:] for t in reg_t]
+        self.cls_ptrs_x3_last, self.reg_ptrs_x3_last = ops.make_ptr_array(self._last_cls), ops.make_ptr_array(self._last_reg)
+
+    def _shipped_head_tables(self, w):
+        """the weight tables of the shipped depth (num_reg_fcs = 2): mv2d_heads_fused_x3(_nc) / mv2d_heads_cls_x3_nc / mv2d_reg_layer_x3"""
         for k in ('cls_w0', 'cls_w3') + (() if self.use_reg_layer else ('reg_w0', 'reg_w2')):   # [L,256,256] -> bf16x3, fragment-major, stacked over L
             w[k + 'x'] = ops.pack_x3_stack(w[k])
         cls_t = (*w['cls_w0x'], w['cls_b0'], w['cls_lnw1'], w['cls_lnb1'], *w['cls_w3x'], w['cls_b3'], w['cls_lnw4'], w['cls_lnb4'], w['cls_w6'], w['cls_b6'])
@@ -227,11 +265,7 @@ class HeadEngine:
             reg_t = w['rl_table'] = tuple(ops.pack_reg_layer(*(w[f'rl_{n}_{k}'] for n in ('s1', 's2', 't1', 't2') for k in ('w', 'b'))))
         else:
             reg_t = (*w['reg_w0x'], w['reg_b0'], *w['reg_w2x'], w['reg_b2'], w['reg_w4'], w['reg_b4'])
-        self.cls_ptrs_x3, self.reg_ptrs_x3 = ops.make_ptr_array(list(cls_t)), ops.make_ptr_array(list(reg_t))
-        # the same tensors from the last decoder layer on: the launch of the last_stage_heads option (every tensor is stacked over L)
-        ll = self.L - 1
-        self._last_cls, self._last_reg = [t[ll:] for t in cls_t], [t[ll:] for t in reg_t]
-        self.cls_ptrs_x3_last, self.reg_ptrs_x3_last = ops.make_ptr_array(self._last_cls), ops.make_ptr_array(self._last_reg)
+        return cls_t, reg_t
 
     def _load_qg_shape(self, g, w):
         """Packed weights and the launch plan of a query generator of other than the shipped shape (self.qg): w['qg_convs'] = [(key16 hi / lo
@@ -289,6 +323,50 @@ class HeadEngine:
             if tuple(dims) != tuple(group_reg_dims):
                 raise ValueError(f'HeadEngine: group_reg_dims={tuple(group_reg_dims)}, the task heads of the state dict are {tuple(dims)} wide')
 
+    @staticmethod
+    def branch_depths(sd):
+        """(class depth, regression depth) of layer 0's prediction branches as the state dict's keys spell them: hidden class blocks at
+        ``cls_branches.0.{3i, 3i+1}`` (Linear, LayerNorm) before the output Linear, Sequential regression blocks at ``reg_branches.0.{2i}`` before the
+        output Linear, RegLayer shared blocks at ``reg_branches.0.reg_branch.{3i}``."""
+        cb, rb = 'bbox_head.cls_branches.0.', 'bbox_head.reg_branches.0.'
+        nc = 0
+        while f'{cb}{3 * nc}.weight' in sd and f'{cb}{3 * nc + 1}.weight' in sd:
+            nc += 1
+        nr = 0
+        if f'{rb}reg_branch.0.weight' in sd:
+            while f'{rb}reg_branch.{3 * nr}.weight' in sd:
+                nr += 1
+        else:
+            while f'{rb}{2 * nr}.weight' in sd and f'{rb}{2 * nr + 2}.weight' in sd:
+                nr += 1
+        return nc, nr
+
+    @staticmethod
+    def check_branch_depth(sd, num_reg_fcs, use_reg_layer=False):
+        """ValueError naming ``num_reg_fcs`` unless the prediction branches of the state dict have exactly that many hidden layers: decided by
+        which keys exist AND by the shapes under them (a depth-1 class branch has its [num_classes, 256] output layer under the key where a
+        depth-2 branch has a [256, 256] hidden one)."""
+        n = ops.check_num_reg_fcs(num_reg_fcs, 'HeadEngine')
+        cb, rb = 'bbox_head.cls_branches.0.', 'bbox_head.reg_branches.0.'
+        shp = lambda k: tuple(sd[k].shape) if k in sd else None
+        want = [(f'{cb}{3 * i}.weight', (C, C)) for i in range(n)] + [(f'{cb}{3 * i + 1}.weight', (C,)) for i in range(n)]
+        if use_reg_layer:
+            want += [(f'{rb}reg_branch.{3 * i}.weight', (C, C)) for i in range(n)]
+            absent = [f'{rb}reg_branch.{3 * n}.weight']
+        else:
+            want += [(f'{rb}{2 * i}.weight', (C, C)) for i in range(n)] + [(f'{rb}{2 * n}.weight', (10, C))]
+            absent = [f'{rb}{2 * n + 2}.weight']
+        absent += [f'{cb}{3 * n + 1}.weight', f'{cb}{3 * n + 3}.weight']
+        out = shp(f'{cb}{3 * n}.weight')
+        ok = (all(shp(k) == s_ for k, s_ in want) and out is not None and len(out) == 2 and out[1] == C and 1 <= out[0] <= 64
+              and not any(k in sd for k in absent))
+        if not ok:
+            nc, nr = HeadEngine.branch_depths(sd)
+            kind = 'RegLayer shared' if use_reg_layer else 'Sequential regression'
+            raise ValueError(f'HeadEngine: num_reg_fcs={n} expects {n} hidden layer(s) per prediction branch (class blocks at cls_branches.{{l}}.{{3i, 3i+1}} '
+                             f'with the output layer at {3 * n}; {kind} blocks at {"reg_branch.{3i}" if use_reg_layer else "{2i} with the output layer at " + str(2 * n)}); '
+                             f'the state dict\'s class branches have {nc} and its regression branches {nr} -- build the engine with the num_reg_fcs of the checkpoint')
+
     def _c3(self, name):
         """K-concatenated split-precision copy [w_hi | w_hi | w_lo] of a PE weight ('w1a', 'w1b', 'w2a', 'w2b', 'wr', 'we'), built on first use
         on the default route (which only keeps the sine branch's pair; the index-exact route holds all six)."""
@@ -305,12 +383,12 @@ class HeadEngine:
         guard are shared by all R of a bucket.  Vg = views per sample, V = all views of the batch; st = the route's storage part (route.Storage):
         routes that store their rows differently never share buffers."""
         # (the dtype of the feature map is part of both keys: ws['featcl'] has it, and a captured graph holds the launches of ONE element format)
-        key = (V, h, w, R, Vg, self.num_classes, self.roi_size, map_dtype, st)
+        key = (V, h, w, R, Vg, self.num_classes, self.roi_size, map_dtype, st, self.num_reg_fcs)
         ws = self._ws.get(key)
         if ws is not None:
             return ws
         cap = max(64, -(-R // 32) * 32)
-        bkey = (V, h, w, cap, Vg, self.num_classes, self.roi_size, map_dtype, st)
+        bkey = (V, h, w, cap, Vg, self.num_classes, self.roi_size, map_dtype, st, self.num_reg_fcs)
         base = self._ws_base.get(bkey)
         if base is None:
             store = []
@@ -937,7 +1015,15 @@ class HeadEngine:
         ll, n = (self.L - 1, 1) if last else (0, self.L)
         cls_p, reg_p = (self.cls_ptrs_x3_last, self.reg_ptrs_x3_last) if last else (self.cls_ptrs_x3, self.reg_ptrs_x3)
         outs, cls, reg = ws['outs'][ll:], ws['cls'][ll:], ws['reg'][ll:]
-        if self.use_reg_layer:
+        nf = self.num_reg_fcs
+        if nf != 2:
+            # another branch depth: the depth-loop kernels (csrc/branch_depth.hip) on their own tables, the same launch structure
+            if self.use_reg_layer:
+                ops.heads_cls_depth_x3(outs, cls_p, cls, R, n, nf, num_classes=self.num_classes)
+                ops.reg_layer_depth_x3(outs, reg_p, ws['ref'], reg, R, n, nf, self.group_reg_dims, self.pc_range_h, dt, dt_rows=dt_rows)
+            else:
+                ops.heads_depth_x3(outs, cls_p, reg_p, ws['ref'], cls, reg, R, n, nf, self.pc_range_h, dt, dt_rows=dt_rows, num_classes=self.num_classes)
+        elif self.use_reg_layer:
             # RegLayer regression branches: the class branch alone through the fused kernel, the regression branch + tail through its own
             ops.heads_cls_x3(outs, cls_p, cls, R, n, num_classes=self.num_classes)
             ops.reg_layer_x3(outs, reg_p, ws['ref'], reg, R, n, self.group_reg_dims, self.pc_range_h, dt, dt_rows=dt_rows)
@@ -1029,7 +1115,7 @@ class HeadEngine:
         # frame scalars; anything else changing (RoI boxes, calibration tables, feature values) is data.  The route carries every option;
         # load_state() re-allocates the weights.
         gkey = (ptrs, 0 if payload is None else payload.data_ptr(), sc['pad_h'], sc['pad_w'], sc['max_rows'], self.num_classes, self.roi_size,
-                self.use_reg_layer, self.group_reg_dims, self._weights_version, rt)
+                self.use_reg_layer, self.group_reg_dims, self.num_reg_fcs, self._weights_version, rt)
         graphs = ws.setdefault('graphs', {})             # one graph per (input buffers, frame scalars): a producer that alternates between
         g = graphs.get(gkey)                             # a few static output buffers replays a few graphs, it does not re-capture
         if ws.pop('graph_stale', False):

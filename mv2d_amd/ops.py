@@ -4,6 +4,7 @@ streams.  Every wrapper enqueues on ``torch.cuda.current_stream()`` and never sy
 There is no CPU path here: tensors must live on a HIP device and the extension must be loadable.
 """
 import math
+import numbers
 
 import torch
 
@@ -406,6 +407,76 @@ def reg_layer_x3(outs, ptrs, ref, reg, M, L, group_reg_dims, pc_range_host, dt=0
     _req(outs, torch.float32, 'outs'); _req(ref, torch.float32, 'ref'); _req(reg, torch.float32, 'reg'); _req(dt_rows, torch.float32, 'dt_rows')
     check(_lib.load().mv2d_reg_layer_x3(_p(outs), ptrs, _p(ref), _p(reg), M, L, len(dims), (ctypes.c_int * len(dims))(*dims),
                                         pc_range_host.data_ptr(), float(dt), _p(dt_rows), _stream()), 'mv2d_reg_layer_x3')
+
+
+def check_num_reg_fcs(v, who):
+    """num_reg_fcs of the box head (hidden layers per prediction branch, RegLayer's shared_reg_fcs) as an int: 1, 2 or 3, the depths the branch
+    kernels take (csrc/branch_depth.hip; 2 is the shipped launch).  bools, floats and strings are refused, not converted."""
+    if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not 1 <= int(v) <= 3:
+        raise ValueError(f'{who}: num_reg_fcs must be an int in [1, 3] (hidden layers per prediction branch), got {v!r}')
+    return int(v)
+
+
+def _pack_x3_depth(W):
+    """fp32 [L,n,256,256] -> (hi, lo), each [L, n * 65536]: pack_x3 of every matrix, stacked layer-major"""
+    L, n = W.shape[0], W.shape[1]
+    return tuple(t.view(L, -1) for t in pack_x3_stack(W.reshape(L * n, 256, 256)))
+
+
+def pack_heads_depth(cls_w, cls_b, cls_lnw, cls_lnb, cls_wo, cls_bo, reg_w=None, reg_b=None, reg_wo=None, reg_bo=None):
+    """The weight tables of heads_depth_x3 / heads_cls_depth_x3 (include/mv2d_hip.h) from fp32 tensors stacked over the L decoder layers and the n
+    hidden layers: cls_w / reg_w [L,n,256,256], cls_b / cls_lnw / cls_lnb / reg_b [L,n,256], cls_wo [L,NC,256], cls_bo [L,NC], reg_wo [L,10,256],
+    reg_bo [L,10].  Returns (cls table of 7 tensors, reg table of 5 tensors or None without the regression arguments): keep them alive next to
+    the make_ptr_array of each."""
+    f = lambda t: t.to(torch.float32).contiguous()
+    check_num_reg_fcs(int(cls_w.shape[1]), 'pack_heads_depth')
+    cls_t = [*_pack_x3_depth(cls_w), f(cls_b), f(cls_lnw), f(cls_lnb), f(cls_wo), f(cls_bo)]
+    if reg_w is None:
+        return cls_t, None
+    assert reg_w.shape[:2] == cls_w.shape[:2], 'both branches have the same depth'
+    return cls_t, [*_pack_x3_depth(reg_w), f(reg_b), f(reg_wo), f(reg_bo)]
+
+
+def pack_reg_layer_depth(s_w, s_b, t1_w, t1_b, t2_w, t2_b):
+    """The weight table of reg_layer_depth_x3: shared layers s_w [L,n,256,256], s_b [L,n,256]; the task heads as in pack_reg_layer.  Returns the 8
+    tensors in table order."""
+    L, G = t1_w.shape[0], t1_w.shape[1]
+    check_num_reg_fcs(int(s_w.shape[1]), 'pack_reg_layer_depth')
+    t1 = [t.view(L, -1) for t in pack_x3_stack(t1_w.reshape(L * G, 256, 256))]
+    f = lambda t: t.to(torch.float32).contiguous()
+    return [*_pack_x3_depth(s_w), f(s_b), t1[0], t1[1], f(t1_b), f(t2_w), f(t2_b)]
+
+
+def _check_nc(num_classes, who):
+    num_classes = int(num_classes)
+    if not 1 <= num_classes <= 64:
+        raise ValueError(f'{who}: num_classes must be in [1, 64], got {num_classes}')
+    return num_classes
+
+
+def heads_depth_x3(outs, cls_ptrs, reg_ptrs, ref, cls, reg, M, L, n, pc_range_host, dt=0.0, eps=1e-5, dt_rows=None, num_classes=10):
+    """heads_fused_x3 with n = num_reg_fcs (1..3) hidden layers per branch; cls_ptrs / reg_ptrs: make_ptr_array of pack_heads_depth's tables."""
+    n, num_classes = check_num_reg_fcs(n, 'heads_depth_x3'), _check_nc(num_classes, 'heads_depth_x3')
+    for t, name in ((outs, 'outs'), (ref, 'ref'), (cls, 'cls'), (reg, 'reg'), (dt_rows, 'dt_rows')):
+        _req(t, torch.float32, name)
+    check(_lib.load().mv2d_heads_depth_x3(_p(outs), cls_ptrs, reg_ptrs, _p(ref), _p(cls), _p(reg), M, L, n, num_classes, float(eps),
+                                          pc_range_host.data_ptr(), float(dt), _p(dt_rows), _stream()), 'mv2d_heads_depth_x3')
+
+
+def heads_cls_depth_x3(outs, cls_ptrs, cls, M, L, n, eps=1e-5, num_classes=10):
+    """The class branch of heads_depth_x3 alone (cls bit for bit the same); the regression branch then runs through reg_layer_depth_x3."""
+    n, num_classes = check_num_reg_fcs(n, 'heads_cls_depth_x3'), _check_nc(num_classes, 'heads_cls_depth_x3')
+    _req(outs, torch.float32, 'outs'); _req(cls, torch.float32, 'cls')
+    check(_lib.load().mv2d_heads_cls_depth_x3(_p(outs), cls_ptrs, _p(cls), M, L, n, num_classes, float(eps), _stream()), 'mv2d_heads_cls_depth_x3')
+
+
+def reg_layer_depth_x3(outs, ptrs, ref, reg, M, L, n, group_reg_dims, pc_range_host, dt=0.0, dt_rows=None):
+    """reg_layer_x3 with n = num_reg_fcs (1..3) shared layers (ptrs: make_ptr_array(pack_reg_layer_depth(...)))."""
+    import ctypes
+    n, dims = check_num_reg_fcs(n, 'reg_layer_depth_x3'), check_group_reg_dims(group_reg_dims)
+    _req(outs, torch.float32, 'outs'); _req(ref, torch.float32, 'ref'); _req(reg, torch.float32, 'reg'); _req(dt_rows, torch.float32, 'dt_rows')
+    check(_lib.load().mv2d_reg_layer_depth_x3(_p(outs), ptrs, _p(ref), _p(reg), M, L, n, len(dims), (ctypes.c_int * len(dims))(*dims),
+                                              pc_range_host.data_ptr(), float(dt), _p(dt_rows), _stream()), 'mv2d_reg_layer_depth_x3')
 
 
 def ffn_pack_weights(W1, W2):

@@ -25,7 +25,7 @@ C = 256
 class RegLayer(nn.Module):
     """RH/bbox_heads/cross_attention_head.py:52-83: the regression branch of a decoder layer as shared layers + one task head per group of
     box-code columns.  Parameter names as in the reference: ``reg_branch.{0,3}`` (Linear, ReLU, Dropout per shared layer) and
-    ``task_heads.{g}.{0,2}``.  The module holds the parameters; the head evaluates it through mv2d_reg_layer_x3 (inference) or the autograd
+    ``task_heads.{g}.{0,2}`` (``reg_branch.{3i}`` for ``shared_reg_fcs`` = the head's ``num_reg_fcs`` shared layers).  The module holds the parameters; the head evaluates it through mv2d_reg_layer_x3 (inference) or the autograd
     operators (training), ``forward`` is the plain torch statement of it."""
 
     def __init__(self, embed_dims=256, shared_reg_fcs=2, group_reg_dims=(2, 1, 3, 2, 2), drop=0.0):
@@ -54,7 +54,9 @@ class CrossAttentionBoxHead(nn.Module):
                                  pc_range=[-51.2, -51.2, -5.0, 51.2, 51.2, 3.0], max_num=100, num_classes=10),
                  sync_cls_avg_factor=False, train_cfg=None, test_cfg=None, **kwargs):
         super().__init__()
-        assert not pre_embed and embed_dims == C and num_reg_fcs == 2, 'kernel path implements the shipped head configuration'
+        assert not pre_embed and embed_dims == C, 'kernel path implements the shipped head configuration'
+        # hidden layers per prediction branch (and RegLayer's shared layers): 1 to 3 (csrc/branch_depth.hip; 2 runs the shipped kernels)
+        self.num_reg_fcs = num_reg_fcs = ops.check_num_reg_fcs(num_reg_fcs, 'CrossAttentionBoxHead')
         # the box code has 10 columns; with use_reg_layer every group is one task head of the RegLayer (mv2d_reg_layer_x3: 1 to 10 groups)
         self.use_reg_layer = bool(use_reg_layer)
         self.group_reg_dims = ops.check_group_reg_dims(group_reg_dims) if self.use_reg_layer else tuple(group_reg_dims)
@@ -119,14 +121,15 @@ class CrossAttentionBoxHead(nn.Module):
         od = outs_dec.reshape(L, M, C).float().contiguous()
         st = lambda idx, attr: torch.stack([_f(getattr(br[idx], attr)) for br in self._cur]).contiguous()
         gk = dict(groups=L, a_gs=M * C, c_gs=M * C)
+        nf = self.num_reg_fcs
         self._cur = self.cls_branches
-        h1 = ops.gemm_f32(od, st(0, 'weight'), st(0, 'bias'), M=M, lda=C, ldc=C, **gk)
-        h2 = ops.row_ln(h1.view(L * M, C), ln=(st(1, 'weight'), st(1, 'bias')), relu=True, rows_per_group=M).view(L, M, C)
-        h1 = ops.gemm_f32(h2, st(3, 'weight'), st(3, 'bias'), M=M, lda=C, ldc=C, **gk)
-        h2 = ops.row_ln(h1.view(L * M, C), ln=(st(4, 'weight'), st(4, 'bias')), relu=True, rows_per_group=M).view(L, M, C)
+        h2 = od
+        for i in range(nf):              # class block i: Linear at 3i, LayerNorm at 3i + 1 (+ ReLU); the output Linear at 3 nf
+            h1 = ops.gemm_f32(h2, st(3 * i, 'weight'), st(3 * i, 'bias'), M=M, lda=C, ldc=C, **gk)
+            h2 = ops.row_ln(h1.view(L * M, C), ln=(st(3 * i + 1, 'weight'), st(3 * i + 1, 'bias')), relu=True, rows_per_group=M).view(L, M, C)
         NC = self.num_classes
         cls = torch.empty((L, M, NC), device=dev)
-        ops.gemm_f32(h2, st(6, 'weight'), st(6, 'bias'), out=cls, M=M, lda=C, ldc=NC, groups=L, a_gs=M * C, c_gs=M * NC)
+        ops.gemm_f32(h2, st(3 * nf, 'weight'), st(3 * nf, 'bias'), out=cls, M=M, lda=C, ldc=NC, groups=L, a_gs=M * C, c_gs=M * NC)
         ref = reference_points.reshape(M, 3).float().contiguous()
         pc_range_h = torch.tensor(self.pc_range, dtype=torch.float32)
         if self.use_reg_layer:
@@ -135,18 +138,24 @@ class CrossAttentionBoxHead(nn.Module):
             one = lambda name: torch.stack([_f(br.get_parameter(name)) for br in self.reg_branches])
             per_group = lambda fmt, join: torch.stack([join([_f(br.get_parameter(fmt.format(g))) for g in range(len(self.group_reg_dims))])
                                                        for br in self.reg_branches])
-            table = ops.pack_reg_layer(one('reg_branch.0.weight'), one('reg_branch.0.bias'), one('reg_branch.3.weight'), one('reg_branch.3.bias'),
-                                       per_group('task_heads.{}.0.weight', torch.stack), per_group('task_heads.{}.0.bias', torch.stack),
-                                       per_group('task_heads.{}.2.weight', torch.cat), per_group('task_heads.{}.2.bias', torch.cat))
+            heads = (per_group('task_heads.{}.0.weight', torch.stack), per_group('task_heads.{}.0.bias', torch.stack),
+                     per_group('task_heads.{}.2.weight', torch.cat), per_group('task_heads.{}.2.bias', torch.cat))
             reg = torch.empty((L, M, 10), device=dev)
-            ops.reg_layer_x3(od, ops.make_ptr_array(table), ref, reg, M, L, self.group_reg_dims, pc_range_h, 0.0)
+            if nf == 2:
+                table = ops.pack_reg_layer(one('reg_branch.0.weight'), one('reg_branch.0.bias'), one('reg_branch.3.weight'), one('reg_branch.3.bias'), *heads)
+                ops.reg_layer_x3(od, ops.make_ptr_array(table), ref, reg, M, L, self.group_reg_dims, pc_range_h, 0.0)
+            else:                        # shared block i at reg_branch.3i (Linear, ReLU, Dropout)
+                shared = lambda k: torch.stack([one(f'reg_branch.{3 * i}.{k}') for i in range(nf)], 1)
+                table = ops.pack_reg_layer_depth(shared('weight'), shared('bias'), *heads)
+                ops.reg_layer_depth_x3(od, ops.make_ptr_array(table), ref, reg, M, L, nf, self.group_reg_dims, pc_range_h, 0.0)
             all_cls_scores, all_bbox_preds = cls.view(L, bs, Q, NC), reg.view(L, bs, Q, 10)
             return (all_cls_scores, all_bbox_preds, outs_dec[-1]) if return_query_feats else (all_cls_scores, all_bbox_preds)
         self._cur = self.reg_branches
-        r1 = ops.gemm_f32(od, st(0, 'weight'), st(0, 'bias'), act=1, M=M, lda=C, ldc=C, **gk)
-        r2 = ops.gemm_f32(r1, st(2, 'weight'), st(2, 'bias'), act=1, M=M, lda=C, ldc=C, **gk)
+        r2 = od
+        for i in range(nf):              # regression block i: Linear at 2i (+ ReLU); the output Linear at 2 nf
+            r2 = ops.gemm_f32(r2, st(2 * i, 'weight'), st(2 * i, 'bias'), act=1, M=M, lda=C, ldc=C, **gk)
         reg = torch.empty((L, M, 10), device=dev)
-        ops.gemm_f32(r2, st(4, 'weight'), st(4, 'bias'), out=reg, M=M, lda=C, ldc=10, groups=L, a_gs=M * C, c_gs=M * 10)
+        ops.gemm_f32(r2, st(2 * nf, 'weight'), st(2 * nf, 'bias'), out=reg, M=M, lda=C, ldc=10, groups=L, a_gs=M * C, c_gs=M * 10)
         del self._cur
         ops.finalize_reg(reg, ref, L, M, pc_range_h, 0.0)
         all_cls_scores, all_bbox_preds = cls.view(L, bs, Q, NC), reg.view(L, bs, Q, 10)
@@ -273,6 +282,7 @@ class MV2DHead(nn.Module):
                                       iou_thr=bc.iou_thr, ratio=bc.ratio, num_classes=self.bbox_head.num_classes, roi_size=self.roi_cells,
                                       use_reg_layer=getattr(self.bbox_head, 'use_reg_layer', False),
                                       group_reg_dims=getattr(self.bbox_head, 'group_reg_dims', (2, 2, 1, 1, 2, 2)),
+                                      num_reg_fcs=getattr(self.bbox_head, 'num_reg_fcs', 2),
                                       masked_row=(self.test_cfg or {}).get('masked_row', 'nan'),
                                       query_generator=self.query_generator.shape,
                                       exact=(self.test_cfg or {}).get('index_exact', None))      # None: MV2D_EXACT decides

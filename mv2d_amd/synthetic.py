@@ -220,6 +220,53 @@ def with_reg_layer_state(sd, seed=0, group_reg_dims=(2, 2, 1, 1, 2, 2)):
     return out
 
 
+def with_branch_depth_state(sd, seed=0, n=2, group_reg_dims=None):
+    """A copy of a make_head_state dict whose prediction branches have ``n`` hidden layers (CrossAttentionBoxHead(num_reg_fcs=n)): class block i at
+    ``cls_branches.{l}.{3i, 3i+1}`` with the output layer at ``{3n}``; Sequential regression block i at ``reg_branches.{l}.{2i}`` with the output
+    layer at ``{2n}`` -- or, with ``group_reg_dims``, a RegLayer with shared block i at ``reg_branch.{3i}`` and make_reg_layer_state's task heads.
+    Only the ``bbox_head.cls_branches.*`` / ``bbox_head.reg_branches.*`` tensors are replaced (their own stream of draws, in their old place in the
+    dict); everything else is the input's, bit for bit.  The class count is the input's."""
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= int(n) <= 3:
+        raise ValueError(f'with_branch_depth_state: num_reg_fcs must be an int in [1, 3], got {n!r}')
+    n = int(n)
+    g = _rng(seed + 104729)
+    C = EMBED
+    layers = sorted({int(k.split('.')[2]) for k in sd if k.startswith('bbox_head.cls_branches.')})
+    last = max(int(k.split('.')[3]) for k in sd if k.startswith('bbox_head.cls_branches.0.'))
+    num_classes = int(sd[f'bbox_head.cls_branches.0.{last}.weight'].shape[0])
+    new = OrderedDict()
+    for l in layers:
+        p = f'bbox_head.cls_branches.{l}.'
+        for i in range(n):
+            new[f'{p}{3 * i}.weight'] = _xavier(g, (C, C)); new[f'{p}{3 * i}.bias'] = _bias(g, C)
+            new[f'{p}{3 * i + 1}.weight'], new[f'{p}{3 * i + 1}.bias'] = _ln(g, C)
+        # the class output layer like a trained head's, not like a freshly initialised one (make_head_state: bias_init_with_prob(0.01), every score
+        # near 0.01): logits spread around 0, so that the ranked scores of a frame lie further apart than the engine's logit bound can move them
+        new[f'{p}{3 * n}.weight'] = _xavier(g, (num_classes, C)) * np.float32(2.0)
+        new[f'{p}{3 * n}.bias'] = _bias(g, num_classes, 1.0)
+    for l in layers:
+        p = f'bbox_head.reg_branches.{l}.'
+        if group_reg_dims is not None:
+            for i in range(n):
+                new[f'{p}reg_branch.{3 * i}.weight'] = _xavier(g, (C, C)); new[f'{p}reg_branch.{3 * i}.bias'] = _bias(g, C)
+            for t, d in enumerate(group_reg_dims):
+                new[f'{p}task_heads.{t}.0.weight'] = _xavier(g, (C, C)); new[f'{p}task_heads.{t}.0.bias'] = _bias(g, C)
+                new[f'{p}task_heads.{t}.2.weight'] = _xavier(g, (CODE_SIZE, C))[:d].copy(); new[f'{p}task_heads.{t}.2.bias'] = _bias(g, d, 0.3)
+            continue
+        for i in range(n):
+            new[f'{p}{2 * i}.weight'] = _xavier(g, (C, C)); new[f'{p}{2 * i}.bias'] = _bias(g, C)
+        new[f'{p}{2 * n}.weight'] = _xavier(g, (CODE_SIZE, C)); new[f'{p}{2 * n}.bias'] = _bias(g, CODE_SIZE, 0.3)
+    out, placed = OrderedDict(), False
+    for k, v in sd.items():
+        if k.startswith(('bbox_head.cls_branches.', 'bbox_head.reg_branches.')):
+            if not placed:
+                out.update(new)
+                placed = True
+            continue
+        out[k] = v
+    return out
+
+
 def with_pe_depth_state(sd, seed=0, depth_num=DEPTH_NUM):
     """A copy of a make_head_state dict whose position_encoding.position_encoder.0.weight is a Xavier [1024, 3 * depth_num, 1, 1] tensor (the PE's
     ``depth_num`` key); its own stream of draws, make_head_state is untouched."""

@@ -254,6 +254,8 @@ class TrainDecoder:
         self.roi_head = roi_head
         # RegLayer regression branches (the head's use_reg_layer switch): the branches then run as per-operator autograd nodes, not as HeadsFn
         self.use_reg_layer, self.group_reg_dims = bool(getattr(bh, 'use_reg_layer', False)), tuple(getattr(bh, 'group_reg_dims', ()))
+        # hidden layers per branch (the head's num_reg_fcs): the fused HeadsFn node is built for 2; other depths take the per-operator nodes
+        self.num_reg_fcs = int(getattr(bh, 'num_reg_fcs', 2))
         self.layers = getattr(getattr(bh.transformer, 'decoder', None), 'layers', None)
         self._warned = False
         import os
@@ -408,7 +410,8 @@ class TrainDecoder:
         ln = lambda t, n: layer_norm(t, P[n + '.weight'], P[n + '.bias'])  # noqa: E731
         if torch.is_tensor(outs) and outs.shape[1] == 0:
             outs = list(outs.unbind(0))
-        if torch.is_tensor(outs) and self.use_reg_layer:
+        nf = self.num_reg_fcs
+        if torch.is_tensor(outs) and (self.use_reg_layer or nf != 2):
             outs = list(outs.unbind(0))
         if torch.is_tensor(outs):
             # (round 5) all branches of all layers as one autograd node, the layers side by side on streams (mv2d_train_heads_fwd / _bwd)
@@ -419,17 +422,21 @@ class TrainDecoder:
         all_cls, ts = [], []
         for l in range(self.L):
             c, g = f'bbox_head.cls_branches.{l}.', f'bbox_head.reg_branches.{l}.'
-            y = F.relu(ln(linear(outs[l], P[c + '0.weight'], P[c + '0.bias']), c + '1'))
-            y = F.relu(ln(linear(y, P[c + '3.weight'], P[c + '3.bias']), c + '4'))
-            all_cls.append(linear(y, P[c + '6.weight'], P[c + '6.bias']))
+            y = outs[l]
+            for i in range(nf):          # class block i: Linear at 3i, LayerNorm at 3i + 1, ReLU; the output Linear at 3 nf
+                y = F.relu(ln(linear(y, P[f'{c}{3 * i}.weight'], P[f'{c}{3 * i}.bias']), f'{c}{3 * i + 1}'))
+            all_cls.append(linear(y, P[f'{c}{3 * nf}.weight'], P[f'{c}{3 * nf}.bias']))
+            t = outs[l]
             if self.use_reg_layer:
-                # RegLayer (cross_attention_head.py:52-83): two shared linears, then one Linear-ReLU-Linear task head per group, concatenated
-                t = linear(linear(outs[l], P[g + 'reg_branch.0.weight'], P[g + 'reg_branch.0.bias'], 1), P[g + 'reg_branch.3.weight'], P[g + 'reg_branch.3.bias'], 1)
+                # RegLayer (cross_attention_head.py:52-83): nf shared linears, then one Linear-ReLU-Linear task head per group, concatenated
+                for i in range(nf):
+                    t = linear(t, P[f'{g}reg_branch.{3 * i}.weight'], P[f'{g}reg_branch.{3 * i}.bias'], 1)
                 ts.append(torch.cat([linear(linear(t, P[f'{g}task_heads.{k}.0.weight'], P[f'{g}task_heads.{k}.0.bias'], 1),
                                             P[f'{g}task_heads.{k}.2.weight'], P[f'{g}task_heads.{k}.2.bias']) for k in range(len(self.group_reg_dims))], -1))
                 continue
-            t = linear(outs[l], P[g + '0.weight'], P[g + '0.bias'], 1)
-            ts.append(linear(linear(t, P[g + '2.weight'], P[g + '2.bias'], 1), P[g + '4.weight'], P[g + '4.bias']))
+            for i in range(nf):          # regression block i: Linear at 2i, ReLU; the output Linear at 2 nf
+                t = linear(t, P[f'{g}{2 * i}.weight'], P[f'{g}{2 * i}.bias'], 1)
+            ts.append(linear(t, P[f'{g}{2 * nf}.weight'], P[f'{g}{2 * nf}.bias']))
         return torch.stack(all_cls), self._box_code(torch.stack(ts), ref, pad, dt)
 
     def _box_code(self, t, ref, pad, dt):
