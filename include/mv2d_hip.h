@@ -287,7 +287,7 @@ int mv2d_heads_cls_x3_nc(const float* outs, const void* const* cls_w, float* cls
 int mv2d_reg_layer_x3(const float* outs, const void* const* w, const float* ref, float* reg, int M, int L, int n_groups, const int* group_dims,
                       const float* pc_range, float dt, const float* dt_rows, void* stream);
 
-/* The prediction branches with n_fcs = 1, 2 or 3 hidden layers per branch (the reference head's num_reg_fcs; csrc/branch_depth.hip): the
+/* The prediction branches with n_fcs = 1, 2 or 3 hidden layers per branch (the reference head's num_reg_fcs; csrc/branches_x3.hip): the
  * launches above with the hidden Linear(256,256) (+ LayerNorm on the class branch) + ReLU blocks as a loop over n_fcs.  Hidden layers in split
  * precision, output layers in exact fp32, the same box-code tail.  Every table is stacked [L][n_fcs] (layer-major, then the block):
  *   cls_w = {w_hi, w_lo, b, ln_w, ln_b, w_out, b_out}: w_hi / w_lo [L][n_fcs] per-matrix mv2d_split_q16x2 + mv2d_pack_wfrag_bf16 copies,

@@ -362,8 +362,6 @@ __global__ __launch_bounds__(1024) void attn_out_fused_x3_kernel(AttnOutX3Params
     }
 }
 
-__device__ __forceinline__ float4 ln_row(float4 v, const float* __restrict__ w, const float* __restrict__ b, int c0, float eps);
-
 // Self-attention core + out_proj + residual + LayerNorm + cross-attention q projection for 16 queries in one block (16 waves):
 // the attention part is self_attn_kernel's (attention.hip: exact fp32 MFMA, S^T = K.Q^T, online softmax, P feeds P.V from registers)
 // with two waves per head splitting the key tiles; the merged context tile goes straight into the bf16 hi/lo LDS images that
@@ -522,15 +520,6 @@ struct FfnOutParams {
     const unsigned short* Wh; const unsigned short* Wl; const float* b_in; float* qkv;     // Wh null -> no in_proj (last layer)
     int M; float eps;
 };
-
-__device__ __forceinline__ float4 ln_row(float4 v, const float* __restrict__ w, const float* __restrict__ b, int c0, float eps) {
-    const float mean = wave_sum(v.x + v.y + v.z + v.w) * (1.0f / C);
-    const float dx = v.x - mean, dy = v.y - mean, dz = v.z - mean, dw = v.w - mean;
-    const float var = wave_sum(dx * dx + dy * dy + dz * dz + dw * dw) * (1.0f / C);
-    const float rstd = 1.0f / sqrtf(var + eps);
-    const float4 ww = *reinterpret_cast<const float4*>(w + c0), bb = *reinterpret_cast<const float4*>(b + c0);
-    return make_float4(dx * rstd * ww.x + bb.x, dy * rstd * ww.y + bb.y, dz * rstd * ww.z + bb.z, dw * rstd * ww.w + bb.w);
-}
 
 // (RT row tiles per block share the in_proj weight fragments, as in attn_out_fused_x3_kernel)
 template <int RT>
@@ -828,19 +817,7 @@ __global__ __launch_bounds__(256, 1) void heads_fused_kernel(HeadsParams p) {
         const int m = m0 + 4 * fg + r;
         if (m >= p.M) continue;
         float v = o[r] + b;
-        if (branch == 1) {
-            // cross_attention_head.py:219-238: add inverse_sigmoid(ref) to (cx, cy) and cz, sigmoid, de-normalise; T head: v / dt
-            if (fr == 0 || fr == 1 || fr == 4) {
-                const int k = fr == 4 ? 2 : fr;
-                const float x = fminf(fmaxf(p.ref[m * 3 + k], 0.f), 1.f);
-                const float is = logf(fmaxf(x, 1e-5f) / fmaxf(1.f - x, 1e-5f));
-                const float s = 1.f / (1.f + expf(-(v + is)));
-                v = fr == 0 ? s * p.pd0 + p.pc0 : (fr == 1 ? s * p.pd1 + p.pc1 : s * p.pd2 + p.pc2);
-            } else if (fr >= 8) {
-                const float dt = p.dt_rows ? p.dt_rows[m] : p.dt;
-                if (dt != 0.f) v = v / dt;
-            }
-        }
+        if (branch == 1) v = box_code_col(BoxTail{p.ref, p.pc0, p.pc1, p.pc2, p.pd0, p.pd1, p.pd2, p.dt, p.dt_rows}, v, m, fr);
         outp[((long long)l * p.M + m) * 10 + fr] = v;
     }
 }
@@ -1002,141 +979,6 @@ __global__ void split_rows_kernel(const float4* __restrict__ a, const float4* __
     lo[i] = l;
 }
 
-// The prediction branches in split precision (bf16x3): same chain as heads_fused_kernel with the four 256x256 linears of a
-// (layer, branch) on v_mfma_f32_16x16x32_bf16 (hi/lo pairs, ~1e-5 relative), 16 waves per block: wave w owns column tile w of a
-// linear and row w of the LayerNorm / ReLU stage; the 256 -> 10 output layer stays exact fp32.  (Profile of a 4-sample batch: the
-// exact-fp32 kernel spent 93 us in 2048-cycle MFMA chains per wave.)
-struct HeadsX3Params {
-    const float* outs;
-    const unsigned short* w0h; const unsigned short* w0l; const float* b0; const float* lnw1; const float* lnb1;
-    const unsigned short* w3h; const unsigned short* w3l; const float* b3; const float* lnw4; const float* lnb4;
-    const float* w6; const float* b6;
-    const unsigned short* r0h; const unsigned short* r0l; const float* rb0; const unsigned short* r2h; const unsigned short* r2l; const float* rb2;
-    const float* r4; const float* rb4;
-    const float* ref; float* cls; float* reg;
-    int M, L; float eps; float pc0, pc1, pc2, pd0, pd1, pd2, dt; const float* dt_rows;
-    int NC;                       // classes: w6 [L,NC,256], b6 [L,NC], cls [L,M,NC]
-};
-
-// RT row tiles (16 rows each) per block share one load of the weight fragments: with many rows (a batch of samples) the kernel is
-// bound by the L2 -> CU traffic of the weights (0.5 MB per block), not by the matrix pipe.
-// CT = 16-column tiles of the class output layer (NC <= 16 CT): wave w finishes row tile w % RT and class tile w / RT, so the waves that
-// sit idle behind the last 256x256 linear at CT = 1 carry the extra class tiles (RT * CT <= 16: up to 64 classes at RT = 4).
-// NCF = the class count as a compile-time constant (the 10-class launch: the instruction stream of the 10-class-only kernel), 0 = p.NC.
-template <int RT, int CT, int NCF>
-__global__ __launch_bounds__(1024) void heads_fused_x3_kernel(HeadsX3Params p) {
-    static_assert(RT * CT <= 16, "one wave per (row tile, class tile)");
-    __shared__ __attribute__((aligned(16))) unsigned char ah[RT * 16 * 512], al[RT * 16 * 512];
-    __shared__ __attribute__((aligned(16))) float tb[RT * 16 * C];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fr = lane & 15, fg = lane >> 4;
-    // the row blocks of one (layer, branch) run on ONE XCD: its 1 MB of weights is fetched by ~2 XCDs instead of all 8
-    const int lin = xcd_chunked(blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z), gridDim.x * gridDim.y * gridDim.z);
-    const int mb = (lin % gridDim.x) * (16 * RT), l = (lin / gridDim.x) % gridDim.y, branch = lin / (gridDim.x * gridDim.y);
-    const long long wo = (long long)l * C * C, bl = (long long)l * C;
-    const unsigned short* W1h = (branch == 0 ? p.w0h : p.r0h) + wo;
-    const unsigned short* W1l = (branch == 0 ? p.w0l : p.r0l) + wo;
-    const unsigned short* W2h = (branch == 0 ? p.w3h : p.r2h) + wo;
-    const unsigned short* W2l = (branch == 0 ? p.w3l : p.r2l) + wo;
-    const float* B1 = (branch == 0 ? p.b0 : p.rb0) + bl;
-    const float* B2 = (branch == 0 ? p.b3 : p.rb2) + bl;
-    float4 av[RT];
-#pragma unroll
-    for (int t = 0; t < RT; ++t)
-        av[t] = *reinterpret_cast<const float4*>(p.outs + ((long long)l * p.M + min(mb + 16 * t + wave, p.M - 1)) * C + lane * 4);
-    BFrag wh[8], wl[8];
-    load_w_x3(wh, wl, W1h, W1l, wave, lane);
-    const int aoff = wave * 512 + (((lane >> 1) ^ wave) << 4) + (lane & 1) * 8;     // this thread's 4 values in the bf16 images of a tile
-#pragma unroll
-    for (int t = 0; t < RT; ++t) {
-        uint2 hi, lo;
-        split4(av[t], hi, lo);
-        *reinterpret_cast<uint2*>(ah + t * 8192 + aoff) = hi;
-        *reinterpret_cast<uint2*>(al + t * 8192 + aoff) = lo;
-    }
-    __syncthreads();
-    const int col = wave * 16 + fr;
-    float* trow = tb + wave * C + ((lane ^ (wave & 15)) << 2);          // row = wave of a tile, columns 4 lane ..
-    // ---- linear 1 -> (LayerNorm) -> ReLU
-    f32x4_t acc[RT];
-#pragma unroll
-    for (int t = 0; t < RT; ++t) acc[t] = tile_mma_x3(ah + t * 8192, al + t * 8192, wh, wl, fr, fg);
-    load_w_x3(wh, wl, W2h, W2l, wave, lane);                            // in flight during the row stage
-    {
-        const float b = B1[col];
-#pragma unroll
-        for (int t = 0; t < RT; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) tb[t * 16 * C + toff(4 * fg + r, col)] = acc[t][r] + b;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int t = 0; t < RT; ++t) {
-        float4 v = *reinterpret_cast<float4*>(trow + t * 16 * C);
-        if (branch == 0) v = ln_row(v, p.lnw1 + bl, p.lnb1 + bl, lane * 4, p.eps);
-        v = make_float4(relu_f(v.x), relu_f(v.y), relu_f(v.z), relu_f(v.w));
-        uint2 hi, lo;
-        split4(v, hi, lo);
-        *reinterpret_cast<uint2*>(ah + t * 8192 + aoff) = hi;
-        *reinterpret_cast<uint2*>(al + t * 8192 + aoff) = lo;
-    }
-    __syncthreads();
-    // ---- linear 2 -> (LayerNorm) -> ReLU, kept as an fp32 tile for the output layer
-#pragma unroll
-    for (int t = 0; t < RT; ++t) acc[t] = tile_mma_x3(ah + t * 8192, al + t * 8192, wh, wl, fr, fg);
-    {
-        const float b = B2[col];
-#pragma unroll
-        for (int t = 0; t < RT; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) tb[t * 16 * C + toff(4 * fg + r, col)] = acc[t][r] + b;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int t = 0; t < RT; ++t) {
-        float4 v = *reinterpret_cast<float4*>(trow + t * 16 * C);
-        if (branch == 0) v = ln_row(v, p.lnw4 + bl, p.lnb4 + bl, lane * 4, p.eps);
-        *reinterpret_cast<float4*>(trow + t * 16 * C) = make_float4(relu_f(v.x), relu_f(v.y), relu_f(v.z), relu_f(v.w));
-    }
-    __syncthreads();
-    // the reg branch has one column tile (10 wide), the cls branch CT
-    if (wave >= (branch == 0 ? CT * RT : RT)) return;
-    const int rt = CT == 1 ? wave : wave % RT, ct = CT == 1 ? 0 : wave / RT;
-    const int m0 = mb + 16 * rt;                                        // wave w finishes row tile w % RT
-    if (m0 >= p.M) return;
-    const float* tbt = tb + rt * 16 * C;
-    // ---- final Linear(256 -> NC | 10): 16x16 tile ct, weight rows >= NC clamped and masked
-    const int nout = branch == 0 ? (NCF ? NCF : p.NC) : 10;
-    const float* wlast = branch == 0 ? p.w6 + (long long)l * nout * C : p.r4 + (long long)l * 10 * C;
-    const float* blast = branch == 0 ? p.b6 + l * nout : p.rb4 + l * 10;
-    float* outp = branch == 0 ? p.cls : p.reg;
-    const int n = 16 * ct + fr;                                         // this lane's output column
-    Frag f;
-    load_w(f, wlast, C, n, nout, fg);
-    const f32x4_t o = tile_mma(tbt, f, fr, fg);
-    if (n >= nout) return;
-    const float b = blast[n];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int m = m0 + 4 * fg + r;
-        if (m >= p.M) continue;
-        float v = o[r] + b;
-        if (branch == 1) {
-            // cross_attention_head.py:219-238: add inverse_sigmoid(ref) to (cx, cy) and cz, sigmoid, de-normalise; T head: v / dt
-            if (fr == 0 || fr == 1 || fr == 4) {
-                const int k = fr == 4 ? 2 : fr;
-                const float x = fminf(fmaxf(p.ref[m * 3 + k], 0.f), 1.f);
-                const float is = logf(fmaxf(x, 1e-5f) / fmaxf(1.f - x, 1e-5f));
-                const float sg = 1.f / (1.f + expf(-(v + is)));
-                v = fr == 0 ? sg * p.pd0 + p.pc0 : (fr == 1 ? sg * p.pd1 + p.pc1 : sg * p.pd2 + p.pc2);
-            } else if (fr >= 8) {
-                const float dt = p.dt_rows ? p.dt_rows[m] : p.dt;
-                if (dt != 0.f) v = v / dt;
-            }
-        }
-        outp[((long long)l * p.M + m) * nout + n] = v;
-    }
-}
-
 }  // namespace
 
 extern "C" int mv2d_pack_wfrag_f32(const float* W, float* Wp, int N, int K, int ldw, void* stream) {
@@ -1267,64 +1109,6 @@ extern "C" int mv2d_heads_fused(const float* outs, const float* const* cls_w, co
     hipLaunchKernelGGL(heads_fused_kernel, dim3(cdiv(M, 16), L, 2), dim3(256), 0, (hipStream_t)stream, p);
     MV2D_LAUNCH_CHECK();
     return MV2D_OK;
-}
-
-// branches = 2: the class and the regression branch (gridDim.z = 2); branches = 1: the class branch alone -- with gridDim.z = 1 the kernel's
-// `branch` is 0 in every block, which reads cls_w and writes cls only (reg_w, ref, reg, pc_range, dt are never touched and may be NULL)
-static int heads_x3_launch(const float* outs, const void* const* cls_w, const void* const* reg_w, const float* ref, float* cls, float* reg, int M,
-                           int L, int num_classes, float eps, const float* pc_range, float dt, const float* dt_rows, void* stream, int branches) {
-    // cls_w: {w0_hi,w0_lo,b0,lnw1,lnb1,w3_hi,w3_lo,b3,lnw4,lnb4,w6,b6}; reg_w: {w0_hi,w0_lo,b0,w2_hi,w2_lo,b2,w4,b4} device pointers,
-    // every tensor stacked over the L layers; the *_hi/_lo matrices are per-layer mv2d_split_bf16x2 + mv2d_pack_wfrag_bf16 copies
-    static const void* const no_reg_w[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    static const float no_range[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (branches == 2) {
-        MV2D_CHECK_ARG(outs && cls_w && reg_w && ref && cls && reg && pc_range && L > 0, "mv2d_heads_fused_x3: null pointer");
-    } else {
-        MV2D_CHECK_ARG(outs && cls_w && cls && L > 0, "mv2d_heads_cls_x3: null pointer");
-        reg_w = no_reg_w, pc_range = no_range, ref = nullptr, reg = nullptr, dt = 0.f, dt_rows = nullptr;
-    }
-    MV2D_CHECK_ARG(num_classes >= 1 && num_classes <= 64, "mv2d_heads_fused_x3: num_classes must be in [1, 64]");
-    for (int i = 0; i < 12; ++i) MV2D_CHECK_ARG(cls_w[i] != nullptr, "mv2d_heads_fused_x3: null cls weight");
-    for (int i = 0; i < 8 && branches == 2; ++i) MV2D_CHECK_ARG(reg_w[i] != nullptr, "mv2d_heads_fused_x3: null reg weight");
-    if (M == 0) return MV2D_OK;
-    typedef const unsigned short* U; typedef const float* Fp;
-    HeadsX3Params p{outs, (U)cls_w[0], (U)cls_w[1], (Fp)cls_w[2], (Fp)cls_w[3], (Fp)cls_w[4], (U)cls_w[5], (U)cls_w[6], (Fp)cls_w[7], (Fp)cls_w[8],
-                    (Fp)cls_w[9], (Fp)cls_w[10], (Fp)cls_w[11],
-                    (U)reg_w[0], (U)reg_w[1], (Fp)reg_w[2], (U)reg_w[3], (U)reg_w[4], (Fp)reg_w[5], (Fp)reg_w[6], (Fp)reg_w[7],
-                    ref, cls, reg, M, L, eps,
-                    pc_range[0], pc_range[1], pc_range[2], pc_range[3] - pc_range[0], pc_range[4] - pc_range[1], pc_range[5] - pc_range[2], dt, dt_rows,
-                    num_classes};
-    const int ct = num_classes == 10 ? 0 : (num_classes + 15) / 16;    // class column tiles (0: the 10-class instance)
-    const hipStream_t st = (hipStream_t)stream;
-#define MV2D_HEADS_X3(RT)                                                                                                             \
-    switch (ct) {                                                                                                                     \
-        case 0: hipLaunchKernelGGL((heads_fused_x3_kernel<RT, 1, 10>), dim3(cdiv(M, 16 * RT), L, branches), dim3(1024), 0, st, p); break;    \
-        case 1: hipLaunchKernelGGL((heads_fused_x3_kernel<RT, 1, 0>), dim3(cdiv(M, 16 * RT), L, branches), dim3(1024), 0, st, p); break;     \
-        case 2: hipLaunchKernelGGL((heads_fused_x3_kernel<RT, 2, 0>), dim3(cdiv(M, 16 * RT), L, branches), dim3(1024), 0, st, p); break;     \
-        case 3: hipLaunchKernelGGL((heads_fused_x3_kernel<RT, 3, 0>), dim3(cdiv(M, 16 * RT), L, branches), dim3(1024), 0, st, p); break;     \
-        default: hipLaunchKernelGGL((heads_fused_x3_kernel<RT, 4, 0>), dim3(cdiv(M, 16 * RT), L, branches), dim3(1024), 0, st, p); break;    \
-    }
-    if (M <= 512) { MV2D_HEADS_X3(1) }
-    else if (M <= 1024) { MV2D_HEADS_X3(2) }
-    else { MV2D_HEADS_X3(4) }
-#undef MV2D_HEADS_X3
-    MV2D_LAUNCH_CHECK();
-    return MV2D_OK;
-}
-
-extern "C" int mv2d_heads_fused_x3_nc(const float* outs, const void* const* cls_w, const void* const* reg_w, const float* ref, float* cls,
-                                      float* reg, int M, int L, int num_classes, float eps, const float* pc_range, float dt, const float* dt_rows,
-                                      void* stream) {
-    return heads_x3_launch(outs, cls_w, reg_w, ref, cls, reg, M, L, num_classes, eps, pc_range, dt, dt_rows, stream, 2);
-}
-
-extern "C" int mv2d_heads_cls_x3_nc(const float* outs, const void* const* cls_w, float* cls, int M, int L, int num_classes, float eps, void* stream) {
-    return heads_x3_launch(outs, cls_w, nullptr, nullptr, cls, nullptr, M, L, num_classes, eps, nullptr, 0.f, nullptr, stream, 1);
-}
-
-extern "C" int mv2d_heads_fused_x3(const float* outs, const void* const* cls_w, const void* const* reg_w, const float* ref, float* cls, float* reg,
-                                   int M, int L, float eps, const float* pc_range, float dt, const float* dt_rows, void* stream) {
-    return mv2d_heads_fused_x3_nc(outs, cls_w, reg_w, ref, cls, reg, M, L, 10, eps, pc_range, dt, dt_rows, stream);
 }
 
 extern "C" int mv2d_linear_x3_ex(const float* A, const float* A2, int n_split, int lda, const void* Whi, const void* Wlo, const float* bias,

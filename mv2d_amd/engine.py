@@ -74,8 +74,8 @@ class HeadEngine:
         # key layout has to agree (load_state), and it is part of the graph key.
         self.use_reg_layer = bool(use_reg_layer)
         self.group_reg_dims = ops.check_group_reg_dims(group_reg_dims) if self.use_reg_layer else tuple(group_reg_dims)
-        # hidden layers per prediction branch (the head's num_reg_fcs; RegLayer's shared layers): 2 launches the shipped kernels with the shipped
-        # tables, 1 and 3 the depth-loop kernels of csrc/branch_depth.hip.  Fixed per engine: the state dict's branches have to have that depth.
+        # hidden layers per prediction branch (the head's num_reg_fcs; RegLayer's shared layers): 2 launches the first entries with their per-layer
+        # tables, 1 and 3 the depth entries with [L][n] tables (csrc/branches_x3.hip: one kernel pair behind both).  Fixed per engine: the state dict's branches have to have that depth.
         self.num_reg_fcs = ops.check_num_reg_fcs(num_reg_fcs, 'HeadEngine')
         # the PE's depth_num / depth_start / position_range (MU/pe.py:52-63).  Every consumer of the frustum rows takes them with Kp = pe_kp(depth_num)
         # columns (3 * depth_num zero-padded to a multiple of 32) and position_encoder.0.weight zero-padded to [1024, Kp]: one instance of the fused PE
@@ -1017,7 +1017,7 @@ class HeadEngine:
         outs, cls, reg = ws['outs'][ll:], ws['cls'][ll:], ws['reg'][ll:]
         nf = self.num_reg_fcs
         if nf != 2:
-            # another branch depth: the depth-loop kernels (csrc/branch_depth.hip) on their own tables, the same launch structure
+            # another branch depth: the depth entries (csrc/branches_x3.hip) on their own tables, the same launch structure
             if self.use_reg_layer:
                 ops.heads_cls_depth_x3(outs, cls_p, cls, R, n, nf, num_classes=self.num_classes)
                 ops.reg_layer_depth_x3(outs, reg_p, ws['ref'], reg, R, n, nf, self.group_reg_dims, self.pc_range_h, dt, dt_rows=dt_rows)

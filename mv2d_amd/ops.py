@@ -411,7 +411,7 @@ def reg_layer_x3(outs, ptrs, ref, reg, M, L, group_reg_dims, pc_range_host, dt=0
 
 def check_num_reg_fcs(v, who):
     """num_reg_fcs of the box head (hidden layers per prediction branch, RegLayer's shared_reg_fcs) as an int: 1, 2 or 3, the depths the branch
-    kernels take (csrc/branch_depth.hip; 2 is the shipped launch).  bools, floats and strings are refused, not converted."""
+    kernels take (csrc/branches_x3.hip; 2 is the shipped launch).  bools, floats and strings are refused, not converted."""
     if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not 1 <= int(v) <= 3:
         raise ValueError(f'{who}: num_reg_fcs must be an int in [1, 3] (hidden layers per prediction branch), got {v!r}')
     return int(v)

@@ -55,7 +55,7 @@ class CrossAttentionBoxHead(nn.Module):
                  sync_cls_avg_factor=False, train_cfg=None, test_cfg=None, **kwargs):
         super().__init__()
         assert not pre_embed and embed_dims == C, 'kernel path implements the shipped head configuration'
-        # hidden layers per prediction branch (and RegLayer's shared layers): 1 to 3 (csrc/branch_depth.hip; 2 runs the shipped kernels)
+        # hidden layers per prediction branch (and RegLayer's shared layers): 1 to 3 (csrc/branches_x3.hip; 2 runs the shipped entries)
         self.num_reg_fcs = num_reg_fcs = ops.check_num_reg_fcs(num_reg_fcs, 'CrossAttentionBoxHead')
         # the box code has 10 columns; with use_reg_layer every group is one task head of the RegLayer (mv2d_reg_layer_x3: 1 to 10 groups)
         self.use_reg_layer = bool(use_reg_layer)
@@ -133,7 +133,7 @@ class CrossAttentionBoxHead(nn.Module):
         ref = reference_points.reshape(M, 3).float().contiguous()
         pc_range_h = torch.tensor(self.pc_range, dtype=torch.float32)
         if self.use_reg_layer:
-            # the RegLayer branches + the box-code tail in one launch (csrc/reglayer.hip)
+            # the RegLayer branches + the box-code tail in one launch (csrc/branches_x3.hip)
             del self._cur
             one = lambda name: torch.stack([_f(br.get_parameter(name)) for br in self.reg_branches])
             per_group = lambda fmt, join: torch.stack([join([_f(br.get_parameter(fmt.format(g))) for g in range(len(self.group_reg_dims))])

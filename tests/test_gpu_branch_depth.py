@@ -1,4 +1,4 @@
-"""Branch depth (CrossAttentionBoxHead(num_reg_fcs=1..3)) on the GPU (-m gpu): the depth-loop kernels of csrc/branch_depth.hip against fp64
+"""Branch depth (CrossAttentionBoxHead(num_reg_fcs=1..3)) on the GPU (-m gpu): the depth entries of csrc/branches_x3.hip against fp64
 restatements and, at depth 2, bit for bit against the shipped launches; the engine against goldens of the unmodified reference built with the key
 (tests/golden/branch_depth_*.npz, tools/gen_golden_branch_depth.py); engine consistency, the plugin head and both training routes.
 
