@@ -146,6 +146,17 @@ int mv2d_pe_fused_x3_k(const float* A1, const void* Xmap, const int* row_index, 
                        const void* Wr_hi, const void* Wr_lo, const float* br, const void* We_hi, const void* We_lo, const float* be,
                        const float* sine_tab, int tab_period, float* pe, void* Xk_hi, void* Xk_lo, void* Xv_hi, void* Xv_lo, int lo_fmt, int pe_at_index,
                        int* lo8_flag, int map_fmt, int Kp, void* stream);
+/* mv2d_pe_fused_x3_k WITHOUT the feature-guided gate (the reference PE's default with_fpe=False: no fpe submodule, MU/pe.py:81-82, 158-159):
+ * pe = sine_tab[position] + position_encoder(A1), the key / value rows as above.  No Wr / We / br / be operands; the arithmetic of position_encoder is
+ * that of mv2d_pe_fused_x3_k step for step (its result is bit for bit the P1 the gated kernel multiplies by its gate), the schedule ends after it:
+ * 4 * (Kp / 32 + 8) k-steps instead of + 16, no gate weights streamed, the feature tile never staged.  The feature rows are read for the key / value
+ * row outputs only: Xmap may be NULL exactly when the four row outputs are NULL (the S path's pe-only launch).  One instance per Kp / 32 in 1 .. 8
+ * and map format; any other Kp is an argument error.  A PE without the sine branch (no_sin_enc=True) passes one all-zero table row with
+ * tab_period = 1 to this entry or to the gated ones. */
+int mv2d_pe_fused_x3_ng(const float* A1, const void* Xmap, const int* row_index, const int* m_dev, int M,
+                        const void* W1a_hi, const void* W1a_lo, const float* b1a, const void* W1b_hi, const void* W1b_lo, const float* b1b,
+                        const float* sine_tab, int tab_period, float* pe, void* Xk_hi, void* Xk_lo, void* Xv_hi, void* Xv_lo,
+                        int lo_fmt, int pe_at_index, int* lo8_flag, int map_fmt, int Kp, void* stream);
 /* The same block on the second shape of the kernel (round 6, csrc/pe_x3b.hip): a wave owns 16 rows through both layers of each MLP, the hidden layer
  * stays in registers (no LDS image, no barrier between the layers), the weights go through a 4-deep LDS ring (LDS-DMA) shared by the 8 waves of a 128-row
  * block, two waves per SIMD.  Same operands EXCEPT that W1a and Wr (the first layers) are packed from the weight with its rows in the order

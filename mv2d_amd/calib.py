@@ -76,17 +76,22 @@ def geometry_tables_batch(metas_list):
 
 
 def shape_tables(shapes, h, w, stride=16, depth_num=64, depth_start=1, position_range=(-61.2, -61.2, -10.0, 61.2, 61.2, 10.0),
-                 eps=1e-6, scale=2 * math.pi):
+                 eps=1e-6, scale=2 * math.pi, lid=True):
     """The part that depends only on the padding geometry of the rig — shapes = ((pad_h, pad_w), ((img_h, img_w) per view)) — and on
     the map size: frustum tables, padding mask, the cumsum embeds of SinePositionalEncoding3D.  Constant for a deployment; callers
-    cache it by its arguments (the ones-image it interpolates is V x pad_h x pad_w floats)."""
+    cache it by its arguments (the ones-image it interpolates is V x pad_h x pad_w floats).  lid: the PE's ``LID`` key -- True: linear-increasing
+    depth bins, False: uniform bins (MU/pe.py:96-104), both in fp64."""
     (pad_h, pad_w), img_shapes = shapes
     V = len(img_shapes)
     coords_h = (torch.arange(h).double() + 0.5) * pad_h / h - 0.5
     coords_w = (torch.arange(w).double() + 0.5) * pad_w / w - 0.5
     index = torch.arange(0, depth_num, 1).double()
-    bin_size = (position_range[3] - depth_start) / (depth_num * (1 + depth_num))
-    coords_d = depth_start + bin_size * index * (index + 1)
+    if lid:
+        bin_size = (position_range[3] - depth_start) / (depth_num * (1 + depth_num))
+        coords_d = depth_start + bin_size * index * (index + 1)
+    else:
+        bin_size = (position_range[3] - depth_start) / depth_num
+        coords_d = depth_start + bin_size * index
     m = torch.ones((1, V, pad_h, pad_w), dtype=torch.float32)
     for i in range(V):
         ih, iw = img_shapes[i]
@@ -113,8 +118,8 @@ def meta_shapes(img_metas):
 
 
 def frame_tables(img_metas, h, w, stride=16, depth_num=64, depth_start=1, position_range=(-61.2, -61.2, -10.0, 61.2, 61.2, 10.0),
-                 eps=1e-6, scale=2 * math.pi):
+                 eps=1e-6, scale=2 * math.pi, lid=True):
     """Host tensors for one frame (dict of contiguous CPU tensors): geometry_tables + shape_tables."""
     out = geometry_tables(img_metas)
-    out.update(shape_tables(meta_shapes(img_metas), h, w, stride, depth_num, depth_start, position_range, eps, scale))
+    out.update(shape_tables(meta_shapes(img_metas), h, w, stride, depth_num, depth_start, position_range, eps, scale, lid))
     return out

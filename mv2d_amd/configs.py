@@ -103,6 +103,17 @@ def _set_pe_depth(d, depth_num, depth_start, position_range):
     return d
 
 
+def _set_pe_options(d, with_fpe, no_sin_enc, adapt_pos3d, LID):
+    # the reference PE's four switches (MU/pe.py:51-82; ops.check_pe_options lists what is accepted).  The shipped configs set with_fpe=True and leave the
+    # other three at the PE's defaults (no key): the defaults here give exactly that dict
+    from . import ops
+    ops.check_pe_options(with_fpe, no_sin_enc, adapt_pos3d, LID, 'configs')
+    for key, v in (('with_fpe', with_fpe), ('no_sin_enc', no_sin_enc), ('adapt_pos3d', adapt_pos3d), ('LID', LID)):
+        if v != ops.PE_OPTION_DEFAULTS[key]:
+            d['pe'][key] = v
+    return d
+
+
 def _set_query_generator(d, query_generator):
     # keys of the reference QueryGenerator (RH/utils/query_generator.py:20-67) laid over the shipped subtree: num_shared_convs, num_shared_fcs,
     # num_center_fcs, fc_out_channels, with_avg_pool, extra_encoding (replaced as a whole).  None leaves the shipped subtree as it is
@@ -128,29 +139,31 @@ def _set_num_reg_fcs(d, num_reg_fcs):
 
 
 def roi_head_cfg_s(num_classes=10, roi_size=ROI_SIZE, reg_layer_dims=None, depth_num=64, depth_start=1, position_range=None, query_generator=None,
-                   num_reg_fcs=2):
+                   num_reg_fcs=2, with_fpe=True, no_sin_enc=False, adapt_pos3d=True, LID=True):
     """CFG-S:40-121 (MV2D-S single frame); ``num_classes`` sets ``bbox_head.num_classes`` and ``bbox_head.bbox_coder.num_classes``,
     ``roi_size`` sets ``bbox_roi_extractor.roi_layer.output_size`` and ``query_generator.roi_feat_size``; ``reg_layer_dims`` (a tuple of
     group widths) sets ``bbox_head.use_reg_layer=True`` with that ``group_reg_dims``; ``depth_num`` (a multiple of 8 in [8, 80]), ``depth_start``
     and ``position_range`` (None: the shipped POST_RANGE) set the keys of the same names in ``pe``; ``query_generator`` (a dict of the reference
     QueryGenerator's own keys: mv2d_amd/qg_shape.py lists the accepted values) is laid over the ``query_generator`` subtree; ``num_reg_fcs`` (1, 2
-    or 3) sets ``bbox_head.num_reg_fcs``, alone or together with ``reg_layer_dims`` (2, the head's default: no key)."""
+    or 3) sets ``bbox_head.num_reg_fcs``, alone or together with ``reg_layer_dims`` (2, the head's default: no key); ``with_fpe``, ``no_sin_enc``,
+    ``adapt_pos3d`` and ``LID`` set the ``pe`` keys of the same names (a key left at the shipped value is not added; ``adapt_pos3d=False`` needs
+    ``no_sin_enc=True``)."""
     d = dict(type='MV2DSHead', use_denoise=False)
     d.update(_common(with_cp=False))
     d['box_correlation'] = dict(correlation_mode='topk_matched:1:0.0:0.0')
-    d = _set_query_generator(_set_pe_depth(d, depth_num, depth_start, position_range), query_generator)
+    d = _set_query_generator(_set_pe_options(_set_pe_depth(d, depth_num, depth_start, position_range), with_fpe, no_sin_enc, adapt_pos3d, LID), query_generator)
     return copy.deepcopy(_set_num_reg_fcs(_set_reg_layer(_set_roi_size(_set_num_classes(d, num_classes), roi_size), reg_layer_dims), num_reg_fcs))
 
 
 def roi_head_cfg_t(num_classes=10, roi_size=ROI_SIZE, reg_layer_dims=None, depth_num=64, depth_start=1, position_range=None, query_generator=None,
-                   num_reg_fcs=2):
-    """CFG-T:40-125 (MV2D-T two frames); ``num_classes``, ``roi_size``, ``reg_layer_dims``, the three ``pe`` keys, ``query_generator`` and ``num_reg_fcs``
-    as in ``roi_head_cfg_s``."""
+                   num_reg_fcs=2, with_fpe=True, no_sin_enc=False, adapt_pos3d=True, LID=True):
+    """CFG-T:40-125 (MV2D-T two frames); ``num_classes``, ``roi_size``, ``reg_layer_dims``, the three ``pe`` keys, ``query_generator``, ``num_reg_fcs``
+    and the PE's four switches as in ``roi_head_cfg_s``."""
     d = dict(type='MV2DTHead', use_denoise=True, neg_bbox_loss=True,
              denoise_noise_scale=1.25, denoise_split=0.6)
     d.update(_common(with_cp=True))
     d['box_correlation'] = dict(expand_stride=2, correlation_mode='topk_matched:20:0.0:0.0')
-    d = _set_query_generator(_set_pe_depth(d, depth_num, depth_start, position_range), query_generator)
+    d = _set_query_generator(_set_pe_options(_set_pe_depth(d, depth_num, depth_start, position_range), with_fpe, no_sin_enc, adapt_pos3d, LID), query_generator)
     return copy.deepcopy(_set_num_reg_fcs(_set_reg_layer(_set_roi_size(_set_num_classes(d, num_classes), roi_size), reg_layer_dims), num_reg_fcs))
 
 

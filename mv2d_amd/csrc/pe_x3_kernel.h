@@ -15,7 +15,8 @@
 // columns through LDS, the gate LAST.  hi and lo images of the input tile and of the hidden tile live side by side in LDS (128 KB): one
 // block per CU, one wave per SIMD (<= 512 registers), 48 MFMAs per k-step per wave -- the kernel is matrix-pipe bound by construction
 // (3 x the MFMAs of the default kernel on the same loads).
-// (this header: the kernel; pe_x3.hip: the 64-bin instance and the C entries; pe_x3_d1.hip / pe_x3_d2.hip: the instances of the other depths)
+// (this header: the kernel; pe_x3.hip: the 64-bin instance and the C entries; pe_x3_d1.hip / pe_x3_d2.hip: the instances of the other depths;
+// pe_x3_ng1.hip / pe_x3_ng2.hip: the instances of the gate-less kernel pe_x3_nogate_kernel<MT, KS1>, the PE built with with_fpe=False)
 #pragma once
 #include "common.h"
 
@@ -42,6 +43,9 @@ struct PeX3ParamsT {
 // compiles the three files side by side): each launches pe_x3_depth_kernel<MT, ks1> on `blocks` blocks, or returns false for a ks1 it does not hold.
 template <class MT> bool mv2d_px_launch_d1(const PeX3ParamsT<MT>& p, int ks1, int blocks, hipStream_t stream);
 template <class MT> bool mv2d_px_launch_d2(const PeX3ParamsT<MT>& p, int ks1, int blocks, hipStream_t stream);
+// The same for the gate-less kernel pe_x3_nogate_kernel<MT, ks1> (pe_x3_ng1.hip: KS1 = 1 .. 4, pe_x3_ng2.hip: KS1 = 5 .. 8); p's Wr / We / br / be are not read.
+template <class MT> bool mv2d_px_launch_ng1(const PeX3ParamsT<MT>& p, int ks1, int blocks, hipStream_t stream);
+template <class MT> bool mv2d_px_launch_ng2(const PeX3ParamsT<MT>& p, int ks1, int blocks, hipStream_t stream);
 
 namespace {
 
@@ -66,20 +70,22 @@ struct XFrag { uint4 h, l; };
 // (1 .. 8 for depth_num 8 .. 80; 6 = the 64 bins of the shipped configs: 72 steps).  The ring runs RING - 1 steps ahead of the MFMAs whatever
 // layer those steps belong to (at KS1 = 1 the prologue's second load is already a W1b fragment); the hidden-image barriers of layer1 order LDS
 // accesses only, so they hold for every KS1.
-template <int KS1> struct Sched {
+// GATE = false (pe_x3_nogate_kernel): the schedule ends after part 3 -- NSTEP = 4 PER, no step belongs to a part 4, the ring stops at the end of W1b.
+template <int KS1, bool GATE = true> struct Sched {
     static_assert(KS1 >= 1 && KS1 <= 8, "the frustum image is at most the 256 columns of an LDS image");
-    static constexpr int PER = KS1 + 8, NSTEP = 4 * PER + 16;
-    static constexpr int part_of(int T) { return T < 4 * PER ? T / PER : 4; }
+    static constexpr int PER = KS1 + 8, NSTEP = 4 * PER + (GATE ? 16 : 0);
+    static constexpr int part_of(int T) { return T < 4 * PER ? T / PER : 4; }          // (4 only for T >= 4 PER: never below NSTEP without the gate)
     static constexpr int first_of(int p) { return p * PER; }
     static constexpr int ks1_of(int p) { return p == 4 ? 8 : KS1; }
 };
 
 struct WBase { const unsigned short* wr[2]; const unsigned short* we[2]; const unsigned short* w1a[2]; const unsigned short* w1b[2]; };   // [hi, lo], + lane * 8 + wave * CT tiles
 
-template <int KS1, int T>
+template <int KS1, int T, bool GATE = true>
 __device__ __forceinline__ long long step_off() {
-    using S = Sched<KS1>;
+    using S = Sched<KS1, GATE>;
     constexpr int p = S::part_of(T), t = T - S::first_of(p), ks1 = S::ks1_of(p);
+    static_assert(GATE || p < 4, "the gate-less schedule has no part 4");
     if constexpr (p == 4) {
         if constexpr (t < ks1) return (long long)(t * 16) * 512;                               // Wr  [ks][16 tiles]
         else return (long long)((t - ks1) * 16) * 512;                                         // We  [ks][16 tiles]
@@ -88,19 +94,19 @@ __device__ __forceinline__ long long step_off() {
         else return (long long)((p * 8 + (t - ks1)) * 16) * 512;                               // W1b [32 k-steps][16 tiles]
     }
 }
-template <int KS1, int T>
+template <int KS1, int T, bool GATE = true>
 __device__ __forceinline__ const unsigned short* step_base(const WBase& w, int part) {
-    using S = Sched<KS1>;
+    using S = Sched<KS1, GATE>;
     constexpr int p = S::part_of(T), t = T - S::first_of(p), ks1 = S::ks1_of(p);
     if constexpr (p == 4) return t < ks1 ? w.wr[part] : w.we[part];
     else return t < ks1 ? w.w1a[part] : w.w1b[part];
 }
 
-template <int KS1, int T>
+template <int KS1, int T, bool GATE = true>
 __device__ __forceinline__ void ring_load(XFrag (&wq)[RING][CT], const WBase& w) {
-    if constexpr (T < Sched<KS1>::NSTEP) {
-        const unsigned short* ph = step_base<KS1, T>(w, 0) + step_off<KS1, T>();
-        const unsigned short* pl = step_base<KS1, T>(w, 1) + step_off<KS1, T>();
+    if constexpr (T < Sched<KS1, GATE>::NSTEP) {
+        const unsigned short* ph = step_base<KS1, T, GATE>(w, 0) + step_off<KS1, T, GATE>();
+        const unsigned short* pl = step_base<KS1, T, GATE>(w, 1) + step_off<KS1, T, GATE>();
 #pragma unroll
         for (int j = 0; j < CT; ++j) {
             wq[T % RING][j].h = *reinterpret_cast<const uint4*>(ph + 512 * j);
@@ -119,12 +125,12 @@ __device__ __forceinline__ void load_a(XFrag (&a)[RT], const unsigned char* Lh, 
 }
 
 // N k-steps of one layer.  The activation fragments of step K + 1 are read from LDS before the MFMAs of step K issue.
-template <int KS1, int T0, int N, int K = 0>
+template <int KS1, int T0, int N, int K = 0, bool GATE = true>
 __device__ __forceinline__ void steps(f32x4_t (&acc)[RT][CT], XFrag (&wq)[RING][CT], XFrag (&a)[2][RT], const WBase& w, const unsigned char* Lh,
                                       const unsigned char* Ll, int fr, int fg) {
     if constexpr (K < N) {
         if constexpr (K == 0) load_a(a[0], Lh, Ll, 0, fr, fg);
-        ring_load<KS1, T0 + K + RING - 1>(wq, w);
+        ring_load<KS1, T0 + K + RING - 1, GATE>(wq, w);
         if constexpr (K + 1 < N) load_a(a[(K + 1) & 1], Lh, Ll, K + 1, fr, fg);
         __builtin_amdgcn_sched_barrier(0);             // the loads stay ahead of the MFMAs
         // product-major: 16 independent MFMAs between two that accumulate into the same tile (a dependent MFMA waits ~8 passes for its input)
@@ -139,7 +145,7 @@ __device__ __forceinline__ void steps(f32x4_t (&acc)[RT][CT], XFrag (&wq)[RING][
                     acc[i][j] = mfma_q16_16x16x32(t == 0 ? wf.l : wf.h, t == 1 ? af.l : af.h, acc[i][j]);
                 }
         __builtin_amdgcn_sched_barrier(0);
-        steps<KS1, T0, N, K + 1>(acc, wq, a, w, Lh, Ll, fr, fg);
+        steps<KS1, T0, N, K + 1, GATE>(acc, wq, a, w, Lh, Ll, fr, fg);
     }
 }
 
@@ -157,12 +163,12 @@ __device__ __forceinline__ void split4(float a, float b, float c, float d, uint2
 
 // layer 1 of part P into the hidden images: lane (fr, fg) holds hidden columns lcol..lcol+3 of row 16 i + fr -> bias, ReLU, hi / lo split,
 // two 8-byte writes.  A barrier before the stores waits for the previous part's layer 2 (one hidden buffer), one after completes the tile.
-template <int KS1, int P>
+template <int KS1, int P, bool GATE = true>
 __device__ __forceinline__ void layer1(XFrag (&wq)[RING][CT], XFrag (&a)[2][RT], const WBase& w, const unsigned char* Ah, const unsigned char* Al,
                                        unsigned char* Hh, unsigned char* Hl, const float* bias /* LDS, this part's 256 */, int wave, int fr, int fg) {
     f32x4_t acc1[RT][CT];
     zero_acc(acc1);
-    steps<KS1, Sched<KS1>::first_of(P), KS1>(acc1, wq, a, w, Ah, Al, fr, fg);
+    steps<KS1, Sched<KS1, GATE>::first_of(P), KS1, 0, GATE>(acc1, wq, a, w, Ah, Al, fr, fg);
     if constexpr (P > 0 && P < 4) __syncthreads();   // (the gate's layer 1 follows a block barrier anyway)
 #pragma unroll
     for (int j = 0; j < CT; ++j) {
@@ -257,6 +263,138 @@ template <class MT, int KS1>
 __global__ __launch_bounds__(NTHR, 1) void pe_x3_depth_kernel(PeX3ParamsT<MT> p) {
     using S = Sched<KS1>;
 #include "pe_x3_body.inc"
+}
+
+// The PE built with with_fpe=False (MU/pe.py:81-82, 158-159: no fpe submodule): pe = tab[position] + position_encoder(A1), no gate.  Parts 0..3 are the
+// calls of the body above in the same order on the same accumulator (P1 is bit for bit the gated kernel's), the schedule ends there (Sched<KS1, false>:
+// 4 (KS1 + 8) k-steps, 56 instead of 72 at 64 bins; the ring stops after the last W1b fragment), the feature tile is never staged into the A images, Wr / We
+// / br / be are never read, the bias block in LDS is [b1a | b1b].  The feature rows are read in the output phase only, and only for the key / value row
+// outputs: without them (S path) Xmap may be NULL.  No early touch of the tile's feature lines (MV2D_PX_TOUCH above): measured with and without on the
+// rows of a 16-sample cfg3_t launch it moves the launch by -1.0 % .. +0.6 %, inside the spread of repeats (profiles/pe_options_kernel_stats.txt).
+enum { NG_1A = 0, NG_1B = 1024, NG_FLOATS = 1280 };
+constexpr int SMEM_NG = 4 * IMG + NG_FLOATS * 4;
+
+template <class MT, int KS1>
+__global__ __launch_bounds__(NTHR, 1) void pe_x3_nogate_kernel(PeX3ParamsT<MT> p) {
+    using S = Sched<KS1, false>;
+    __shared__ __attribute__((aligned(16))) unsigned char smem[SMEM_NG];
+    unsigned char* Ah = smem;
+    unsigned char* Al = smem + IMG;
+    unsigned char* Hh = smem + 2 * IMG;
+    unsigned char* Hl = smem + 3 * IMG;
+    float* Bs = reinterpret_cast<float*>(smem + 4 * IMG);
+    int M = p.M;
+    if (p.m_dev) { const int md = *p.m_dev; M = md < M ? md : M; }
+    const int m0 = blockIdx.x * BM;
+    if (m0 >= M) return;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fr = lane & 15, fg = lane >> 4;
+    const long long lo = (long long)lane * 8 + (long long)wave * CT * 512;
+    const WBase w{{nullptr, nullptr}, {nullptr, nullptr}, {p.W1a_h + lo, p.W1a_l + lo}, {p.W1b_h + lo, p.W1b_l + lo}};
+    XFrag wq[RING][CT], a[2][RT];
+    const bool rows16 = p.Xk_hi != nullptr;
+    ring_load<KS1, 0, false>(wq, w);
+    ring_load<KS1, 1, false>(wq, w);
+    if constexpr (RING > 3) ring_load<KS1, 2, false>(wq, w);
+    if constexpr (RING > 4) ring_load<KS1, 3, false>(wq, w);
+    if constexpr (RING > 5) ring_load<KS1, 4, false>(wq, w);
+    {
+        // biases -> LDS: [b1a | b1b] as 320 float4
+        constexpr int NB = (NG_FLOATS / 4 + NTHR - 1) / NTHR;
+#pragma unroll
+        for (int i = 0; i < NB; ++i) {
+            const int t = tid + NTHR * i;
+            if (t < NG_FLOATS / 4) {
+                const float* src = t < 256 ? p.b1a + 4 * t : p.b1b + 4 * (t - 256);
+                *reinterpret_cast<float4*>(Bs + 4 * t) = *reinterpret_cast<const float4*>(src);
+            }
+        }
+        Stage<4 * KS1> st;
+        st.load(p.A1, 32 * KS1, nullptr, m0, M, tid);
+        st.commit(Ah, Al, tid);
+    }
+    __syncthreads();
+    const int n0 = wave * CT * 16 + 4 * fg;             // this lane's 4 output columns of column tile j start at n0 + 16 j
+    f32x4_t accf[RT][CT];                               // P1 = position_encoder(A1), bias added at the end
+
+    // ---- 1. P1 in four parts of 256 hidden columns
+    zero_acc(accf);
+    layer1<KS1, 0, false>(wq, a, w, Ah, Al, Hh, Hl, Bs + NG_1A, wave, fr, fg);
+    steps<KS1, S::first_of(0) + KS1, 8, 0, false>(accf, wq, a, w, Hh, Hl, fr, fg);
+    layer1<KS1, 1, false>(wq, a, w, Ah, Al, Hh, Hl, Bs + NG_1A + 256, wave, fr, fg);
+    steps<KS1, S::first_of(1) + KS1, 8, 0, false>(accf, wq, a, w, Hh, Hl, fr, fg);
+    layer1<KS1, 2, false>(wq, a, w, Ah, Al, Hh, Hl, Bs + NG_1A + 512, wave, fr, fg);
+    steps<KS1, S::first_of(2) + KS1, 8, 0, false>(accf, wq, a, w, Hh, Hl, fr, fg);
+    layer1<KS1, 3, false>(wq, a, w, Ah, Al, Hh, Hl, Bs + NG_1A + 768, wave, fr, fg);
+    // read-back mapping of the output phase: lane -> (row r0 + 8 k, columns c4..c4+3 of 32); the row indices, the table rows and (row outputs) the
+    // feature rows of the first 32 output columns travel under the last layer 2
+    constexpr int NK = BM / 8;
+    const int c4 = (lane & 7) * 4, r0 = lane >> 3;
+    int ri[NK];
+#pragma unroll
+    for (int k = 0; k < NK; ++k) {
+        const int m = min(m0 + 8 * k + r0, M - 1);
+        ri[k] = p.row_index ? p.row_index[m] : m;
+    }
+    float4 tvq[NK];
+    typename MapElem<MT>::raw4 fvq[NK];                // as loaded, widened where it is used
+    auto request = [&](int jp) {
+        const long long gcol = wave * CT * 16 + jp * 32 + c4;
+#pragma unroll
+        for (int k = 0; k < NK; ++k) {
+            tvq[k] = *reinterpret_cast<const float4*>(p.sine_tab + (long long)(ri[k] % p.tab_period) * C + gcol);
+            if (rows16) fvq[k] = MapElem<MT>::ld4(p.Xmap + (long long)ri[k] * C + gcol);
+        }
+    };
+    request(0);
+    steps<KS1, S::first_of(3) + KS1, 8, 0, false>(accf, wq, a, w, Hh, Hl, fr, fg);
+    // ---- 2. pe = tab + (P1 + b); T path: Xk = pe + feat, Xv = feat as key16 hi + lo pairs.  Through a wave-private LDS tile
+    // [BM rows][32 columns], then whole 128-byte row pieces (the output phase of the gated kernel).
+#pragma unroll
+    for (int j = 0; j < CT; ++j) {
+        const float4 fb = *reinterpret_cast<const float4*>(Bs + NG_1B + n0 + 16 * j);
+#pragma unroll
+        for (int i = 0; i < RT; ++i)
+            accf[i][j] = f32x4_t{accf[i][j][0] + fb.x, accf[i][j][1] + fb.y, accf[i][j][2] + fb.z, accf[i][j][3] + fb.w};
+    }
+    __syncthreads();                                   // all LDS images free: they become the waves' output tiles
+    float* ot = reinterpret_cast<float*>(smem) + wave * (BM * OT_PITCH);
+#pragma unroll
+    for (int jp = 0; jp < CT / 2; ++jp) {               // 32 columns (two column tiles) at a time
+        if (jp > 0) __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int i = 0; i < RT; ++i)
+                *reinterpret_cast<float4*>(ot + (16 * i + fr) * OT_PITCH + 16 * j + 4 * fg) =
+                    make_float4(accf[i][2 * jp + j][0], accf[i][2 * jp + j][1], accf[i][2 * jp + j][2], accf[i][2 * jp + j][3]);
+        __builtin_amdgcn_wave_barrier();               // the tile is read back by the same wave only
+        const long long gcol = wave * CT * 16 + jp * 32 + c4;
+#pragma unroll
+        for (int k = 0; k < NK; ++k) {
+            const int row = 8 * k + r0, m = m0 + row;
+            float4 v = *reinterpret_cast<const float4*>(ot + row * OT_PITCH + c4);
+            const float4 tv = tvq[k];
+            v = make_float4(v.x + tv.x, v.y + tv.y, v.z + tv.z, v.w + tv.w);
+            if (m < M) {
+                if (p.pe) *reinterpret_cast<float4*>(p.pe + (long long)(p.pe_at_index ? ri[k] : m) * C + gcol) = v;
+                if (rows16) {
+                    const float4 f = MapElem<MT>::widen(fvq[k]);
+                    uint2 h, l;
+                    split_k16x2(v.x + f.x, v.y + f.y, h.x, l.x);
+                    split_k16x2(v.z + f.z, v.w + f.w, h.y, l.y);
+                    *reinterpret_cast<uint2*>(p.Xk_hi + (long long)m * C + gcol) = h;
+                    if (p.lo8) *reinterpret_cast<unsigned int*>(reinterpret_cast<unsigned char*>(p.Xk_lo) + (long long)m * C + gcol) = lo8_pack4_flag(l.x, l.y, p.lo8_flag);
+                    else *reinterpret_cast<uint2*>(p.Xk_lo + (long long)m * C + gcol) = l;
+                    split_k16x2(f.x, f.y, h.x, l.x);
+                    split_k16x2(f.z, f.w, h.y, l.y);
+                    *reinterpret_cast<uint2*>(p.Xv_hi + (long long)m * C + gcol) = h;
+                    if (p.lo8) *reinterpret_cast<unsigned int*>(reinterpret_cast<unsigned char*>(p.Xv_lo) + (long long)m * C + gcol) = lo8_pack4_flag(l.x, l.y, p.lo8_flag);
+                    else *reinterpret_cast<uint2*>(p.Xv_lo + (long long)m * C + gcol) = l;
+                }
+            }
+        }
+        if (jp + 1 < CT / 2) request(jp + 1);
+    }
 }
 
 constexpr int PX_BM = BM, PX_NTHR = NTHR;

@@ -49,7 +49,8 @@ class HeadEngine:
                  max_num=300, pc_range=(-51.2, -51.2, -5.0, 51.2, 51.2, 3.0),
                  post_range=(-61.2, -61.2, -10.0, 61.2, 61.2, 10.0), depth_num=64, stride=16, col_cap_per_query=2048,
                  iou_thr=0.0, ratio=0.0, masked_row='nan', exact=None, num_classes=10, roi_size=7, use_reg_layer=False,
-                 group_reg_dims=(2, 2, 1, 1, 2, 2), depth_start=1, position_range=None, query_generator=None, num_reg_fcs=2):
+                 group_reg_dims=(2, 2, 1, 1, 2, 2), depth_start=1, position_range=None, query_generator=None, num_reg_fcs=2,
+                 with_fpe=True, no_sin_enc=False, adapt_pos3d=True, LID=True):
         assert kind in ('S', 'T')
         self.kind = kind
         self.dev = torch.device(device)
@@ -85,6 +86,11 @@ class HeadEngine:
         self.pe_kp = ops.pe_kp(self.depth_num)
         self.depth_start, pe_range = ops.check_pe_range(depth_start, post_range if position_range is None else position_range, 'HeadEngine')
         self.pe_range_h64 = torch.tensor(pe_range, dtype=torch.float64)
+        # the PE's four switches (MU/pe.py:51-82; ops.check_pe_options).  Fixed per engine: the state dict's key layout has to agree (load_state).  The
+        # shipped values allocate, pack and launch what they always did; with_fpe=False runs the gate-less instance of the fused PE kernel
+        # (mv2d_pe_fused_x3_ng: no fpe weights), no_sin_enc=True feeds either instance one all-zero table row (no adapt_pos3d weights, no sine rows),
+        # LID=False only changes the depth table.  Anything but the shipped values runs on the index-exact route only (route.resolve).
+        self.with_fpe, self.no_sin_enc, self.adapt_pos3d, self.LID = ops.check_pe_options(with_fpe, no_sin_enc, adapt_pos3d, LID, 'HeadEngine')
         self.stride = stride
         self.iou_thr, self.ratio = iou_thr, ratio
         self.col_cap_per_query = col_cap_per_query
@@ -119,6 +125,7 @@ class HeadEngine:
         d, L, nf = self.dev, self.L, self.num_reg_fcs
         self.check_reg_layout(sd, self.use_reg_layer, self.group_reg_dims)
         self.check_branch_depth(sd, nf, self.use_reg_layer)
+        self.check_pe_layout(sd, self.with_fpe, self.no_sin_enc)
         nc = int(tuple(sd[f'bbox_head.cls_branches.0.{3 * nf}.weight'].shape)[0])
         if nc != self.num_classes:
             raise ValueError(f'HeadEngine: the state dict has {nc} classes (cls_branches.*.{3 * nf}.weight), num_classes={self.num_classes}')
@@ -216,27 +223,32 @@ class HeadEngine:
         c1 = lambda k: ops.pad_pe_w1a(g(pe + k)) if k == 'position_encoder.0.weight' else g(pe + k).flatten(1).contiguous()
         pe_names = (('w1a', 'position_encoder.0'), ('w1b', 'position_encoder.2'), ('w2a', 'adapt_pos3d.0'), ('w2b', 'adapt_pos3d.2'),
                     ('wr', 'fpe.conv_reduce'), ('we', 'fpe.conv_expand'))
+        # (the submodules the PE's switches leave out have no weights: nothing of theirs is read or packed)
+        pe_names = tuple((n_, k_) for n_, k_ in pe_names if (self.with_fpe or n_[1] not in 're') and (not self.no_sin_enc or n_[1] != '2'))
         for n_, k_ in pe_names:
             w['pe_b' + n_[1:]] = g(pe + k_ + '.bias')
         self._pe_w32 = {n_: c1(k_ + '.weight') for n_, k_ in pe_names}               # fp32 originals (3 MB): _c3 builds split copies on demand
         # fragment-major key16 copies for the fused PE kernel (one allocation, in the order the kernel streams them)
         names = ('wr', 'we', 'w1a', 'w1b')
-        packs = [k16(c1(dict(pe_names)[n] + '.weight')).view(-1) for n in names]
-        flat, off = torch.cat(packs), 0
-        w['pe_pack'] = dict(b1a=w['pe_b1a'], b1b=w['pe_b1b'], br=w['pe_br'], be=w['pe_be'], flat=flat)
-        for n, t in zip(names, packs):
-            w['pe_pack'][n] = flat[off:off + t.numel()]
-            off += t.numel()
+        if self.with_fpe:                  # (the key16 mode's kernel has no gate-less form: route.resolve refuses it)
+            packs = [k16(c1(dict(pe_names)[n] + '.weight')).view(-1) for n in names]
+            flat, off = torch.cat(packs), 0
+            w['pe_pack'] = dict(b1a=w['pe_b1a'], b1b=w['pe_b1b'], br=w['pe_br'], be=w['pe_be'], flat=flat)
+            for n, t in zip(names, packs):
+                w['pe_pack'][n] = flat[off:off + t.numel()]
+                off += t.numel()
         # the sine branch's table is built in fp32-class arithmetic (split-precision linears on the unrounded sine rows; once per (weights, geometry))
-        for n_, k_ in pe_names[2:4]:
-            w['pe_' + n_ + '_x3'] = ops.pack_x3(c1(k_ + '.weight'))
+        for n_, k_ in pe_names:
+            if n_ in ('w2a', 'w2b'):
+                w['pe_' + n_ + '_x3'] = ops.pack_x3(c1(k_ + '.weight'))
         if self.exact:
             # bf16 hi / lo fragment-major pairs for the split-precision PE kernel (csrc/pe_x3.hip)
-            w['pe_x3'] = dict(b1a=w['pe_b1a'], b1b=w['pe_b1b'], br=w['pe_br'], be=w['pe_be'],
+            w['pe_x3'] = dict(b1a=w['pe_b1a'], b1b=w['pe_b1b'], **({'br': w['pe_br'], 'be': w['pe_be']} if self.with_fpe else {}),
                               **{n_: ops.pack_x3(c1(k_ + '.weight')) for n_, k_ in pe_names if n_ in ('w1a', 'w1b', 'wr', 'we')})
             # first-layer weights with their rows in the order csrc/pe_x3b.hip chains the two layers in registers with
-            w['pe_x3']['w1a_p'] = ops.pack_x3_rowperm(c1('position_encoder.0.weight'))
-            w['pe_x3']['wr_p'] = ops.pack_x3_rowperm(c1('fpe.conv_reduce.weight'))
+            if self.with_fpe:
+                w['pe_x3']['w1a_p'] = ops.pack_x3_rowperm(c1('position_encoder.0.weight'))
+                w['pe_x3']['wr_p'] = ops.pack_x3_rowperm(c1('fpe.conv_reduce.weight'))
             if self.qg.is_default:
                 w['qg_conv_wx3'] = ops.pack_key16_x3(conv)
         self.w = w
@@ -366,6 +378,18 @@ class HeadEngine:
             raise ValueError(f'HeadEngine: num_reg_fcs={n} expects {n} hidden layer(s) per prediction branch (class blocks at cls_branches.{{l}}.{{3i, 3i+1}} '
                              f'with the output layer at {3 * n}; {kind} blocks at {"reg_branch.{3i}" if use_reg_layer else "{2i} with the output layer at " + str(2 * n)}); '
                              f'the state dict\'s class branches have {nc} and its regression branches {nr} -- build the engine with the num_reg_fcs of the checkpoint')
+
+    @staticmethod
+    def check_pe_layout(sd, with_fpe=True, no_sin_enc=False):
+        """ValueError naming the switch (``with_fpe`` / ``no_sin_enc``) when the state dict's ``position_encoding.fpe.*`` / ``adapt_pos3d.*`` keys
+        disagree with it, in either direction.  Needs neither the library nor a GPU."""
+        pe = 'position_encoding.'
+        for sub, want, switch, value in (('fpe.', with_fpe, 'with_fpe', with_fpe), ('adapt_pos3d.', not no_sin_enc, 'no_sin_enc', no_sin_enc)):
+            have = sorted(k for k in sd if k.startswith(pe + sub))
+            if have and not want:
+                raise ValueError(f'HeadEngine: the state dict holds {pe}{sub}* ({have[0]}, ...) but {switch}={value} builds no such submodule')
+            if want and not have:
+                raise ValueError(f'HeadEngine: the state dict has no {pe}{sub}* keys but {switch}={value} needs them')
 
     def _c3(self, name):
         """K-concatenated split-precision copy [w_hi | w_hi | w_lo] of a PE weight ('w1a', 'w1b', 'w2a', 'w2b', 'wr', 'we'), built on first use
@@ -508,13 +532,13 @@ class HeadEngine:
                                  umask=alloc(ucap, torch.uint8, zero=True), ucap=ucap, ctl=ws['grp_ctl'])
         # key16 rows of the PE block's inputs: frustum [.,192], sine [.,384] (training route only: the inference kernel reads the folded
         # table), feature rows [.,256] (the SE gate's input; the value rows of the T path)
-        ws['A1'] = e((P, self.pe_kp), K16); ws['A2'] = e((P, 384), K16)
+        ws['A1'] = e((P, self.pe_kp), K16); ws['A2'] = None if self.no_sin_enc else e((P, 384), K16)      # (no sine branch: no sine rows)
         ws['Xf_b'] = e((P, C), K16)
         if st.exact:
             # index-exact route: the unrounded fp32 frustum rows of the PE block (the feature rows are read from the map), the lo halves of the
             # key / value rows and RoI cells -- all pre-allocated (no per-frame allocation, no host synchronisation: the route is
             # graph-replayable like the default one)
-            ws['xa1'] = e((P, self.pe_kp)); ws['xa2'] = e((P, 384))
+            ws['xa1'] = e((P, self.pe_kp)); ws['xa2'] = None if self.no_sin_enc else e((P, 384))
             lo8, LO = st.lo8, torch.uint8 if st.lo8 else K16
             if st.kind == 'T':
                 ws['xk_lo'] = z((P, C), LO); ws['xv_lo'] = z((P, C), LO)
@@ -552,7 +576,7 @@ class HeadEngine:
         sht = self._shape_cache.get(skey)
         if sht is None:
             sht = calib.shape_tables(skey[0], h, w, stride=self.stride, depth_num=self.depth_num, depth_start=self.depth_start,
-                                     position_range=tuple(self.pe_range_h64.tolist()))
+                                     position_range=tuple(self.pe_range_h64.tolist()), lid=self.LID)
             if len(self._shape_cache) >= 16:
                 self._shape_cache.pop(next(iter(self._shape_cache)))
             self._shape_cache[skey] = sht
@@ -632,7 +656,12 @@ class HeadEngine:
         # that (or the weights) change -- in fp32-class arithmetic on both routes (fp32 sine rows, K-concatenated split-precision GEMMs:
         # a once-per-rig cost), so that the table adds no 16-bit rounding of its own to pe
         skey = (self._weights_version,) + tuple(k[0] for k in shape_key)
-        if sh.get('sine_key') != skey:
+        if self.no_sin_enc:
+            # no sine branch (MU/pe.py:163-166 skipped): the PE kernel's table is ONE all-zero row of period 1, built once -- no sine rows, no weights
+            if sh.get('sine_tab') is None:
+                sh['sine_tab'] = torch.zeros((1, C), device=self.dev, dtype=F32)
+                sh['sine_gen'], sh['sine_period'] = sh.get('sine_gen', 0) + 1, 1
+        elif sh.get('sine_key') != skey:
             same = all(k == skey[1] for k in skey[1:])
             P = V * h * w
             Pt = P // B if same else P                                  # one sample's positions when all samples share the geometry
@@ -850,7 +879,8 @@ class HeadEngine:
         (o.pe_fused_x3b if rt.pe_rows_in_waves else o.pe_fused_x3)(
             ws['xa1'], featcl, md, W_['pe_x3'], sh['sine_tab'], sh['sine_period'], pe=(ws['pe_pos'] if at_pos else ws['pe']) if (not rows or rt.stages) else None,
             Xk=(ws['Xk'], ws['xk_lo']) if rows else None, Xv=(ws['Xf_b'], ws['xv_lo']) if rows else None, M=P, row_index=ws['s2pos'], pe_at_index=at_pos, lo8_flag=ws['lo8_flag'] if (rows and rt.lo8) else None,
-            **({} if self.depth_num == 64 else dict(Kp=self.pe_kp)))            # (64 bins: the entries without a size argument, as before)
+            **({} if self.depth_num == 64 and self.with_fpe else dict(Kp=self.pe_kp)),            # (64 bins: the entries without a size argument, as before)
+            **({} if self.with_fpe else dict(gate=False)))                                          # (with_fpe=False: the gate-less kernel, mv2d_pe_fused_x3_ng)
 
     def _pe_ld(self):
         """Row pitch argument of the frustum-row producers: None (the entries without a pitch, rows of 3 * depth_num columns) unless the rows are padded."""
@@ -863,10 +893,10 @@ class HeadEngine:
         n = int(positions.numel())
         T, d = ws['tab'], self.dev
         a1 = torch.empty((n, self.pe_kp), device=d, dtype=self.K16)
-        a2 = torch.empty((n, 384), device=d, dtype=self.K16)
+        a2 = None if self.no_sin_enc else torch.empty((n, 384), device=d, dtype=self.K16)       # (no sine branch: no sine rows, None in their place)
         xb = torch.empty((n, C), device=d, dtype=self.K16)
         a1f = torch.empty((n, self.pe_kp), device=d, dtype=F32) if f32 else None
-        a2f = torch.empty((n, 384), device=d, dtype=F32) if f32 else None
+        a2f = torch.empty((n, 384), device=d, dtype=F32) if (f32 and not self.no_sin_enc) else None
         ops.pe_inputs(positions.contiguous(), torch.tensor([n], dtype=torch.int32, device=d), n, ws['featcl'], T['img2lidar'], T['coords_w'],
                       T['coords_h'], T['coords_d'], T['embeds'], self.const['dim_t'], a1, a2, xb, None, V, h, w, self.depth_num, self.pe_range_h64,
                       A_frustum_f32=a1f, A_sine_f32=a2f, ld=self._pe_ld())
@@ -1076,7 +1106,8 @@ class HeadEngine:
         ops.map_format(map_dtype)                         # ValueError for anything but fp32 / fp16 / bf16
         if any(f.dtype != map_dtype for f in fl):
             raise ValueError(f'mv2d engine: the feature maps of a batch must share one dtype, got {sorted({str(f.dtype) for f in fl})}')
-        rt = route.resolve(self, self.kind, self.exact, self.depth_num, map_dtype, keep_stages, use_graph)     # (ValueError for impossible combinations)
+        rt = route.resolve(self, self.kind, self.exact, self.depth_num, map_dtype, keep_stages, use_graph,     # (ValueError for impossible combinations)
+                           pe_options=dict(with_fpe=self.with_fpe, no_sin_enc=self.no_sin_enc, LID=self.LID))
         if not self.qg.is_default and not rt.conv_x3:
             raise ValueError('mv2d engine: a query generator of other than the shipped shape runs on the index-exact route only (exact=True, the default, '
                              "without 'conv' in exact_skip): the engine has no key16-mode plan for " + repr(tuple(self.qg)))
@@ -1181,9 +1212,8 @@ class HeadEngine:
                 def mlp1(x32, n1, n2, **kw):
                     h3 = o.gemm_bf16(o.split3_rows(x32), self._c3(n1), W_['pe_b' + n1[1:]], act=1, split3=True)
                     return o.gemm_bf16(h3, self._c3(n2), W_['pe_b' + n2[1:]], out_dtype=F32, **kw)
-                gate = mlp1(f0, 'wr', 'we', act=2)
-                pg = mlp1(a1f, 'w1a', 'w1b', mul=gate)
-                pe0 = mlp1(a2f, 'w2a', 'w2b', add=pg)
+                pg = mlp1(a1f, 'w1a', 'w1b', **(dict(mul=mlp1(f0, 'wr', 'we', act=2)) if self.with_fpe else {}))        # (the PE's switches: no gate / no sine term)
+                pe0 = pg if self.no_sin_enc else mlp1(a2f, 'w2a', 'w2b', add=pg)
                 ws['Xk'][s0:s0 + 1].copy_(o.f32_to_key16(pe0 + f0)); ws['Xf_b'][s0:s0 + 1].copy_(o.f32_to_key16(f0))
             row_ptr, col_fb, _ = fallback_key_csr(row_ptr.clone(), ws['col_idx'][:int(row_ptr[R].item())].clone(), s0)
         no_dn = dn_ref is None or dn_ref.shape[0] == 0

@@ -613,6 +613,23 @@ def check_pe_range(depth_start, position_range, who):
     return ds, pr
 
 
+PE_OPTION_DEFAULTS = dict(with_fpe=True, no_sin_enc=False, adapt_pos3d=True, LID=True)      # the shipped configs' values of the PE's four switches
+
+
+def check_pe_options(with_fpe=True, no_sin_enc=False, adapt_pos3d=True, LID=True, who='PE'):
+    """The reference PE's four switches (MU/pe.py:51-82) as the one accepted set, or ValueError naming the key: each a bool; with_fpe=False = no fpe
+    submodule, no gate; no_sin_enc=True = no adapt_pos3d, no positional_encoding, no sine term (adapt_pos3d is then ignored, as in the reference);
+    adapt_pos3d=False with no_sin_enc=False is refused (the reference builds it, its forward raises AttributeError at MU/pe.py:165); LID=False =
+    uniform depth bins.  Returns (with_fpe, no_sin_enc, adapt_pos3d, LID)."""
+    for key, v in (('with_fpe', with_fpe), ('no_sin_enc', no_sin_enc), ('adapt_pos3d', adapt_pos3d), ('LID', LID)):
+        if not isinstance(v, bool):
+            raise ValueError(f'{who}: {key} must be True or False, got {v!r}')
+    if not adapt_pos3d and not no_sin_enc:
+        raise ValueError(f'{who}: adapt_pos3d=False needs no_sin_enc=True (with the sine branch on, the reference PE\'s forward calls the adapt_pos3d '
+                         f'it did not build)')
+    return with_fpe, no_sin_enc, adapt_pos3d, LID
+
+
 def pad_pe_w1a(W, depth_num=None):
     """position_encoder.0.weight [1024, 3 D] (or [1024, 3 D, 1, 1]) -> [1024, Kp] with zero pad columns (what pack_x3 / pack_key16 / the training
     route's K-concatenated copies are built from); the tensor itself when 3 D is a multiple of 32.  With depth_num, W may also arrive with Kp
@@ -632,23 +649,33 @@ def pad_pe_w1a(W, depth_num=None):
 
 
 def pe_fused_x3(A1, Xmap, m_dev, wx, sine_tab, tab_period, pe=None, Xk=None, Xv=None, M=None, row_index=None, pe_at_index=False, lo8_flag=None,
-                map_fmt=None, Kp=None):
-    """The PE block in split precision on unrounded inputs (index-exact route, csrc/pe_x3.hip).  A1 [M,Kp] fp32 (Kp = pe_kp(depth_num): frustum rows with zero
+                map_fmt=None, Kp=None, gate=True):
+    """The PE block in split precision on unrounded inputs (index-exact route, csrc/pe_x3.hip).  gate=False: the PE without the feature-guided gate
+    (with_fpe=False; mv2d_pe_fused_x3_ng, any Kp): wx needs no 'wr','we','br','be', and Xmap may be None when neither Xk nor Xv is asked for.  A1 [M,Kp] fp32 (Kp = pe_kp(depth_num): frustum rows with zero
     pad columns, wx['w1a'] packed from pad_pe_w1a(weight); Kp=None: the 192 columns of 64 bins through the entries that have no size argument); Xmap feature rows, fp32, fp16 or
     bf16 (widened in the kernel; indexed by row_index when given); wx: dict 'w1a','w1b','wr','we' = pack_x3(weight) pairs + fp32 biases 'b1a','b1b','br','be'; pe [M,256]
     fp32 and / or Xk = (hi, lo), Xv = (hi, lo) key16 [M,256] pairs (key rows pe + feat, value rows feat).  pe_at_index: pe row m goes to row
     row_index[m] of `pe` (a position-indexed map for roi_align without map1_index)."""
     _req(A1, torch.float32, 'A1'); _req(sine_tab, torch.float32, 'sine_tab'); _req(pe, torch.float32, 'pe')
-    fmt = _req_map(Xmap, 'Xmap', map_fmt)
+    fmt = 0 if (Xmap is None and not gate) else _req_map(Xmap, 'Xmap', map_fmt)
     _req(row_index, torch.int32, 'row_index'); _req(m_dev, torch.int32, 'm_dev')
     for pair in (Xk, Xv):
         if pair is not None:
             _req16(pair[0], 'hi')
     lo_fmt = _lo_fmt(Xk[1] if Xk else None, Xv[1] if Xv else None)
-    for k in ('w1a', 'w1b', 'wr', 'we'):
+    for k in ('w1a', 'w1b', 'wr', 'we') if gate else ('w1a', 'w1b'):
         _req(wx[k][0], q16_dtype(), k); _req(wx[k][1], q16_dtype(), k)
     M = A1.shape[0] if M is None else M
     xk, xv = Xk or (None, None), Xv or (None, None)
+    if not gate:
+        Kp = 192 if Kp is None else Kp
+        if A1.dim() != 2 or A1.shape[1] != Kp or wx['w1a'][0].numel() != 1024 * Kp:
+            raise _lib.Mv2dHipError(f'pe_fused_x3: A1 {tuple(A1.shape)} / w1a ({wx["w1a"][0].numel()} elements) do not have Kp = {Kp} columns')
+        check(_lib.load().mv2d_pe_fused_x3_ng(_p(A1), _p(Xmap), _p(row_index), _p(m_dev), M, _p(wx['w1a'][0]), _p(wx['w1a'][1]), _p(wx['b1a']),
+                                              _p(wx['w1b'][0]), _p(wx['w1b'][1]), _p(wx['b1b']), _p(sine_tab), int(tab_period), _p(pe), _p(xk[0]), _p(xk[1]),
+                                              _p(xv[0]), _p(xv[1]), lo_fmt, 1 if (pe_at_index and row_index is not None) else 0, _p(lo8_flag), fmt, int(Kp),
+                                              _stream()), 'mv2d_pe_fused_x3_ng')
+        return pe
     if Kp is not None:
         if A1.dim() != 2 or A1.shape[1] != Kp or wx['w1a'][0].numel() != 1024 * Kp:
             raise _lib.Mv2dHipError(f'pe_fused_x3: A1 {tuple(A1.shape)} / w1a ({wx["w1a"][0].numel()} elements) do not have Kp = {Kp} columns')

@@ -278,7 +278,9 @@ class MV2DHead(nn.Module):
                                       expand_stride=bc.expand_stride, num_layers=self.bbox_head.num_pred, max_num=coder.max_num,
                                       pc_range=tuple(self.pc_range), post_range=tuple(coder.post_center_range),
                                       depth_num=self.position_encoding.depth_num, depth_start=self.position_encoding.depth_start,
-                                      position_range=tuple(self.position_encoding.position_range), stride=self.strides[self.feat_lvl],
+                                      position_range=tuple(self.position_encoding.position_range),
+                                      with_fpe=self.position_encoding.with_fpe, no_sin_enc=self.position_encoding.no_sin_enc,
+                                      adapt_pos3d=self.position_encoding.adapt_pos3d_key, LID=self.position_encoding.LID, stride=self.strides[self.feat_lvl],
                                       iou_thr=bc.iou_thr, ratio=bc.ratio, num_classes=self.bbox_head.num_classes, roi_size=self.roi_cells,
                                       use_reg_layer=getattr(self.bbox_head, 'use_reg_layer', False),
                                       group_reg_dims=getattr(self.bbox_head, 'group_reg_dims', (2, 2, 1, 1, 2, 2)),
@@ -344,13 +346,14 @@ class MV2DHead(nn.Module):
         empty = (row_ptr[1:] == row_ptr[:-1]).any().to(torch.int32) if self.KIND == 'T' else row_ptr.new_zeros(())
         nnz, S, any_empty, s0 = (int(v) for v in torch.stack([row_ptr[R], ws['S_dev'].reshape(()).to(torch.int32), empty, ws['pos2s'][0].to(torch.int32)]).tolist())
         col = ws['col_idx'][:nnz].clone()
-        A1, A2, s2pos = ws['A1'][:S].clone(), ws['A2'][:S].clone(), ws['s2pos'][:S].long()
+        no_sin = ws['A2'] is None                              # (PE without the sine branch: no sine rows anywhere)
+        A1, A2, s2pos = ws['A1'][:S].clone(), None if no_sin else ws['A2'][:S].clone(), ws['s2pos'][:S].long()
         if self.KIND == 'T' and any_empty:
             # a RoI without a single visible key: in training the reference un-masks the key at map position (view 0, 0, 0) for it
             # (RH/mv2d_t_head.py:80-82) instead of producing a NaN row; that position joins the key list if no RoI lists it
             if s0 < 0:
                 a1, a2 = eng.pe_input_rows(ws, torch.zeros(1, dtype=torch.int32, device=fm.device), V, h, w)
-                A1, A2, s2pos, s0 = torch.cat([A1, a1]), torch.cat([A2, a2]), torch.cat([s2pos, s2pos.new_zeros(1)]), S
+                A1, A2, s2pos, s0 = torch.cat([A1, a1]), None if no_sin else torch.cat([A2, a2]), torch.cat([s2pos, s2pos.new_zeros(1)]), S
             row_ptr, col, _ = train.fallback_key_csr(row_ptr, col, s0)
         # the PE block at the positions the engine listed (T: the gathered keys; S: every position a RoIAlign tap can touch)
         key_rows, val_rows, pe_rows = train.key_embedding_autograd(self, A1, A2, fm[s2pos])

@@ -161,16 +161,22 @@ class PE(nn.Module):
     def __init__(self, positional_encoding, strides, position_range, depth_num, depth_start=1, LID=True, embed_dims=256,
                  with_fpe=False, adapt_pos3d=True, no_sin_enc=False):
         super().__init__()
-        assert LID and with_fpe and adapt_pos3d and not no_sin_enc and embed_dims == C, 'kernel path implements the shipped config'
+        assert embed_dims == C, 'kernel path implements the shipped config'
+        # the four switches (ops.check_pe_options: the one list of accepted values).  The submodules are exactly the reference's (MU/pe.py:70-82): no fpe
+        # under with_fpe=False, no adapt_pos3d and no positional_encoding under no_sin_enc=True -- a reference checkpoint loads with strict=True
+        with_fpe, no_sin_enc, adapt_pos3d, LID = ops.check_pe_options(with_fpe, no_sin_enc, adapt_pos3d, LID, 'PE')
         # the three keys the fused engine takes at any supported value (depth_num: one instance of the fused PE kernel per 32 frustum columns)
         depth_num = ops.check_pe_depth(depth_num, 'PE')
         ops.check_pe_range(depth_start, position_range, 'PE')
         self.strides, self.position_range, self.depth_num, self.depth_start = strides, position_range, depth_num, depth_start
-        self.embed_dims, self.with_fpe = embed_dims, with_fpe
+        self.embed_dims, self.with_fpe, self.no_sin_enc, self.LID = embed_dims, with_fpe, no_sin_enc, LID
+        self.adapt_pos3d_key = adapt_pos3d                  # (the config key; ``adapt_pos3d`` itself is the submodule, as in the reference)
         self.position_encoder = nn.Sequential(nn.Conv2d(3 * depth_num, 4 * C, 1), nn.ReLU(), nn.Conv2d(4 * C, C, 1))
-        self.adapt_pos3d = nn.Sequential(nn.Conv2d(C * 3 // 2, 4 * C, 1), nn.ReLU(), nn.Conv2d(4 * C, C, 1))
-        self.positional_encoding = build_positional_encoding(positional_encoding)
-        self.fpe = SELayer(C)
+        if not no_sin_enc:
+            self.adapt_pos3d = nn.Sequential(nn.Conv2d(C * 3 // 2, 4 * C, 1), nn.ReLU(), nn.Conv2d(4 * C, C, 1))
+            self.positional_encoding = build_positional_encoding(positional_encoding)
+        if with_fpe:
+            self.fpe = SELayer(C)
         self._b = _Bf16Cache()
 
     def forward(self, mlvl_feats, img_metas):
@@ -180,7 +186,7 @@ class PE(nn.Module):
         P = V * h * w
         dev = x.device
         ft = calib.frame_tables(img_metas, h, w, stride=self.strides[0], depth_num=self.depth_num, depth_start=self.depth_start,
-                                position_range=tuple(self.position_range))
+                                position_range=tuple(self.position_range), lid=self.LID)
         ct = calib.constant_tables()
         s2pos = torch.arange(P, dtype=torch.int32, device=dev)
         S_dev = torch.tensor([P], dtype=torch.int32, device=dev)
@@ -188,21 +194,30 @@ class PE(nn.Module):
         # module-level call (whole map, not the engine's hot path): the kernel's fp32 rows feed the generic bf16 tile GEMM chain
         k16, f32 = ops.key16_dtype(), torch.float32
         e = lambda n, dt: torch.empty((P, n), device=dev, dtype=dt)
-        A1f, A2f, Xf = e(3 * self.depth_num, f32), e(384, f32), e(C, f32)
+        sin = not self.no_sin_enc                            # (no sine branch: no sine rows are produced)
+        A1f, A2f, Xf = e(3 * self.depth_num, f32), e(384, f32) if sin else None, e(C, f32)
         ops.pe_inputs(s2pos, S_dev, P, fcl, ft['img2lidar'].to(dev), ft['coords_w'].to(dev), ft['coords_h'].to(dev),
-                      ft['coords_d'].to(dev), ft['embeds'].to(dev), ct['dim_t'].to(dev), e(3 * self.depth_num, k16), e(384, k16), e(C, k16), Xf, V, h, w,
+                      ft['coords_d'].to(dev), ft['embeds'].to(dev), ct['dim_t'].to(dev), e(3 * self.depth_num, k16), e(384, k16) if sin else None, e(C, k16), Xf, V, h, w,
                       self.depth_num, torch.tensor(self.position_range, dtype=torch.float64), A_frustum_f32=A1f, A_sine_f32=A2f)
-        A1, A2, Xb = ops.f32_to_bf16(A1f), ops.f32_to_bf16(A2f), ops.f32_to_bf16(Xf)
+        A1, A2, Xb = ops.f32_to_bf16(A1f), ops.f32_to_bf16(A2f) if sin else None, ops.f32_to_bf16(Xf)
         g = lambda name, mod: (self._b.get(name, mod.weight.flatten(1)), _f(mod.bias))
         w1a, b1a = g('w1a', self.position_encoder[0]); w1b, b1b = g('w1b', self.position_encoder[2])
-        w2a, b2a = g('w2a', self.adapt_pos3d[0]); w2b, b2b = g('w2b', self.adapt_pos3d[2])
-        wr, br = g('wr', self.fpe.conv_reduce); we, be = g('we', self.fpe.conv_expand)
+        kpad = -A1.shape[1] % 64
+        if kpad:                        # the tile GEMM takes K in multiples of 64 (192 at 64 bins): other depths get zero columns on both operands
+            pad = lambda t: torch.nn.functional.pad(t, (0, kpad))
+            A1, w1a = pad(A1), self._b.get('w1a_pad', self.position_encoder[0].weight.flatten(1), lambda t: ops.f32_to_bf16(pad(t).contiguous()))
         H1 = ops.gemm_bf16(A1, w1a, b1a, act=1)
-        H2 = ops.gemm_bf16(A2, w2a, b2a, act=1)
-        Hg = ops.gemm_bf16(Xb, wr, br, act=1)
-        gate = ops.gemm_bf16(Hg, we, be, act=2, out_dtype=torch.float32)
-        Pg = ops.gemm_bf16(H1, w1b, b1b, mul=gate, out_dtype=torch.float32)
-        pe = ops.gemm_bf16(H2, w2b, b2b, add=Pg, out_dtype=torch.float32)
+        if self.with_fpe:
+            wr, br = g('wr', self.fpe.conv_reduce); we, be = g('we', self.fpe.conv_expand)
+            Hg = ops.gemm_bf16(Xb, wr, br, act=1)
+            gate = ops.gemm_bf16(Hg, we, be, act=2, out_dtype=torch.float32)
+            pe = ops.gemm_bf16(H1, w1b, b1b, mul=gate, out_dtype=torch.float32)
+        else:
+            pe = ops.gemm_bf16(H1, w1b, b1b, out_dtype=torch.float32)                  # no gate (MU/pe.py:158-159)
+        if not self.no_sin_enc:
+            w2a, b2a = g('w2a', self.adapt_pos3d[0]); w2b, b2b = g('w2b', self.adapt_pos3d[2])
+            H2 = ops.gemm_bf16(A2, w2a, b2a, act=1)
+            pe = ops.gemm_bf16(H2, w2b, b2b, add=pe, out_dtype=torch.float32)
         return [pe.view(V, h, w, C).permute(0, 3, 1, 2)]
 
 

@@ -141,8 +141,9 @@ class Route(NamedTuple):
 Storage = namedtuple('Storage', Route._fields[:6])
 
 
-def resolve(opts, kind, exact, depth_num, map_dtype=torch.float32, keep_stages=False, use_graph=False):
-    """The Route of one call.  ``opts``: any object with the attributes ``OPTIONS`` (a HeadEngine).  ValueError for impossible combinations."""
+def resolve(opts, kind, exact, depth_num, map_dtype=torch.float32, keep_stages=False, use_graph=False, pe_options=None):
+    """The Route of one call.  ``opts``: any object with the attributes ``OPTIONS`` (a HeadEngine).  ``pe_options``: the engine's PE switches as a
+    dict with any of ``with_fpe`` / ``no_sin_enc`` / ``LID`` (None or a missing key: the shipped value).  ValueError for impossible combinations."""
     o, stages = opts, bool(keep_stages)
     skip, debug, group = o.exact_skip, bool(o.debug_attn), bool(o.group_xattn)
     pe_x3 = exact and 'pe' not in skip
@@ -150,6 +151,14 @@ def resolve(opts, kind, exact, depth_num, map_dtype=torch.float32, keep_stages=F
         raise ValueError(f'mv2d engine: the key16 mode\'s PE kernel (csrc/pe_tab96.hip) is built for depth_num = 64 only; run the index-exact route (exact=True, the default) with depth_num = {depth_num}')
     if depth_num != 64 and o.pe_rows_in_waves:
         raise ValueError(f'mv2d engine: pe_rows_in_waves (csrc/pe_x3b.hip) is built for depth_num = 64 only; unset it for depth_num = {depth_num}')
+    # the PE's switches (HeadEngine.with_fpe / no_sin_enc / LID): the key16 mode's PE kernel and the second shape of the split-precision one are
+    # built for the shipped PE only
+    for key, shipped in (('with_fpe', True), ('no_sin_enc', False), ('LID', True)):
+        v = (pe_options or {}).get(key, shipped)
+        if v != shipped and not pe_x3:
+            raise ValueError(f'mv2d engine: the key16 mode\'s PE kernel (csrc/pe_tab96.hip) is built for {key}={shipped} only; run the index-exact route (exact=True, the default) with {key}={v}')
+        if v != shipped and o.pe_rows_in_waves:
+            raise ValueError(f'mv2d engine: pe_rows_in_waves (csrc/pe_x3b.hip) is built for {key}={shipped} only; unset it for {key}={v}')
     if map_dtype != torch.float32 and o.pe_rows_in_waves and pe_x3:
         raise ValueError('mv2d engine: pe_rows_in_waves (csrc/pe_x3b.hip) reads fp32 feature maps only; unset it for a torch.float16 / torch.bfloat16 map')
     lo8 = bool(o.lo8_rows) and exact and not group

@@ -276,6 +276,13 @@ def with_pe_depth_state(sd, seed=0, depth_num=DEPTH_NUM):
     return out
 
 
+def with_pe_options_state(sd, with_fpe=True, no_sin_enc=False):
+    """A copy of a head state dict laid out for a PE built with these switches: without the position_encoding.fpe.* keys under with_fpe=False, without
+    the position_encoding.adapt_pos3d.* keys under no_sin_enc=True (the reference builds neither submodule then).  No draws: make_head_state is untouched."""
+    drop = (() if with_fpe else ('position_encoding.fpe.',)) + (('position_encoding.adapt_pos3d.',) if no_sin_enc else ())
+    return {k: v for k, v in sd.items() if not k.startswith(drop)} if drop else dict(sd)
+
+
 def with_qg_shape_state(sd, seed=0, query_generator=None, roi_size=7):
     """A copy of a make_head_state dict whose ``query_generator.*`` entries are those of the reference module built with the given
     ``query_generator=dict(...)`` keys (mv2d_amd/qg_shape.py) at ``roi_size``: Xavier matrices, small biases, fc_center scaled and centred like

@@ -525,7 +525,8 @@ def query_generator_autograd(roi_head, roi_feat, intr_feat, minv):
 def key_embedding_autograd(roi_head, A1, A2, Xf):
     """The PE block at the gathered key positions (MU/pe.py:36-48,150-166) as torch autograd over the module's parameters, on the inputs the
     engine prepared: A1 [S,Kp] inverse-sigmoid frustum coordinates (3 * depth_num columns zero-padded to a multiple of 32; 192 at 64 bins), A2 [S,384] sine embedding (bf16, no gradient), Xf [S,256] feature rows
-    (differentiable).  Returns (feat + pe, feat, pe) [S,256] fp32: the T path's keys / values; the S path RoI-aligns pe."""
+    (differentiable).  Returns (feat + pe, feat, pe) [S,256] fp32: the T path's keys / values; the S path RoI-aligns pe.  The PE's switches drop their
+    terms: with_fpe=False the gate product, no_sin_enc=True the sine branch (A2 is then None)."""
     from .autograd_ops import linear
     pe = roi_head.position_encoding
     lin = lambda conv, t, act=0: linear(t, conv.weight.flatten(1), conv.bias, act)  # noqa: E731   (1x1 convs on the HIP GEMM)
@@ -535,7 +536,7 @@ def key_embedding_autograd(roi_head, A1, A2, Xf):
     if A1.shape[1] != w1a.shape[1]:
         w1a = torch.nn.functional.pad(w1a, (0, A1.shape[1] - w1a.shape[1]))
     p3d = lin(pe.position_encoder[2], linear(A1.detach().float(), w1a, pe.position_encoder[0].bias, 1))
-    gate = torch.sigmoid(lin(pe.fpe.conv_expand, lin(pe.fpe.conv_reduce, feat, 1)))
-    sine = lin(pe.adapt_pos3d[2], lin(pe.adapt_pos3d[0], A2.detach().float(), 1))
-    pos = p3d * gate + sine
+    pos = p3d * torch.sigmoid(lin(pe.fpe.conv_expand, lin(pe.fpe.conv_reduce, feat, 1))) if pe.with_fpe else p3d
+    if not pe.no_sin_enc:
+        pos = pos + lin(pe.adapt_pos3d[2], lin(pe.adapt_pos3d[0], A2.detach().float(), 1))
     return feat + pos, feat, pos
