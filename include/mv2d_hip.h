@@ -157,6 +157,16 @@ int mv2d_pe_fused_x3_ng(const float* A1, const void* Xmap, const int* row_index,
                         const void* W1a_hi, const void* W1a_lo, const float* b1a, const void* W1b_hi, const void* W1b_lo, const float* b1b,
                         const float* sine_tab, int tab_period, float* pe, void* Xk_hi, void* Xk_lo, void* Xv_hi, void* Xv_lo,
                         int lo_fmt, int pe_at_index, int* lo8_flag, int map_fmt, int Kp, void* stream);
+/* The GATE of mv2d_pe_fused_x3_k alone on a cached frustum MLP (csrc/pe_x3_gate.hip): pe[m] = sine_tab[pos] + Q[pos] * gate(feature row), pos =
+ * row_index[m] % tab_period.  Q [tab_period,256] fp32 = position_encoder(A1) + b1b for every position of ONE sample, as mv2d_pe_fused_x3_ng writes
+ * it on a one-row zero table (tab_period 1): on a rig whose camera matrices repeat it is constant from frame to frame, and the 16 gate k-steps are
+ * all that is left of the 4 * (Kp / 32 + 8) + 16 of the gated kernel.  pe is bit for bit that of mv2d_pe_fused_x3_k on the frustum rows Q was built
+ * from (the product and the table sum stay two roundings; a Q value of -0.0f was stored as +0.0f, which shows only where the table value is -0.0f
+ * too).  One instance per map format, none per depth.  pe only: the four key / value row pointers must be NULL (argument error otherwise). */
+int mv2d_pe_gate_x3(const float* Q, const void* Xmap, const int* row_index, const int* m_dev, int M,
+                    const void* Wr_hi, const void* Wr_lo, const float* br, const void* We_hi, const void* We_lo, const float* be,
+                    const float* sine_tab, int tab_period, float* pe, void* Xk_hi, void* Xk_lo, void* Xv_hi, void* Xv_lo, int pe_at_index,
+                    int map_fmt, void* stream);
 /* The same block on the second shape of the kernel (round 6, csrc/pe_x3b.hip): a wave owns 16 rows through both layers of each MLP, the hidden layer
  * stays in registers (no LDS image, no barrier between the layers), the weights go through a 4-deep LDS ring (LDS-DMA) shared by the 8 waves of a 128-row
  * block, two waves per SIMD.  Same operands EXCEPT that W1a and Wr (the first layers) are packed from the weight with its rows in the order

@@ -44,6 +44,7 @@ SIGNATURES = {
     'mv2d_pe_fused_x3_fmt': (I, [P, P, P, P, I] + [P] * 13 + [I] + [P] * 5 + [I, I, P, I, P]),
     'mv2d_pe_fused_x3_k': (I, [P, P, P, P, I] + [P] * 13 + [I] + [P] * 5 + [I, I, P, I, I, P]),
     'mv2d_pe_fused_x3_ng': (I, [P, P, P, P, I] + [P] * 7 + [I] + [P] * 5 + [I, I, P, I, I, P]),
+    'mv2d_pe_gate_x3': (I, [P, P, P, P, I] + [P] * 7 + [I] + [P] * 5 + [I, I, P]),
     'mv2d_pe_fused_x3b': (I, [P, P, P, P, I] + [P] * 13 + [I] + [P] * 5 + [I, I, P, P]),
     'mv2d_key16_format': (I, []),
     'mv2d_f32_to_key16': (I, [P, P, P, LL, P]),

@@ -21,7 +21,7 @@ import os
 import numpy as np
 import torch
 
-from . import calib, ops, qg_shape, route
+from . import calib, ops, pe_cache, qg_shape, route
 
 BF16 = torch.bfloat16
 F32 = torch.float32
@@ -116,6 +116,7 @@ class HeadEngine:
         # adapt_pos3d(sine) (MU/pe.py:164-166) depends only on the weights and on the padding geometry of the rig, not on features, boxes
         # or calibration: it is constant-folded into a per-(weights version, geometry) table that the fused PE kernel adds in its epilogue
         self._weights_version = 0     # bumped by every load_state(): invalidates whatever was folded from the weights
+        self.pe_cache_builds = 0      # tables of the cached frustum MLP this engine built (route option pe_cache, _build_pe_q)
         self.exact = (os.environ.get('MV2D_EXACT', '1') != '0') if exact is None else bool(exact)
         self.K16 = ops.key16_dtype()  # dtype of the key side's 16-bit buffers (csrc/common.h "key16": fp16 since round 4)
         self.load_state(state_dict)
@@ -649,6 +650,7 @@ class HeadEngine:
             put('img2lidar', img2lidar); put('trans', trans)
             ws['blob_d'][:split].copy_(bh[:split], non_blocking=True)
             sh['mats'] = mats
+            sh['mats_gen'], sh['mats_one_rig'] = sh.get('mats_gen', 0) + 1, None       # (pe_cache below: the matrices moved)
         nv = self.num_views
         dts = [float(ts[b, nv:].mean() - ts[b, :nv].mean()) if (self.kind == 'T' and Vg > nv) else 0.0 for b in range(B)]
         sh['frame_scalars'] = dict(pad_h=f0['pad_h'], pad_w=f0['pad_w'], dt=dts[0])
@@ -688,6 +690,24 @@ class HeadEngine:
         if ws.get('sine_gen') != sh['sine_gen']:
             ws['sine_gen'] = sh['sine_gen']
             ws['graph_stale'] = True                                     # this workspace's graphs were captured with another table
+        # the frustum MLP of the PE depends on the weights, the padding geometry and the camera matrices: on a rig whose matrices repeat it is kept
+        # as a table Q per position of one sample and a frame runs only the gate (route option pe_cache, mv2d_amd/pe_cache.py, csrc/pe_x3_gate.hip)
+        ws['pe_hit'], ws['pe_cache_state'] = False, 'off'
+        if rt.pe_cache:
+            pol = sh.get('pe_q_policy')
+            if pol is None:
+                pol = sh['pe_q_policy'] = pe_cache.PeCachePolicy()
+            Pt = (V * h * w) // B
+            usable = sh['sine_period'] == Pt                             # (Q and the sine table share the kernel's one period)
+            if usable and pol.prev is not None and pol.prev[2] == sh['mats_gen'] and sh['mats_one_rig'] is None:
+                sh['mats_one_rig'] = pe_cache.one_rig(mats, B)           # the matrices repeat: do the samples share them?  (asked once per set of matrices)
+            state = pol.observe(pe_cache.rig_key(self._weights_version, shape_key, sh['mats_gen'], sh['mats_one_rig'] is not False) if usable else None)
+            if state == 'build':
+                self._build_pe_q(ws, sh, Pt, V, h, w)
+            ws['pe_hit'], ws['pe_cache_state'] = state != 'miss', state
+            if ws.get('pe_q_gen') != sh.get('pe_q_gen'):
+                ws['pe_q_gen'] = sh.get('pe_q_gen')
+                ws['graph_stale'] = True                                 # (a re-allocated table: captured graphs hold the old pointer)
         ws['view_start_h'].numpy()[:] = np.concatenate([[0], np.cumsum(counts)])
         ws['grp_start_h'].numpy()[:] = grp
         if self.kind == 'T':
@@ -864,6 +884,12 @@ class HeadEngine:
         1.09 ms (S) / 2.17 ms (T) per 16-sample launch.  No host synchronisation, no allocation: graph-replayable."""
         o, W_, T, rt = ops, self.w, ws['tab'], ws['route']
         md = ws['S_dev']
+        if ws.get('pe_hit'):
+            # the rig's matrices repeat (route option pe_cache): no frustum rows, no frustum MLP -- the gate alone on the table Q, same pe bits
+            sh = ws['shared']
+            o.pe_gate_x3(sh['pe_q'], featcl, md, W_['pe_x3'], sh['sine_tab'], sh['sine_period'], ws['pe_pos'] if rt.pe_at_pos else ws['pe'], P,
+                         row_index=ws['s2pos'], pe_at_index=rt.pe_at_pos)
+            return
         if rt.keep_sine_rows:
             # (training route: it also reads the key16 rows and the sine rows)
             o.pe_inputs(ws['s2pos'], md, P, featcl, T['img2lidar'], T['coords_w'], T['coords_h'], T['coords_d'], T['embeds'],
@@ -881,6 +907,25 @@ class HeadEngine:
             Xk=(ws['Xk'], ws['xk_lo']) if rows else None, Xv=(ws['Xf_b'], ws['xv_lo']) if rows else None, M=P, row_index=ws['s2pos'], pe_at_index=at_pos, lo8_flag=ws['lo8_flag'] if (rows and rt.lo8) else None,
             **({} if self.depth_num == 64 and self.with_fpe else dict(Kp=self.pe_kp)),            # (64 bins: the entries without a size argument, as before)
             **({} if self.with_fpe else dict(gate=False)))                                          # (with_fpe=False: the gate-less kernel, mv2d_pe_fused_x3_ng)
+
+    def _build_pe_q(self, ws, sh, Pt, V, h, w):
+        """The table of the cached frustum MLP, Q [Pt,256] = position_encoder(frustum rows) + b1b at every position of ONE sample, with the matrices
+        this frame uploaded: the gate-less PE kernel on a one-row zero table (the gated kernel's bits of P1 + b1b; x + 0.0f keeps every value but
+        -0.0f).  Enqueued on the current stream in front of the frame, outside any captured graph; written in place when the table exists, so that
+        captured graphs keep a valid pointer.  A once-per-calibration cost (17 MB and ~0.13 ms at cfg2_s)."""
+        T, o, d = ws['tab'], ops, self.dev
+        a1 = torch.zeros((Pt, self.pe_kp), device=d, dtype=F32)
+        o.pe_frustum_f32(torch.arange(Pt, dtype=torch.int32, device=d), torch.tensor([Pt], dtype=torch.int32, device=d), Pt, T['img2lidar'], T['coords_w'],
+                         T['coords_h'], T['coords_d'], a1, V, h, w, self.depth_num, self.pe_range_h64, ld=self._pe_ld())
+        q = sh.get('pe_q')
+        if q is None or tuple(q.shape) != (Pt, C):
+            if q is not None:
+                sh['pe_q_gen'] = sh.get('pe_q_gen', 0) + 1
+            q = sh['pe_q'] = torch.empty((Pt, C), device=d, dtype=F32)
+        if sh.get('pe_q_zero') is None:
+            sh['pe_q_zero'] = torch.zeros((1, C), device=d, dtype=F32)
+        o.pe_fused_x3(a1, None, None, self.w['pe_x3'], sh['pe_q_zero'], 1, pe=q, M=Pt, Kp=self.pe_kp, gate=False)
+        self.pe_cache_builds = getattr(self, 'pe_cache_builds', 0) + 1
 
     def _pe_ld(self):
         """Row pitch argument of the frustum-row producers: None (the entries without a pitch, rows of 3 * depth_num columns) unless the rows are padded."""
@@ -1063,7 +1108,8 @@ class HeadEngine:
     def _result(self, ws, R, batch=False):
         sel = (lambda t: t) if batch else (lambda t: t[0])
         out = dict(R=R, ws=ws, cls=ws['cls'][:, :R], reg=ws['reg'][:, :R], boxes=sel(ws['boxes']), scores=sel(ws['scores']), labels=sel(ws['labels']),
-                   bbox_index=sel(ws['bbox_index']), count=ws['count'] if batch else ws['count'][:1], grp_start=ws['grp_start_h'].clone())
+                   bbox_index=sel(ws['bbox_index']), count=ws['count'] if batch else ws['count'][:1], grp_start=ws['grp_start_h'].clone(),
+                   pe_cache=ws.get('pe_cache_state', 'off'))     # 'off' | 'miss' | 'build' | 'hit': what this frame's PE launch was (route option pe_cache)
         if ws['route'].stages:
             # copies of the intermediate buffers restricted to the REAL rows (the launches run on the bucket size, see _host_prepare)
             rows0 = ('rois', 'minv', 'enc', 'roi_feat', 'center', 'xyz', 'ref', 'posemb', 'qpos', 'match')
@@ -1149,8 +1195,20 @@ class HeadEngine:
                 self.use_reg_layer, self.group_reg_dims, self.num_reg_fcs, self._weights_version, rt)
         graphs = ws.setdefault('graphs', {})             # one graph per (input buffers, frame scalars): a producer that alternates between
         g = graphs.get(gkey)                             # a few static output buffers replays a few graphs, it does not re-capture
+        # A key's graph exists in up to two FORMS: with the full PE launches, or with the gate-only one (pe_hit, route option pe_cache).  ws['graphs']
+        # holds the form the key's last frame ran, the other one is parked beside it and swapped back in when the form flips (a rig's first frame
+        # captures the full form, its second the hit form; a stream never re-captures a form it has)
+        hit, parked = ws['pe_hit'], ws.setdefault('graphs_other_pe_form', {})
+        if g is not None and g[2] != hit:
+            other = parked.pop(gkey, None)
+            if len(parked) >= 32:
+                parked.pop(next(iter(parked)))
+            parked[gkey] = graphs.pop(gkey)
+            g = other
+            if g is not None:
+                graphs[gkey] = g
         if ws.pop('graph_stale', False):
-            graphs.clear()
+            graphs.clear(); parked.clear()
             g = None
         if g is None:
             prof, self.prof = self.prof, None
@@ -1167,7 +1225,7 @@ class HeadEngine:
             self.prof = prof
             if len(graphs) >= 32:      # (input buffers x payload rows a producer cycles through: bench.py replays 12 per engine)
                 graphs.pop(next(iter(graphs)))
-            graphs[gkey] = (g, feat)
+            graphs[gkey] = (g, feat, hit)
         else:
             g = g[0]
         g.replay()

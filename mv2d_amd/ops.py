@@ -699,6 +699,27 @@ def pe_fused_x3(A1, Xmap, m_dev, wx, sine_tab, tab_period, pe=None, Xk=None, Xv=
     return pe
 
 
+def pe_gate_x3(Q, Xmap, m_dev, wx, sine_tab, tab_period, pe, M, row_index=None, pe_at_index=False, map_fmt=None, Xk=None, Xv=None):
+    """The gate of pe_fused_x3 alone on a cached frustum MLP (csrc/pe_x3_gate.hip): pe[m] = sine_tab[pos] + Q[pos] * gate(Xmap row), pos = row_index[m]
+    % tab_period.  Q [tab_period,256] fp32 = what pe_fused_x3(..., gate=False) writes on a one-row zero table for every position of one sample; wx:
+    'wr','we' pack_x3 pairs + 'br','be'.  pe is bit for bit pe_fused_x3's on the frustum rows Q was built from.  pe only: Xk / Xv are refused."""
+    name = 'mv2d_pe_gate_x3'
+    _req(Q, torch.float32, name + ': Q'); _req(sine_tab, torch.float32, name + ': sine_tab'); _req(pe, torch.float32, name + ': pe')
+    if Q is None or pe is None or Xmap is None:
+        raise _lib.Mv2dHipError(name + ': Q, Xmap and pe are required')
+    fmt = _req_map(Xmap, name + ': Xmap', map_fmt)
+    _req(row_index, torch.int32, name + ': row_index'); _req(m_dev, torch.int32, name + ': m_dev')
+    for k in ('wr', 'we'):
+        _req(wx[k][0], q16_dtype(), name + ': ' + k); _req(wx[k][1], q16_dtype(), name + ': ' + k)
+    if int(tab_period) > 0 and (tuple(Q.shape) != (int(tab_period), 256) or sine_tab.dim() != 2 or sine_tab.shape[0] < int(tab_period) or sine_tab.shape[1] != 256):
+        raise _lib.Mv2dHipError(f'{name}: Q {tuple(Q.shape)} / sine_tab {tuple(sine_tab.shape)} do not hold tab_period = {tab_period} rows of 256')
+    xk, xv = Xk or (None, None), Xv or (None, None)
+    check(_lib.load().mv2d_pe_gate_x3(_p(Q), _p(Xmap), _p(row_index), _p(m_dev), int(M), _p(wx['wr'][0]), _p(wx['wr'][1]), _p(wx['br']), _p(wx['we'][0]),
+                                      _p(wx['we'][1]), _p(wx['be']), _p(sine_tab), int(tab_period), _p(pe), _p(xk[0]), _p(xk[1]), _p(xv[0]), _p(xv[1]),
+                                      1 if (pe_at_index and row_index is not None) else 0, fmt, _stream()), name)
+    return pe
+
+
 def pe_fused_x3b(A1, Xmap, m_dev, wx, sine_tab, tab_period, pe=None, Xk=None, Xv=None, M=None, row_index=None, pe_at_index=False, lo8_flag=None):
     """pe_fused_x3 on the second shape of the kernel (csrc/pe_x3b.hip: a wave owns 16 rows through both layers, the hidden layer stays in registers, the
     weights go through an LDS ring): bitwise the same outputs.  wx additionally holds 'w1a_p', 'wr_p' = pack_x3_rowperm of the two first-layer weights."""

@@ -17,7 +17,7 @@ def default_options():
         xattn_waves=int(env('MV2D_XATTN_WAVES', '2')), q_order=True, fold_sa0=True, masked_transpose=True, last_stage_heads=False,
         exact_skip=frozenset({'conv'}), lo8_rows=True, pe_at_positions=env('MV2D_PE_AT_POS', '1') != '0', pe_rows_in_waves=False,
         ablate_zero_lo=frozenset(), keep_sine_rows=False, stop_before_decoder=False, force_nc=None, debug_attn=False,
-        fuse_qg_tail=env('MV2D_QG_TAIL', '1') != '0')
+        fuse_qg_tail=env('MV2D_QG_TAIL', '1') != '0', pe_cache=env('MV2D_PE_CACHE', '1') != '0')
 
 
 OPTIONS = tuple(default_options())
@@ -124,6 +124,13 @@ class Route(NamedTuple):
     # replaces).  Not for keep_stages runs (they expose enc, which the launch does not write); the engine also keeps the four launches for
     # the training route and for weights of other than the shipped dimensions.  MV2D_QG_TAIL=0 turns it off (A/B runs).
     qg_tail_fused: bool
+    # option pe_cache: on a rig whose camera matrices repeat from frame to frame, the frustum MLP of the PE (56 of the 72 k-steps of csrc/pe_x3.hip at 64
+    # bins, and the frustum-row launch in front of it) is computed ONCE into a per-position table Q = position_encoder(A1) + b1b and a frame runs only
+    # the gate (csrc/pe_x3_gate.hip: pe = tab + Q * gate, bit for bit the full kernel's pe).  This field: the route ALLOWS it -- S path, split-precision
+    # PE with its gate (with_fpe) and its sine table (not no_sin_enc: Q and the table share one period), no keep_stages run, not the training route's
+    # sine rows, not the rows-in-waves shape.  Whether a frame does use the table is decided per frame from its matrices (mv2d_amd/pe_cache.py) and is
+    # part of the graph key next to the route.  MV2D_PE_CACHE=0 turns it off (A/B runs).
+    pe_cache: bool
 
     @property
     def storage(self):
@@ -166,6 +173,9 @@ def resolve(opts, kind, exact, depth_num, map_dtype=torch.float32, keep_stages=F
         raise ValueError('ablate_zero_lo works on key16 lo rows: set lo8_rows = False')
     assert not (debug and use_graph), 'debug_attn: eager runs only'
     pe_pos = kind == 'S' and exact and bool(o.pe_at_positions)
+    pe_opt = lambda key, shipped: (pe_options or {}).get(key, shipped)      # noqa: E731
+    pe_cache = (bool(o.pe_cache) and kind == 'S' and pe_x3 and bool(pe_opt('with_fpe', True)) and not pe_opt('no_sin_enc', False) and not stages
+                and not o.keep_sine_rows and not o.pe_rows_in_waves)
     forked = kind == 'T' and (o.prof is None or use_graph) and bool(o.fork_qg) and not exact        # (a graph is captured with stage timing off)
     return Route(
         kind=kind, exact=exact, lo8=lo8, pe_pos=pe_pos, group_tab=group, q_order=bool(o.q_order), map_dtype=map_dtype, stages=stages,
@@ -176,4 +186,4 @@ def resolve(opts, kind, exact, depth_num, map_dtype=torch.float32, keep_stages=F
         masked=bool(o.masked_transpose) and not forked and not o.keep_sine_rows and not stages,
         last_stage_heads=bool(o.last_stage_heads) and not stages, debug_attn=debug, stop_before_decoder=bool(o.stop_before_decoder),
         force_nc=o.force_nc, ablate_zero_lo=frozenset(o.ablate_zero_lo) if exact else frozenset(),
-        qg_tail_fused=bool(o.fuse_qg_tail) and not stages)
+        qg_tail_fused=bool(o.fuse_qg_tail) and not stages, pe_cache=pe_cache)
