@@ -1205,6 +1205,10 @@ def roi_align(map0, rois, H, W, *, map1=None, out0=None, out1=None, out0_f32=Non
 
 def box_correlation(rois, view_start, trans, lin, depths, match, V, topk, pad_h, pad_w, max_per_view, sample_size=4,
                     num_depth=8, depth_start=0.5, iou_thr=0.0, ratio=0.0):
+    """match [R, V, topk] int32: per RoI and view of its sample the RoIs of that view in IoU rank order, -1 where the keep rule drops an entry,
+    behind the list, in the RoI's own view and in a view without RoIs.  lin / depths: calib.constant_tables(sample_size, num_depth, depth_start).
+    depth_start, iou_thr and ratio cross the ABI as fp32, the reference compares the camera depth with depth_start in double: pass an
+    fp32-representable depth_start (0.25, 0.5, 1.0, ...), or a sample whose depth lies between the two values is valid on one side only."""
     _req(rois, torch.float32, 'rois'); _req(view_start, torch.int32, 'view_start'); _req(trans, torch.float64, 'trans')
     _req(match, torch.int32, 'match')
     check(_lib.load().mv2d_box_correlation(_p(rois), _p(view_start), _p(trans), _p(lin), _p(depths), _p(match), rois.shape[0], V,
@@ -1213,13 +1217,14 @@ def box_correlation(rois, view_start, trans, lin, depths, match, V, topk, pad_h,
 
 
 def frame_geometry(rois, viewK, viewE, intr, ld_intr, minv, view_start, trans, lin, depths, match, V, topk, pad_h, pad_w, max_per_view,
-                   K_roi=None, roi_size=7.0, intr_scale=0.1, min_size=4.0, sample_size=4, num_depth=8, depth_start=0.5, iou_thr=0.0, ratio=0.0, zero=None):
-    """box_params + box_correlation (+ clearing the uint8 buffer `zero`) in one launch."""
+                   K_roi=None, roi_size=7.0, intr_scale=0.1, min_size=4.0, sample_size=4, num_depth=8, depth_start=0.5, iou_thr=0.0, ratio=0.0, zero=None, R=None):
+    """box_params + box_correlation (+ clearing the uint8 buffer `zero`) in one launch.  R: the number of RoIs when `rois` is a larger buffer
+    (default: its rows); R = 0 only clears `zero` (the pointers must still be valid: an empty tensor has none)."""
     _req(rois, torch.float32, 'rois'); _req(viewK, torch.float64, 'viewK'); _req(viewE, torch.float64, 'viewE'); _req(view_start, torch.int32, 'view_start')
     _req(trans, torch.float64, 'trans'); _req(match, torch.int32, 'match'); _req(zero, torch.uint8, 'zero')
     check(_lib.load().mv2d_frame_geometry(_p(rois), _p(viewK), _p(viewE), _p(K_roi), _p(intr), ld_intr, _p(minv), roi_size, intr_scale, min_size,
-                                          _p(view_start), _p(trans), _p(lin), _p(depths), _p(match), rois.shape[0], V, sample_size, num_depth, topk,
-                                          pad_h, pad_w, depth_start, iou_thr, ratio, max_per_view, _p(zero), zero.numel() if zero is not None else 0,
+                                          _p(view_start), _p(trans), _p(lin), _p(depths), _p(match), rois.shape[0] if R is None else R, V, sample_size,
+                                          num_depth, topk, pad_h, pad_w, depth_start, iou_thr, ratio, max_per_view, _p(zero), zero.numel() if zero is not None else 0,
                                           _stream()), 'mv2d_frame_geometry')
 
 

@@ -286,13 +286,14 @@ def epipolar_in_box(rois, num_per_view, image_shape, trans, topk, iou_thr=0.0, r
     return out
 
 
-def gen_box_roi_correlation(rois, num_per_view, img_metas, topk=1):
-    """S-path: box_correlation.py:165-193 -> corr [R,n_c] int64 (pad id 0), mask [R,n_c] bool."""
+def gen_box_roi_correlation(rois, num_per_view, img_metas, topk=1, iou_thr=0.0, ratio=0.0, sample_size=4, num_depth=8, depth_start=0.5):
+    """S-path: box_correlation.py:165-193 -> corr [R,n_c] int64 (pad id 0), mask [R,n_c] bool.  iou_thr .. depth_start: the keys of
+    epipolar_in_box (the defaults are the values the function used before it took them)."""
     R = rois.size(0)
     if rois.numel() == 0:
         return rois.new_zeros((0, 0), dtype=torch.int64), rois.new_zeros((0, 0), dtype=torch.bool)
     trans = view_transforms(img_metas)
-    ep = epipolar_in_box(rois, num_per_view, img_metas[0]['pad_shape'], trans, topk)
+    ep = epipolar_in_box(rois, num_per_view, img_metas[0]['pad_shape'], trans, topk, iou_thr, ratio, sample_size, num_depth, depth_start)
     rows = [[r] + [i for (i, k) in ep[r] if k] for r in range(R)]
     n_c = max(len(x) for x in rows)
     corr = torch.zeros((R, n_c), dtype=torch.int64)
@@ -317,12 +318,14 @@ def feat_in_rois_mask(rois, V, h, w, stride, expand_stride):
     return out
 
 
-def gen_box_correlation(rois, num_per_view, img_metas, h, w, stride=16, expand_stride=2, topk=20):
-    """T-path: box_correlation.py:95-162 -> feat_in_corr_rois [R,V,h,w] bool."""
+def gen_box_correlation(rois, num_per_view, img_metas, h, w, stride=16, expand_stride=2, topk=20, iou_thr=0.0, ratio=0.0, sample_size=4,
+                        num_depth=8, depth_start=0.5):
+    """T-path: box_correlation.py:95-162 -> feat_in_corr_rois [R,V,h,w] bool.  iou_thr .. depth_start: the keys of epipolar_in_box (the
+    defaults are the values the function used before it took them)."""
     V = len(img_metas)
     fin = feat_in_rois_mask(rois, V, h, w, stride, expand_stride)
     trans = view_transforms(img_metas)
-    ep = epipolar_in_box(rois, num_per_view, img_metas[0]['pad_shape'], trans, topk)
+    ep = epipolar_in_box(rois, num_per_view, img_metas[0]['pad_shape'], trans, topk, iou_thr, ratio, sample_size, num_depth, depth_start)
     out = torch.zeros_like(fin)
     for r in range(rois.size(0)):
         ids = [r] + [i for (i, k) in ep[r] if k]
