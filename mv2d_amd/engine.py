@@ -60,7 +60,7 @@ class HeadEngine:
         self.expand = float(expand_stride if expand_stride is not None else (0 if kind == 'S' else 2))
         self.max_num = max_num
         self.num_classes = int(num_classes)
-        if not 1 <= self.num_classes <= 64:       # the class output layer of mv2d_heads_fused_x3_nc: up to 4 column tiles of 16
+        if not 1 <= self.num_classes <= 64:       # the class output layer of the branch kernels: up to 4 column tiles of 16
             raise ValueError(f'HeadEngine: num_classes must be in [1, 64], got {num_classes}')
         # RoIAlign output size s (square): s x s bins per RoI -> s * s RoI cells (query-generator conv input; the S path's keys per RoI)
         self.roi_size = int(roi_size)
@@ -71,12 +71,12 @@ class HeadEngine:
         # the shipped shape, which allocates and launches exactly what it always did).  Fixed per engine: the state dict has to agree (load_state).
         self.qg = qg_shape.parse(query_generator, 'HeadEngine')
         # the regression branches as the reference's RegLayer (CrossAttentionBoxHead(use_reg_layer=True): two shared linears, one task head per
-        # entry of group_reg_dims) -- mv2d_reg_layer_x3 next to the class-only launch of the fused branches.  Fixed per engine: the state dict's
+        # entry of group_reg_dims) -- mv2d_reg_layer_depth_x3 next to the class-only launch of the fused branches.  Fixed per engine: the state dict's
         # key layout has to agree (load_state), and it is part of the graph key.
         self.use_reg_layer = bool(use_reg_layer)
         self.group_reg_dims = ops.check_group_reg_dims(group_reg_dims) if self.use_reg_layer else tuple(group_reg_dims)
-        # hidden layers per prediction branch (the head's num_reg_fcs; RegLayer's shared layers): 2 launches the first entries with their per-layer
-        # tables, 1 and 3 the depth entries with [L][n] tables (csrc/branches_x3.hip: one kernel pair behind both).  Fixed per engine: the state dict's branches have to have that depth.
+        # hidden layers per prediction branch (the head's num_reg_fcs; RegLayer's shared layers): every depth launches the depth entries with [L][n]
+        # tables (csrc/branches_x3.hip picks the kernel instance from n).  Fixed per engine: the state dict's branches have to have that depth.
         self.num_reg_fcs = ops.check_num_reg_fcs(num_reg_fcs, 'HeadEngine')
         # the PE's depth_num / depth_start / position_range (MU/pe.py:52-63).  Every consumer of the frustum rows takes them with Kp = pe_kp(depth_num)
         # columns (3 * depth_num zero-padded to a multiple of 32) and position_encoder.0.weight zero-padded to [1024, Kp]: one instance of the fused PE
@@ -163,39 +163,30 @@ class HeadEngine:
         w['post_w'], w['post_b'] = g(dec + 'post_norm.weight'), g(dec + 'post_norm.bias')
         w['qe_b0'], w['qe_b2'] = g('bbox_head.query_embedding.0.bias'), g('bbox_head.query_embedding.2.bias')
         w['qe_w0x'], w['qe_w2x'] = ops.pack_x3(g('bbox_head.query_embedding.0.weight')), ops.pack_x3(g('bbox_head.query_embedding.2.weight'))
+        # the box head's weight tables, one layout for every depth (csrc/branches_x3.hip STACKED): the nf hidden layers of a branch in one [L][nf]
+        # array, every tensor layer-major.  Class block i at cls_branches.{l}.{3i, 3i+1}, output at {3nf}; Sequential regression block i at {2i},
+        # output at {2nf}; RegLayer shared block i at reg_branch.{3i}, then one task head per entry of group_reg_dims
         st = lambda fmt: torch.stack([g(fmt.format(l)) for l in range(L)]).contiguous()
-        rb = 'bbox_head.reg_branches.'
-        if nf == 2:
-            for n in ('0', '3'):
-                w[f'cls_w{n}'], w[f'cls_b{n}'] = st('bbox_head.cls_branches.{}.' + n + '.weight'), st('bbox_head.cls_branches.{}.' + n + '.bias')
-            for n in ('1', '4'):
-                w[f'cls_lnw{n}'], w[f'cls_lnb{n}'] = st('bbox_head.cls_branches.{}.' + n + '.weight'), st('bbox_head.cls_branches.{}.' + n + '.bias')
-            w['cls_w6'], w['cls_b6'] = st('bbox_head.cls_branches.{}.6.weight'), st('bbox_head.cls_branches.{}.6.bias')
-        else:
-            # branches of another depth, stacked [L][nf]: class block i at {3i, 3i+1}, output at {3nf}; Sequential regression block i at {2i}, output
-            # at {2nf}; RegLayer shared block i at reg_branch.{3i}
-            stn = lambda fmt, idx: torch.stack([torch.stack([g(fmt.format(l, i)) for i in idx]) for l in range(L)]).contiguous()
-            cb = 'bbox_head.cls_branches.{}.{}.'
-            lin_i, ln_i = [3 * i for i in range(nf)], [3 * i + 1 for i in range(nf)]
-            w['clsd_w'], w['clsd_b'] = stn(cb + 'weight', lin_i), stn(cb + 'bias', lin_i)
-            w['clsd_lnw'], w['clsd_lnb'] = stn(cb + 'weight', ln_i), stn(cb + 'bias', ln_i)
-            w['clsd_wo'], w['clsd_bo'] = st('bbox_head.cls_branches.{}.' + str(3 * nf) + '.weight'), st('bbox_head.cls_branches.{}.' + str(3 * nf) + '.bias')
-            if self.use_reg_layer:
-                w['rld_s_w'], w['rld_s_b'] = stn(rb + '{}.reg_branch.{}.weight', lin_i), stn(rb + '{}.reg_branch.{}.bias', lin_i)
-            else:
-                w['regd_w'], w['regd_b'] = stn(rb + '{}.{}.weight', [2 * i for i in range(nf)]), stn(rb + '{}.{}.bias', [2 * i for i in range(nf)])
-                w['regd_wo'], w['regd_bo'] = st(rb + '{}.' + str(2 * nf) + '.weight'), st(rb + '{}.' + str(2 * nf) + '.bias')
+        stn = lambda fmt, idx: torch.stack([torch.stack([g(fmt.format(l, i)) for i in idx]) for l in range(L)]).contiguous()
+        cb, rb = 'bbox_head.cls_branches.{}.', 'bbox_head.reg_branches.{}.'
+        lin_i, ln_i, seq_i = [3 * i for i in range(nf)], [3 * i + 1 for i in range(nf)], [2 * i for i in range(nf)]
+        cls_src = (stn(cb + '{}.weight', lin_i), stn(cb + '{}.bias', lin_i), stn(cb + '{}.weight', ln_i), stn(cb + '{}.bias', ln_i),
+                   st(cb + f'{3 * nf}.weight'), st(cb + f'{3 * nf}.bias'))
         if self.use_reg_layer:
             G = len(self.group_reg_dims)
-            if nf == 2:
-                for n, k in (('s1', 'reg_branch.0'), ('s2', 'reg_branch.3')):
-                    w[f'rl_{n}_w'], w[f'rl_{n}_b'] = st(rb + '{}.' + k + '.weight'), st(rb + '{}.' + k + '.bias')
-            stg = lambda fmt, cat: torch.stack([cat([g(rb + fmt.format(l, g_)) for g_ in range(G)]) for l in range(L)]).contiguous()
-            w['rl_t1_w'], w['rl_t1_b'] = stg('{}.task_heads.{}.0.weight', torch.stack), stg('{}.task_heads.{}.0.bias', torch.stack)
-            w['rl_t2_w'], w['rl_t2_b'] = stg('{}.task_heads.{}.2.weight', torch.cat), stg('{}.task_heads.{}.2.bias', torch.cat)
-        elif nf == 2:
-            for n in ('0', '2', '4'):
-                w[f'reg_w{n}'], w[f'reg_b{n}'] = st(rb + '{}.' + n + '.weight'), st(rb + '{}.' + n + '.bias')
+            stg = lambda fmt, cat: torch.stack([cat([g(rb.format(l) + fmt.format(g_)) for g_ in range(G)]) for l in range(L)]).contiguous()
+            cls_t, _ = ops.pack_heads_depth(*cls_src)
+            reg_t = ops.pack_reg_layer_depth(stn(rb + 'reg_branch.{}.weight', lin_i), stn(rb + 'reg_branch.{}.bias', lin_i),
+                                             stg('task_heads.{}.0.weight', torch.stack), stg('task_heads.{}.0.bias', torch.stack),
+                                             stg('task_heads.{}.2.weight', torch.cat), stg('task_heads.{}.2.bias', torch.cat))
+        else:
+            cls_t, reg_t = ops.pack_heads_depth(*cls_src, stn(rb + '{}.weight', seq_i), stn(rb + '{}.bias', seq_i),
+                                                st(rb + f'{2 * nf}.weight'), st(rb + f'{2 * nf}.bias'))
+        w['head_tables'] = cls_t, reg_t = tuple(cls_t), tuple(reg_t)
+        self.cls_ptrs_x3, self.reg_ptrs_x3 = ops.make_ptr_array(list(cls_t)), ops.make_ptr_array(list(reg_t))
+        # the same tensors from the last decoder layer on: the launch of the last_stage_heads option
+        self._last_cls, self._last_reg = [t[L - 1:] for t in cls_t], [t[L - 1:] for t in reg_t]
+        self.cls_ptrs_x3_last, self.reg_ptrs_x3_last = ops.make_ptr_array(self._last_cls), ops.make_ptr_array(self._last_reg)
         q = 'query_generator.'
         self.qg.check_state(sd, self.roi_size, 'HeadEngine')
         if not self.qg.is_default:
@@ -253,32 +244,6 @@ class HeadEngine:
             if self.qg.is_default:
                 w['qg_conv_wx3'] = ops.pack_key16_x3(conv)
         self.w = w
-        if nf != 2:
-            # the tables of mv2d_heads_depth_x3 / mv2d_heads_cls_depth_x3 / mv2d_reg_layer_depth_x3 (every tensor layer-major, like the shipped ones)
-            seq = () if self.use_reg_layer else (w['regd_w'], w['regd_b'], w['regd_wo'], w['regd_bo'])
-            cls_t, reg_t = ops.pack_heads_depth(w['clsd_w'], w['clsd_b'], w['clsd_lnw'], w['clsd_lnb'], w['clsd_wo'], w['clsd_bo'], *seq)
-            if self.use_reg_layer:
-                reg_t = ops.pack_reg_layer_depth(w['rld_s_w'], w['rld_s_b'], w['rl_t1_w'], w['rl_t1_b'], w['rl_t2_w'], w['rl_t2_b'])
-            cls_t, reg_t = tuple(cls_t), tuple(reg_t)
-            w['heads_depth_tables'] = (cls_t, reg_t)
-        else:
-            cls_t, reg_t = self._shipped_head_tables(w)
-        self.cls_ptrs_x3, self.reg_ptrs_x3 = ops.make_ptr_array(list(cls_t)), ops.make_ptr_array(list(reg_t))
-        # the same tensors from the last decoder layer on: the launch of the last_stage_heads option (every tensor is stacked over L)
-        ll = self.L - 1
-        self._last_cls, self._last_reg = [t[ll:] for t in cls_t], [t[ll:] for t in reg_t]
-        self.cls_ptrs_x3_last, self.reg_ptrs_x3_last = ops.make_ptr_array(self._last_cls), ops.make_ptr_array(self._last_reg)
-
-    def _shipped_head_tables(self, w):
-        """the weight tables of the shipped depth (num_reg_fcs = 2): mv2d_heads_fused_x3(_nc) / mv2d_heads_cls_x3_nc / mv2d_reg_layer_x3"""
-        for k in ('cls_w0', 'cls_w3') + (() if self.use_reg_layer else ('reg_w0', 'reg_w2')):   # [L,256,256] -> bf16x3, fragment-major, stacked over L
-            w[k + 'x'] = ops.pack_x3_stack(w[k])
-        cls_t = (*w['cls_w0x'], w['cls_b0'], w['cls_lnw1'], w['cls_lnb1'], *w['cls_w3x'], w['cls_b3'], w['cls_lnw4'], w['cls_lnb4'], w['cls_w6'], w['cls_b6'])
-        if self.use_reg_layer:              # the weight table of mv2d_reg_layer_x3 (every tensor stacked over L, like the tables above)
-            reg_t = w['rl_table'] = tuple(ops.pack_reg_layer(*(w[f'rl_{n}_{k}'] for n in ('s1', 's2', 't1', 't2') for k in ('w', 'b'))))
-        else:
-            reg_t = (*w['reg_w0x'], w['reg_b0'], *w['reg_w2x'], w['reg_b2'], w['reg_w4'], w['reg_b4'])
-        return cls_t, reg_t
 
     def _load_qg_shape(self, g, w):
         """Packed weights and the launch plan of a query generator of other than the shipped shape (self.qg): w['qg_convs'] = [(key16 hi / lo
@@ -674,7 +639,7 @@ class HeadEngine:
             a1f = torch.empty((Pt, self.pe_kp), device=self.dev, dtype=F32)
             o.pe_inputs(s2, torch.tensor([Pt], dtype=torch.int32, device=self.dev), Pt, ws['featcl'], T['img2lidar'], T['coords_w'], T['coords_h'],
                         T['coords_d'], T['embeds'], self.const['dim_t'], k16e(self.pe_kp), k16e(384), k16e(C), None, V, h, w, self.depth_num,
-                        self.pe_range_h64, A_frustum_f32=a1f, A_sine_f32=a2f, ld=self._pe_ld())
+                        self.pe_range_h64, A_frustum_f32=a1f, A_sine_f32=a2f, ld=self.pe_kp)
             w2a, w2b = self._pe_w32['w2a'], self._pe_w32['w2b']
             h2 = o.linear_x3(a2f, W_['pe_w2a_x3'], W_['pe_b2a'], N=w2a.shape[0], K=w2a.shape[1], act=1)
             tab = o.linear_x3(h2, W_['pe_w2b_x3'], W_['pe_b2b'], N=w2b.shape[0], K=w2b.shape[1])
@@ -826,7 +791,7 @@ class HeadEngine:
             tk('pe_inputs')
             o.pe_inputs(ws['s2pos'], md, P, featcl, T['img2lidar'], T['coords_w'], T['coords_h'], T['coords_d'], T['embeds'],
                         self.const['dim_t'], ws['A1'], ws['A2'] if rt.keep_sine_rows else None, ws['Xf_b'], None,
-                        V, h, w, self.depth_num, self.pe_range_h64, ld=self._pe_ld())
+                        V, h, w, self.depth_num, self.pe_range_h64, ld=self.pe_kp)
             tk('pe_fused')
             # only what the path reads is written: S: pe (RoIAlign reads it; its keys are RoI-aligned rows), T: Xk (nothing reads pe);
             # a keep_stages run writes both
@@ -894,19 +859,20 @@ class HeadEngine:
             # (training route: it also reads the key16 rows and the sine rows)
             o.pe_inputs(ws['s2pos'], md, P, featcl, T['img2lidar'], T['coords_w'], T['coords_h'], T['coords_d'], T['embeds'],
                         self.const['dim_t'], ws['A1'], ws['A2'], ws['Xf_b'], None, V, h, w, self.depth_num,
-                        self.pe_range_h64, A_frustum_f32=ws['xa1'], A_sine_f32=ws['xa2'], ld=self._pe_ld())
+                        self.pe_range_h64, A_frustum_f32=ws['xa1'], A_sine_f32=ws['xa2'], ld=self.pe_kp)
         else:
             # the unrounded frustum rows alone (round 5: 156 -> ~50 us per 141 k positions; the feature rows are read from the map by the PE kernel)
             o.pe_frustum_f32(ws['s2pos'], md, P, T['img2lidar'], T['coords_w'], T['coords_h'], T['coords_d'], ws['xa1'], V, h, w, self.depth_num,
-                             self.pe_range_h64, ld=self._pe_ld())
+                             self.pe_range_h64, ld=self.pe_kp)
         sh = ws['shared']
         rows = rt.kind == 'T'
         at_pos = rt.pe_at_pos
+        # (pe_fused_x3b, opt-in, has the shipped PE's one instance: route.resolve lets it through for 64 bins with the gate only)
+        size = {} if rt.pe_rows_in_waves else dict(Kp=self.pe_kp, gate=self.with_fpe)
         (o.pe_fused_x3b if rt.pe_rows_in_waves else o.pe_fused_x3)(
             ws['xa1'], featcl, md, W_['pe_x3'], sh['sine_tab'], sh['sine_period'], pe=(ws['pe_pos'] if at_pos else ws['pe']) if (not rows or rt.stages) else None,
             Xk=(ws['Xk'], ws['xk_lo']) if rows else None, Xv=(ws['Xf_b'], ws['xv_lo']) if rows else None, M=P, row_index=ws['s2pos'], pe_at_index=at_pos, lo8_flag=ws['lo8_flag'] if (rows and rt.lo8) else None,
-            **({} if self.depth_num == 64 and self.with_fpe else dict(Kp=self.pe_kp)),            # (64 bins: the entries without a size argument, as before)
-            **({} if self.with_fpe else dict(gate=False)))                                          # (with_fpe=False: the gate-less kernel, mv2d_pe_fused_x3_ng)
+            **size)
 
     def _build_pe_q(self, ws, sh, Pt, V, h, w):
         """The table of the cached frustum MLP, Q [Pt,256] = position_encoder(frustum rows) + b1b at every position of ONE sample, with the matrices
@@ -916,7 +882,7 @@ class HeadEngine:
         T, o, d = ws['tab'], ops, self.dev
         a1 = torch.zeros((Pt, self.pe_kp), device=d, dtype=F32)
         o.pe_frustum_f32(torch.arange(Pt, dtype=torch.int32, device=d), torch.tensor([Pt], dtype=torch.int32, device=d), Pt, T['img2lidar'], T['coords_w'],
-                         T['coords_h'], T['coords_d'], a1, V, h, w, self.depth_num, self.pe_range_h64, ld=self._pe_ld())
+                         T['coords_h'], T['coords_d'], a1, V, h, w, self.depth_num, self.pe_range_h64, ld=self.pe_kp)
         q = sh.get('pe_q')
         if q is None or tuple(q.shape) != (Pt, C):
             if q is not None:
@@ -926,10 +892,6 @@ class HeadEngine:
             sh['pe_q_zero'] = torch.zeros((1, C), device=d, dtype=F32)
         o.pe_fused_x3(a1, None, None, self.w['pe_x3'], sh['pe_q_zero'], 1, pe=q, M=Pt, Kp=self.pe_kp, gate=False)
         self.pe_cache_builds = getattr(self, 'pe_cache_builds', 0) + 1
-
-    def _pe_ld(self):
-        """Row pitch argument of the frustum-row producers: None (the entries without a pitch, rows of 3 * depth_num columns) unless the rows are padded."""
-        return None if self.pe_kp == 3 * self.depth_num else self.pe_kp
 
     def pe_input_rows(self, ws, positions, V, h, w, f32=False):
         """PE input rows (frustum [n,Kp] = 3 * depth_num columns + zero pad, 192 at 64 bins; sine [n,384]; key16, or unrounded fp32 with f32=True) at the given map positions (int32, device)
@@ -944,7 +906,7 @@ class HeadEngine:
         a2f = torch.empty((n, 384), device=d, dtype=F32) if (f32 and not self.no_sin_enc) else None
         ops.pe_inputs(positions.contiguous(), torch.tensor([n], dtype=torch.int32, device=d), n, ws['featcl'], T['img2lidar'], T['coords_w'],
                       T['coords_h'], T['coords_d'], T['embeds'], self.const['dim_t'], a1, a2, xb, None, V, h, w, self.depth_num, self.pe_range_h64,
-                      A_frustum_f32=a1f, A_sine_f32=a2f, ld=self._pe_ld())
+                      A_frustum_f32=a1f, A_sine_f32=a2f, ld=self.pe_kp)
         return (a1f, a2f) if f32 else (a1, a2)
 
     def _enqueue_qg(self, ws, R):
@@ -1091,19 +1053,12 @@ class HeadEngine:
         cls_p, reg_p = (self.cls_ptrs_x3_last, self.reg_ptrs_x3_last) if last else (self.cls_ptrs_x3, self.reg_ptrs_x3)
         outs, cls, reg = ws['outs'][ll:], ws['cls'][ll:], ws['reg'][ll:]
         nf = self.num_reg_fcs
-        if nf != 2:
-            # another branch depth: the depth entries (csrc/branches_x3.hip) on their own tables, the same launch structure
-            if self.use_reg_layer:
-                ops.heads_cls_depth_x3(outs, cls_p, cls, R, n, nf, num_classes=self.num_classes)
-                ops.reg_layer_depth_x3(outs, reg_p, ws['ref'], reg, R, n, nf, self.group_reg_dims, self.pc_range_h, dt, dt_rows=dt_rows)
-            else:
-                ops.heads_depth_x3(outs, cls_p, reg_p, ws['ref'], cls, reg, R, n, nf, self.pc_range_h, dt, dt_rows=dt_rows, num_classes=self.num_classes)
-        elif self.use_reg_layer:
+        if self.use_reg_layer:
             # RegLayer regression branches: the class branch alone through the fused kernel, the regression branch + tail through its own
-            ops.heads_cls_x3(outs, cls_p, cls, R, n, num_classes=self.num_classes)
-            ops.reg_layer_x3(outs, reg_p, ws['ref'], reg, R, n, self.group_reg_dims, self.pc_range_h, dt, dt_rows=dt_rows)
+            ops.heads_cls_depth_x3(outs, cls_p, cls, R, n, nf, num_classes=self.num_classes)
+            ops.reg_layer_depth_x3(outs, reg_p, ws['ref'], reg, R, n, nf, self.group_reg_dims, self.pc_range_h, dt, dt_rows=dt_rows)
         else:
-            ops.heads_fused_x3(outs, cls_p, reg_p, ws['ref'], cls, reg, R, n, self.pc_range_h, dt, dt_rows=dt_rows, num_classes=self.num_classes)
+            ops.heads_depth_x3(outs, cls_p, reg_p, ws['ref'], cls, reg, R, n, nf, self.pc_range_h, dt, dt_rows=dt_rows, num_classes=self.num_classes)
 
     def _result(self, ws, R, batch=False):
         sel = (lambda t: t) if batch else (lambda t: t[0])

@@ -571,14 +571,9 @@ def pe_fused_tab(A1, Xfb, Xf32, m_dev, wp, sine_tab, tab_period, pe, Xk, M=None,
     _req16(A1, 'A1'); _req16(Xfb, 'Xfb'); _req(sine_tab, torch.float32, 'sine_tab'); _req16(Xk, 'Xk')
     fmt = 0 if Xf32 is None else _req_map(Xf32, 'Xf32', map_fmt)
     M = A1.shape[0] if M is None else M
-    if fmt:
-        check(_lib.load().mv2d_pe_fused_tab_fmt(_p(A1), _p(Xfb), _p(Xf32), _p(row_index), _p(m_dev), M, _p(wp['w1a']), _p(wp['b1a']), _p(wp['w1b']),
-                                                _p(wp['b1b']), _p(wp['wr']), _p(wp['br']), _p(wp['we']), _p(wp['be']), _p(sine_tab), int(tab_period),
-                                                _p(pe), _p(Xk), int(shape), fmt, _stream()), 'mv2d_pe_fused_tab_fmt')
-        return pe, Xk
-    check(_lib.load().mv2d_pe_fused_tab2(_p(A1), _p(Xfb), _p(Xf32), _p(row_index), _p(m_dev), M, _p(wp['w1a']), _p(wp['b1a']), _p(wp['w1b']),
-                                         _p(wp['b1b']), _p(wp['wr']), _p(wp['br']), _p(wp['we']), _p(wp['be']), _p(sine_tab), int(tab_period),
-                                         _p(pe), _p(Xk), int(shape), _stream()), 'mv2d_pe_fused_tab')
+    check(_lib.load().mv2d_pe_fused_tab_fmt(_p(A1), _p(Xfb), _p(Xf32), _p(row_index), _p(m_dev), M, _p(wp['w1a']), _p(wp['b1a']), _p(wp['w1b']),
+                                            _p(wp['b1b']), _p(wp['wr']), _p(wp['br']), _p(wp['we']), _p(wp['be']), _p(sine_tab), int(tab_period),
+                                            _p(pe), _p(Xk), int(shape), fmt, _stream()), 'mv2d_pe_fused_tab')
     return pe, Xk
 
 
@@ -651,8 +646,8 @@ def pad_pe_w1a(W, depth_num=None):
 def pe_fused_x3(A1, Xmap, m_dev, wx, sine_tab, tab_period, pe=None, Xk=None, Xv=None, M=None, row_index=None, pe_at_index=False, lo8_flag=None,
                 map_fmt=None, Kp=None, gate=True):
     """The PE block in split precision on unrounded inputs (index-exact route, csrc/pe_x3.hip).  gate=False: the PE without the feature-guided gate
-    (with_fpe=False; mv2d_pe_fused_x3_ng, any Kp): wx needs no 'wr','we','br','be', and Xmap may be None when neither Xk nor Xv is asked for.  A1 [M,Kp] fp32 (Kp = pe_kp(depth_num): frustum rows with zero
-    pad columns, wx['w1a'] packed from pad_pe_w1a(weight); Kp=None: the 192 columns of 64 bins through the entries that have no size argument); Xmap feature rows, fp32, fp16 or
+    (with_fpe=False; mv2d_pe_fused_x3_ng): wx needs no 'wr','we','br','be', and Xmap may be None when neither Xk nor Xv is asked for.  A1 [M,Kp] fp32 (Kp = pe_kp(depth_num): frustum rows with zero
+    pad columns, wx['w1a'] packed from pad_pe_w1a(weight); Kp=None: the columns of A1; the library picks the kernel instance from Kp); Xmap feature rows, fp32, fp16 or
     bf16 (widened in the kernel; indexed by row_index when given); wx: dict 'w1a','w1b','wr','we' = pack_x3(weight) pairs + fp32 biases 'b1a','b1b','br','be'; pe [M,256]
     fp32 and / or Xk = (hi, lo), Xv = (hi, lo) key16 [M,256] pairs (key rows pe + feat, value rows feat).  pe_at_index: pe row m goes to row
     row_index[m] of `pe` (a position-indexed map for roi_align without map1_index)."""
@@ -667,35 +662,17 @@ def pe_fused_x3(A1, Xmap, m_dev, wx, sine_tab, tab_period, pe=None, Xk=None, Xv=
         _req(wx[k][0], q16_dtype(), k); _req(wx[k][1], q16_dtype(), k)
     M = A1.shape[0] if M is None else M
     xk, xv = Xk or (None, None), Xv or (None, None)
-    if not gate:
-        Kp = 192 if Kp is None else Kp
-        if A1.dim() != 2 or A1.shape[1] != Kp or wx['w1a'][0].numel() != 1024 * Kp:
-            raise _lib.Mv2dHipError(f'pe_fused_x3: A1 {tuple(A1.shape)} / w1a ({wx["w1a"][0].numel()} elements) do not have Kp = {Kp} columns')
-        check(_lib.load().mv2d_pe_fused_x3_ng(_p(A1), _p(Xmap), _p(row_index), _p(m_dev), M, _p(wx['w1a'][0]), _p(wx['w1a'][1]), _p(wx['b1a']),
-                                              _p(wx['w1b'][0]), _p(wx['w1b'][1]), _p(wx['b1b']), _p(sine_tab), int(tab_period), _p(pe), _p(xk[0]), _p(xk[1]),
-                                              _p(xv[0]), _p(xv[1]), lo_fmt, 1 if (pe_at_index and row_index is not None) else 0, _p(lo8_flag), fmt, int(Kp),
-                                              _stream()), 'mv2d_pe_fused_x3_ng')
-        return pe
-    if Kp is not None:
-        if A1.dim() != 2 or A1.shape[1] != Kp or wx['w1a'][0].numel() != 1024 * Kp:
-            raise _lib.Mv2dHipError(f'pe_fused_x3: A1 {tuple(A1.shape)} / w1a ({wx["w1a"][0].numel()} elements) do not have Kp = {Kp} columns')
-        check(_lib.load().mv2d_pe_fused_x3_k(_p(A1), _p(Xmap), _p(row_index), _p(m_dev), M, _p(wx['w1a'][0]), _p(wx['w1a'][1]), _p(wx['b1a']),
-                                             _p(wx['w1b'][0]), _p(wx['w1b'][1]), _p(wx['b1b']), _p(wx['wr'][0]), _p(wx['wr'][1]), _p(wx['br']),
-                                             _p(wx['we'][0]), _p(wx['we'][1]), _p(wx['be']), _p(sine_tab), int(tab_period), _p(pe), _p(xk[0]), _p(xk[1]),
-                                             _p(xv[0]), _p(xv[1]), lo_fmt, 1 if (pe_at_index and row_index is not None) else 0, _p(lo8_flag), fmt, int(Kp),
-                                             _stream()), 'mv2d_pe_fused_x3_k')
-        return pe
-    if fmt:
-        check(_lib.load().mv2d_pe_fused_x3_fmt(_p(A1), _p(Xmap), _p(row_index), _p(m_dev), M, _p(wx['w1a'][0]), _p(wx['w1a'][1]), _p(wx['b1a']),
-                                               _p(wx['w1b'][0]), _p(wx['w1b'][1]), _p(wx['b1b']), _p(wx['wr'][0]), _p(wx['wr'][1]), _p(wx['br']),
-                                               _p(wx['we'][0]), _p(wx['we'][1]), _p(wx['be']), _p(sine_tab), int(tab_period), _p(pe), _p(xk[0]), _p(xk[1]),
-                                               _p(xv[0]), _p(xv[1]), lo_fmt, 1 if (pe_at_index and row_index is not None) else 0, _p(lo8_flag), fmt,
-                                               _stream()), 'mv2d_pe_fused_x3_fmt')
-        return pe
-    check(_lib.load().mv2d_pe_fused_x3(_p(A1), _p(Xmap), _p(row_index), _p(m_dev), M, _p(wx['w1a'][0]), _p(wx['w1a'][1]), _p(wx['b1a']),
-                                       _p(wx['w1b'][0]), _p(wx['w1b'][1]), _p(wx['b1b']), _p(wx['wr'][0]), _p(wx['wr'][1]), _p(wx['br']),
-                                       _p(wx['we'][0]), _p(wx['we'][1]), _p(wx['be']), _p(sine_tab), int(tab_period), _p(pe), _p(xk[0]), _p(xk[1]),
-                                       _p(xv[0]), _p(xv[1]), lo_fmt, 1 if (pe_at_index and row_index is not None) else 0, _p(lo8_flag), _stream()), 'mv2d_pe_fused_x3')
+    Kp = A1.shape[-1] if Kp is None else Kp
+    if A1.dim() != 2 or A1.shape[1] != Kp or wx['w1a'][0].numel() != 1024 * Kp:
+        raise _lib.Mv2dHipError(f'pe_fused_x3: A1 {tuple(A1.shape)} / w1a ({wx["w1a"][0].numel()} elements) do not have Kp = {Kp} columns')
+    rows = (_p(A1), _p(Xmap), _p(row_index), _p(m_dev), M, _p(wx['w1a'][0]), _p(wx['w1a'][1]), _p(wx['b1a']), _p(wx['w1b'][0]), _p(wx['w1b'][1]), _p(wx['b1b']))
+    outs = (_p(sine_tab), int(tab_period), _p(pe), _p(xk[0]), _p(xk[1]), _p(xv[0]), _p(xv[1]), lo_fmt, 1 if (pe_at_index and row_index is not None) else 0,
+            _p(lo8_flag), fmt, int(Kp), _stream())
+    if gate:
+        check(_lib.load().mv2d_pe_fused_x3_k(*rows, _p(wx['wr'][0]), _p(wx['wr'][1]), _p(wx['br']), _p(wx['we'][0]), _p(wx['we'][1]), _p(wx['be']), *outs),
+              'mv2d_pe_fused_x3')
+    else:
+        check(_lib.load().mv2d_pe_fused_x3_ng(*rows, *outs), 'mv2d_pe_fused_x3_ng')
     return pe
 
 
@@ -763,12 +740,8 @@ def qg_conv_pool(roi_feat, W, bias, out, R=None, ld_out=None, roi_size=7):
     _req16(roi_feat, 'roi_feat'); _req16(W, 'W'); _req(bias, torch.float32, 'bias'); _req(out, torch.float32, 'out')
     R = roi_feat.shape[0] if R is None else R
     s = _roi_size(roi_size)
-    if s == 7:
-        check(_lib.load().mv2d_qg_conv_pool(_p(roi_feat), _p(W), _p(bias), _p(out), out.stride(0) if ld_out is None else ld_out, R, _stream()),
-              'mv2d_qg_conv_pool')
-    else:
-        check(_lib.load().mv2d_qg_conv_pool_s(_p(roi_feat), _p(W), _p(bias), _p(out), out.stride(0) if ld_out is None else ld_out, R, s, _stream()),
-              'mv2d_qg_conv_pool_s')
+    check(_lib.load().mv2d_qg_conv_pool_s(_p(roi_feat), _p(W), _p(bias), _p(out), out.stride(0) if ld_out is None else ld_out, R, s, _stream()),
+          'mv2d_qg_conv_pool')
     return out
 
 
@@ -777,12 +750,8 @@ def qg_conv_pool_x3(roi_hi, roi_lo, W_x3, bias, out, R=None, ld_out=None, roi_si
     _req16(roi_hi, 'roi_hi'); _req16(roi_lo, 'roi_lo'); _req16(W_x3[0], 'W_hi'); _req16(W_x3[1], 'W_lo'); _req(bias, torch.float32, 'bias'); _req(out, torch.float32, 'out')
     R = roi_hi.shape[0] if R is None else R
     s = _roi_size(roi_size)
-    if s == 7:
-        check(_lib.load().mv2d_qg_conv_pool_x3(_p(roi_hi), _p(roi_lo), _p(W_x3[0]), _p(W_x3[1]), _p(bias), _p(out),
-                                               out.stride(0) if ld_out is None else ld_out, R, _stream()), 'mv2d_qg_conv_pool_x3')
-    else:
-        check(_lib.load().mv2d_qg_conv_pool_x3_s(_p(roi_hi), _p(roi_lo), _p(W_x3[0]), _p(W_x3[1]), _p(bias), _p(out),
-                                                 out.stride(0) if ld_out is None else ld_out, R, s, _stream()), 'mv2d_qg_conv_pool_x3_s')
+    check(_lib.load().mv2d_qg_conv_pool_x3_s(_p(roi_hi), _p(roi_lo), _p(W_x3[0]), _p(W_x3[1]), _p(bias), _p(out),
+                                             out.stride(0) if ld_out is None else ld_out, R, s, _stream()), 'mv2d_qg_conv_pool_x3')
     return out
 
 
@@ -876,16 +845,10 @@ def nchw_to_nhwc(x, out=None, mask=None, map_fmt=None):
             raise _lib.Mv2dHipError('nchw_to_nhwc: the masked form writes into a caller-owned buffer')
         out = torch.empty((V * h * w, Cn), device=x.device, dtype=x.dtype)
     _req(out, x.dtype, 'out')
-    if fmt:
-        if mask is not None:
-            check(_lib.load().mv2d_nchw_to_nhwc_masked_fmt(_p(x), _p(out), _p(mask), V, Cn, h * w, fmt, _stream()), 'mv2d_nchw_to_nhwc_masked_fmt')
-        else:
-            check(_lib.load().mv2d_nchw_to_nhwc_fmt(_p(x), _p(out), V, Cn, h * w, fmt, _stream()), 'mv2d_nchw_to_nhwc_fmt')
-        return out
     if mask is not None:
-        check(_lib.load().mv2d_nchw_to_nhwc_masked(_p(x), _p(out), _p(mask), V, Cn, h * w, _stream()), 'mv2d_nchw_to_nhwc_masked')
+        check(_lib.load().mv2d_nchw_to_nhwc_masked_fmt(_p(x), _p(out), _p(mask), V, Cn, h * w, fmt, _stream()), 'mv2d_nchw_to_nhwc_masked')
     else:
-        check(_lib.load().mv2d_nchw_to_nhwc(_p(x), _p(out), V, Cn, h * w, _stream()), 'mv2d_nchw_to_nhwc')
+        check(_lib.load().mv2d_nchw_to_nhwc_fmt(_p(x), _p(out), V, Cn, h * w, fmt, _stream()), 'mv2d_nchw_to_nhwc')
     return out
 
 
@@ -1178,29 +1141,17 @@ def posemb3d(ref, dim_t, out=None):
 def roi_align(map0, rois, H, W, *, map1=None, out0=None, out1=None, out0_f32=None, out1_f32=None, spatial_scale=1.0 / 16,
               sampling_ratio=-1, map1_index=None, out1_is_sum=False, R=None, out0_lo=None, out1_lo=None, out0_lo8=None, out1_lo8=None, lo8_flag=None,
               roi_size=7, map_fmt=None):
-    """roi_size s (1..14): s x s bins, every output [R, s*s, 256]; 7 runs the 7x7 entry mv2d_roi_align_ex.  map0 (the feature map) is fp32, fp16 or
-    bf16 -- a 16-bit map is widened in the kernel (mv2d_roi_align_fmt), the outputs are those of map0.float(); map1 (the PE map) is fp32."""
+    """roi_size s (1..14): s x s bins, every output [R, s*s, 256] (mv2d_roi_align_fmt: the library runs its 7x7 kernel at s = 7).  map0 (the feature
+    map) is fp32, fp16 or bf16 -- a 16-bit map is widened in the kernel, the outputs are those of map0.float(); map1 (the PE map) is fp32."""
     fmt = _req_map(map0, 'map0', map_fmt)
     _req(map1, torch.float32, 'map1'); _req(rois, torch.float32, 'rois')
     _req16(out0, 'out0'); _req16(out1, 'out1'); _req16(out0_lo, 'out0_lo'); _req16(out1_lo, 'out1_lo')
     _req(out0_lo8, torch.uint8, 'out0_lo8'); _req(out1_lo8, torch.uint8, 'out1_lo8'); _req(lo8_flag, torch.int32, 'lo8_flag')
     s = _roi_size(roi_size)
-    if fmt:
-        check(_lib.load().mv2d_roi_align_fmt(_p(map0), _p(map1), _p(rois), _p(out0), _p(out1), _p(out0_f32), _p(out1_f32),
-                                             rois.shape[0] if R is None else R, H, W, map0.shape[-1], spatial_scale, sampling_ratio,
-                                             _p(map1_index), 1 if out1_is_sum else 0, _p(out0_lo), _p(out1_lo), _p(out0_lo8), _p(out1_lo8), _p(lo8_flag), s,
-                                             fmt, _stream()), 'mv2d_roi_align_fmt')
-        return
-    if s != 7:
-        check(_lib.load().mv2d_roi_align_s(_p(map0), _p(map1), _p(rois), _p(out0), _p(out1), _p(out0_f32), _p(out1_f32),
-                                           rois.shape[0] if R is None else R, H, W, map0.shape[-1], spatial_scale, sampling_ratio,
-                                           _p(map1_index), 1 if out1_is_sum else 0, _p(out0_lo), _p(out1_lo), _p(out0_lo8), _p(out1_lo8), _p(lo8_flag), s,
-                                           _stream()), 'mv2d_roi_align_s')
-        return
-    check(_lib.load().mv2d_roi_align_ex(_p(map0), _p(map1), _p(rois), _p(out0), _p(out1), _p(out0_f32), _p(out1_f32),
-                                        rois.shape[0] if R is None else R, H, W, map0.shape[-1], spatial_scale, sampling_ratio,
-                                        _p(map1_index), 1 if out1_is_sum else 0, _p(out0_lo), _p(out1_lo), _p(out0_lo8), _p(out1_lo8), _p(lo8_flag), _stream()),
-          'mv2d_roi_align')
+    check(_lib.load().mv2d_roi_align_fmt(_p(map0), _p(map1), _p(rois), _p(out0), _p(out1), _p(out0_f32), _p(out1_f32),
+                                         rois.shape[0] if R is None else R, H, W, map0.shape[-1], spatial_scale, sampling_ratio,
+                                         _p(map1_index), 1 if out1_is_sum else 0, _p(out0_lo), _p(out1_lo), _p(out0_lo8), _p(out1_lo8), _p(lo8_flag), s,
+                                         fmt, _stream()), 'mv2d_roi_align')
 
 
 def box_correlation(rois, view_start, trans, lin, depths, match, V, topk, pad_h, pad_w, max_per_view, sample_size=4,
@@ -1252,25 +1203,15 @@ def roi_positions_csr(rois, pad_mask, roi_mask, rect, pos2s, s2pos, S_out, R, V,
     roi_size s (1..14): s*s cells per listed RoI, and the tap cells of an s x s RoIAlign (expand_stride < 0)."""
     _req(order, torch.int32, 'order'); _req(grp_start, torch.int32, 'grp_start'); _req(order_flags, torch.int32, 'order_flags')
     s = _roi_size(roi_size)
-    if s != 7:
-        check(_lib.load().mv2d_roi_positions_csr_s(_p(rois), _p(pad_mask), _p(roi_mask), _p(rect), _p(pos2s), _p(s2pos), _p(S_out), R, V, h, w, float(stride),
-                                                   float(expand_stride), _p(match), _p(row_ptr), _p(col_idx), _p(nnz_out), Vg, topk, _p(grp_start),
-                                                   grp_start.numel() - 1 if grp_start is not None else 0, _p(order), _p(order_flags), s, _stream()),
-              'mv2d_roi_positions_csr_s')
-        return
-    check(_lib.load().mv2d_roi_positions_csr(_p(rois), _p(pad_mask), _p(roi_mask), _p(rect), _p(pos2s), _p(s2pos), _p(S_out), R, V, h, w, float(stride),
-                                             float(expand_stride), _p(match), _p(row_ptr), _p(col_idx), _p(nnz_out), Vg, topk, _p(grp_start),
-                                             grp_start.numel() - 1 if grp_start is not None else 0, _p(order), _p(order_flags), _stream()),
+    check(_lib.load().mv2d_roi_positions_csr_s(_p(rois), _p(pad_mask), _p(roi_mask), _p(rect), _p(pos2s), _p(s2pos), _p(S_out), R, V, h, w, float(stride),
+                                               float(expand_stride), _p(match), _p(row_ptr), _p(col_idx), _p(nnz_out), Vg, topk, _p(grp_start),
+                                               grp_start.numel() - 1 if grp_start is not None else 0, _p(order), _p(order_flags), s, _stream()),
           'mv2d_roi_positions_csr')
 
 
 def csr_from_corr(match, row_ptr, col_idx, nnz_out, R, V, topk, roi_size=7):
     s = _roi_size(roi_size)
-    if s != 7:
-        check(_lib.load().mv2d_csr_from_corr_s(_p(match), _p(row_ptr), _p(col_idx), _p(nnz_out), R, V, topk, s, _stream()), 'mv2d_csr_from_corr_s')
-        return
-    check(_lib.load().mv2d_csr_from_corr(_p(match), _p(row_ptr), _p(col_idx), _p(nnz_out), R, V, topk, _stream()),
-          'mv2d_csr_from_corr')
+    check(_lib.load().mv2d_csr_from_corr_s(_p(match), _p(row_ptr), _p(col_idx), _p(nnz_out), R, V, topk, s, _stream()), 'mv2d_csr_from_corr')
 
 
 def pe_inputs(s2pos, S_dev, S_max, featcl, img2lidar, coords_w, coords_h, coords_d, embeds, dim_t, A_frustum, A_sine, Xf_k16,
@@ -1281,22 +1222,13 @@ def pe_inputs(s2pos, S_dev, S_max, featcl, img2lidar, coords_w, coords_h, coords
     _req16(A_frustum, 'A_frustum'); _req16(A_sine, 'A_sine'); _req16(Xf_k16, 'Xf_k16')
     _req(A_frustum_f32, torch.float32, 'A_frustum_f32'); _req(A_sine_f32, torch.float32, 'A_sine_f32'); _req(Xf_f32, torch.float32, 'Xf_f32')
     fmt = _req_map(featcl, 'featcl', map_fmt)
+    ld = 3 * depth_num if ld is None else int(ld)
     for t in (A_frustum, A_frustum_f32):
-        if t is not None and (t.dim() != 2 or t.shape[1] != (3 * depth_num if ld is None else ld)):
-            raise _lib.Mv2dHipError(f'pe_inputs: frustum rows {tuple(t.shape)} do not have {3 * depth_num if ld is None else ld} columns')
-    if ld is not None:
-        check(_lib.load().mv2d_pe_inputs_ld(_p(s2pos), _p(S_dev), S_max, _p(featcl), _p(img2lidar), _p(coords_w), _p(coords_h), _p(coords_d),
-                                            _p(embeds), _p(dim_t), _p(A_frustum), _p(A_sine), _p(Xf_k16), _p(Xf_f32), _p(A_frustum_f32),
-                                            _p(A_sine_f32), V, h, w, depth_num, position_range_host.data_ptr(), fmt, int(ld), _stream()), 'mv2d_pe_inputs_ld')
-        return
-    if fmt:
-        check(_lib.load().mv2d_pe_inputs_fmt(_p(s2pos), _p(S_dev), S_max, _p(featcl), _p(img2lidar), _p(coords_w), _p(coords_h), _p(coords_d),
-                                             _p(embeds), _p(dim_t), _p(A_frustum), _p(A_sine), _p(Xf_k16), _p(Xf_f32), _p(A_frustum_f32),
-                                             _p(A_sine_f32), V, h, w, depth_num, position_range_host.data_ptr(), fmt, _stream()), 'mv2d_pe_inputs_fmt')
-        return
-    check(_lib.load().mv2d_pe_inputs(_p(s2pos), _p(S_dev), S_max, _p(featcl), _p(img2lidar), _p(coords_w), _p(coords_h), _p(coords_d),
-                                     _p(embeds), _p(dim_t), _p(A_frustum), _p(A_sine), _p(Xf_k16), _p(Xf_f32), _p(A_frustum_f32),
-                                     _p(A_sine_f32), V, h, w, depth_num, position_range_host.data_ptr(), _stream()), 'mv2d_pe_inputs')
+        if t is not None and (t.dim() != 2 or t.shape[1] != ld):
+            raise _lib.Mv2dHipError(f'pe_inputs: frustum rows {tuple(t.shape)} do not have {ld} columns')
+    check(_lib.load().mv2d_pe_inputs_ld(_p(s2pos), _p(S_dev), S_max, _p(featcl), _p(img2lidar), _p(coords_w), _p(coords_h), _p(coords_d),
+                                        _p(embeds), _p(dim_t), _p(A_frustum), _p(A_sine), _p(Xf_k16), _p(Xf_f32), _p(A_frustum_f32),
+                                        _p(A_sine_f32), V, h, w, depth_num, position_range_host.data_ptr(), fmt, ld, _stream()), 'mv2d_pe_inputs')
 
 
 def pe_frustum_f32(s2pos, S_dev, S_max, img2lidar, coords_w, coords_h, coords_d, out, V, h, w, depth_num, position_range_host, ld=None):
@@ -1305,14 +1237,11 @@ def pe_frustum_f32(s2pos, S_dev, S_max, img2lidar, coords_w, coords_h, coords_d,
     _req(s2pos, torch.int32, 's2pos'); _req(S_dev, torch.int32, 'S_dev'); _req(out, torch.float32, 'out')
     for t, n_ in ((img2lidar, 'img2lidar'), (coords_w, 'coords_w'), (coords_h, 'coords_h'), (coords_d, 'coords_d')):
         _req(t, torch.float64, n_)
-    if out.dim() != 2 or out.shape[1] != (3 * depth_num if ld is None else ld):
-        raise _lib.Mv2dHipError(f'pe_frustum_f32: out {tuple(out.shape)} does not have {3 * depth_num if ld is None else ld} columns')
-    if ld is not None:
-        check(_lib.load().mv2d_pe_frustum_f32_ld(_p(s2pos), _p(S_dev), S_max, _p(img2lidar), _p(coords_w), _p(coords_h), _p(coords_d), _p(out), V, h, w,
-                                                 depth_num, position_range_host.data_ptr(), int(ld), _stream()), 'mv2d_pe_frustum_f32_ld')
-        return out
-    check(_lib.load().mv2d_pe_frustum_f32(_p(s2pos), _p(S_dev), S_max, _p(img2lidar), _p(coords_w), _p(coords_h), _p(coords_d), _p(out), V, h, w,
-                                          depth_num, position_range_host.data_ptr(), _stream()), 'mv2d_pe_frustum_f32')
+    ld = 3 * depth_num if ld is None else int(ld)
+    if out.dim() != 2 or out.shape[1] != ld:
+        raise _lib.Mv2dHipError(f'pe_frustum_f32: out {tuple(out.shape)} does not have {ld} columns')
+    check(_lib.load().mv2d_pe_frustum_f32_ld(_p(s2pos), _p(S_dev), S_max, _p(img2lidar), _p(coords_w), _p(coords_h), _p(coords_d), _p(out), V, h, w,
+                                             depth_num, position_range_host.data_ptr(), ld, _stream()), 'mv2d_pe_frustum_f32')
     return out
 
 
@@ -1352,7 +1281,7 @@ def pack_detections(boxes, scores, labels, count, out, max_num=300):
 
 class RoIAlignRows(torch.autograd.Function):
     """RoIAlign (mmcv semantics, s x s bins with s = roi_size (default 7), stride 16) of a position-major fp32 map [rows,256] -> [R,s*s,256]
-    fp32, differentiable w.r.t. the map (``mv2d_roi_align`` / ``mv2d_roi_align_bwd`` and their ``_s`` entries).  ``index`` (int32 [V*H*W] or
+    fp32, differentiable w.r.t. the map (``mv2d_roi_align_fmt`` / ``mv2d_roi_align_bwd_s``).  ``index`` (int32 [V*H*W] or
     None): position -> row of a compacted map (the PE rows of the S path); ``full`` is then any full-size map the kernel can read alongside
     (its output is discarded)."""
 
@@ -1375,12 +1304,8 @@ class RoIAlignRows(torch.autograd.Function):
         rois, index = ctx.saved_tensors
         H, W, n, indexed, s = ctx.meta
         gmap = torch.zeros((n, 256), device=gout.device, dtype=torch.float32)
-        if s == 7:
-            check(_lib.load().mv2d_roi_align_bwd(_p(gout.contiguous().float()), _p(rois), _p(gmap), _p(index) if indexed else None, rois.shape[0], H, W,
-                                                 256, 1.0 / 16, -1, _stream()), 'mv2d_roi_align_bwd')
-        else:
-            check(_lib.load().mv2d_roi_align_bwd_s(_p(gout.contiguous().float()), _p(rois), _p(gmap), _p(index) if indexed else None, rois.shape[0], H, W,
-                                                   256, 1.0 / 16, -1, s, _stream()), 'mv2d_roi_align_bwd_s')
+        check(_lib.load().mv2d_roi_align_bwd_s(_p(gout.contiguous().float()), _p(rois), _p(gmap), _p(index) if indexed else None, rois.shape[0], H, W,
+                                               256, 1.0 / 16, -1, s, _stream()), 'mv2d_roi_align_bwd')
         return gmap, None, None, None, None, None, None
 
 

@@ -25,7 +25,7 @@ C = 256
 class RegLayer(nn.Module):
     """RH/bbox_heads/cross_attention_head.py:52-83: the regression branch of a decoder layer as shared layers + one task head per group of
     box-code columns.  Parameter names as in the reference: ``reg_branch.{0,3}`` (Linear, ReLU, Dropout per shared layer) and
-    ``task_heads.{g}.{0,2}`` (``reg_branch.{3i}`` for ``shared_reg_fcs`` = the head's ``num_reg_fcs`` shared layers).  The module holds the parameters; the head evaluates it through mv2d_reg_layer_x3 (inference) or the autograd
+    ``task_heads.{g}.{0,2}`` (``reg_branch.{3i}`` for ``shared_reg_fcs`` = the head's ``num_reg_fcs`` shared layers).  The module holds the parameters; the head evaluates it through mv2d_reg_layer_depth_x3 (inference) or the autograd
     operators (training), ``forward`` is the plain torch statement of it."""
 
     def __init__(self, embed_dims=256, shared_reg_fcs=2, group_reg_dims=(2, 1, 3, 2, 2), drop=0.0):
@@ -55,12 +55,12 @@ class CrossAttentionBoxHead(nn.Module):
                  sync_cls_avg_factor=False, train_cfg=None, test_cfg=None, **kwargs):
         super().__init__()
         assert not pre_embed and embed_dims == C, 'kernel path implements the shipped head configuration'
-        # hidden layers per prediction branch (and RegLayer's shared layers): 1 to 3 (csrc/branches_x3.hip; 2 runs the shipped entries)
+        # hidden layers per prediction branch (and RegLayer's shared layers): 1 to 3 (csrc/branches_x3.hip: the depth entries, 2 is the shipped depth)
         self.num_reg_fcs = num_reg_fcs = ops.check_num_reg_fcs(num_reg_fcs, 'CrossAttentionBoxHead')
-        # the box code has 10 columns; with use_reg_layer every group is one task head of the RegLayer (mv2d_reg_layer_x3: 1 to 10 groups)
+        # the box code has 10 columns; with use_reg_layer every group is one task head of the RegLayer (mv2d_reg_layer_depth_x3: 1 to 10 groups)
         self.use_reg_layer = bool(use_reg_layer)
         self.group_reg_dims = ops.check_group_reg_dims(group_reg_dims) if self.use_reg_layer else tuple(group_reg_dims)
-        # the class output layer of the fused prediction branches (mv2d_heads_fused_x3_nc) holds up to 4 column tiles of 16 classes
+        # the class output layer of the fused prediction branches (csrc/branches_x3.hip) holds up to 4 column tiles of 16 classes
         if not 1 <= int(num_classes) <= 64:
             raise ValueError(f'CrossAttentionBoxHead: num_classes must be in [1, 64] (the fused heads kernel), got {num_classes}')
         coder_nc = (bbox_coder or {}).get('num_classes', 10)

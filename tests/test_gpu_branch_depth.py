@@ -394,6 +394,47 @@ def test_engine_eager_graph_batch_fp16_and_last_stage(case, problem, n, dims):
         HeadEngine(_state(n, dims), prob['kind'], torch.device(DEV), num_views=prob['views_per_frame'], **rl)
 
 
+def _per_layer_tables(sd, L, dims=None):
+    """The tables of the per-layer entries (ops.heads_fused_x3 / heads_cls_x3 / reg_layer_x3: one [L] array per hidden layer) from a depth-2 state
+    dict, packed as tests/test_gpu_branches_parent_bits.py packs them"""
+    from mv2d_amd import ops
+    t = lambda k: torch.as_tensor(sd['bbox_head.' + k]).float().to(DEV)
+    st = lambda fmt: torch.stack([t(fmt.format(l)) for l in range(L)]).contiguous()
+    c = {k: st('cls_branches.{}.' + k) for k in ('0.weight', '0.bias', '1.weight', '1.bias', '3.weight', '3.bias', '4.weight', '4.bias',
+                                                 '6.weight', '6.bias')}
+    cw = [*ops.pack_x3_stack(c['0.weight']), c['0.bias'], c['1.weight'], c['1.bias'], *ops.pack_x3_stack(c['3.weight']), c['3.bias'], c['4.weight'],
+          c['4.bias'], c['6.weight'], c['6.bias']]
+    if dims is None:
+        r = {k: st('reg_branches.{}.' + k) for k in ('0.weight', '0.bias', '2.weight', '2.bias', '4.weight', '4.bias')}
+        return cw, [*ops.pack_x3_stack(r['0.weight']), r['0.bias'], *ops.pack_x3_stack(r['2.weight']), r['2.bias'], r['4.weight'], r['4.bias']]
+    sg = lambda fmt, join: torch.stack([join([t('reg_branches.' + fmt.format(l, g)) for g in range(len(dims))]) for l in range(L)]).contiguous()
+    return cw, ops.pack_reg_layer(st('reg_branches.{}.reg_branch.0.weight'), st('reg_branches.{}.reg_branch.0.bias'),
+                                  st('reg_branches.{}.reg_branch.3.weight'), st('reg_branches.{}.reg_branch.3.bias'),
+                                  sg('{}.task_heads.{}.0.weight', torch.stack), sg('{}.task_heads.{}.0.bias', torch.stack),
+                                  sg('{}.task_heads.{}.2.weight', torch.cat), sg('{}.task_heads.{}.2.bias', torch.cat))
+
+
+def _assert_per_layer_entries_write_the_engines_bits(eng, out, sd):
+    """The per-layer entries on the decoder outputs and reference points the finished run left in its workspace, with the rows, time steps and tables
+    of the engine's own launch: cls and reg bit for bit the engine's (which launches the depth entries on [L][2] tables)."""
+    from mv2d_amd import ops
+    ws, R = out['ws'], out['R']
+    L, M = ws['outs'].shape[:2]
+    assert ws['cls'].shape[:2] == ws['reg'].shape[:2] == (L, M) and R <= M
+    dims = eng.group_reg_dims if eng.use_reg_layer else None
+    cw, rw = _per_layer_tables(sd, L, dims)
+    cp, rp = ops.make_ptr_array(cw), ops.make_ptr_array(rw)
+    cls, reg = torch.full_like(ws['cls'], SENTINEL), torch.full_like(ws['reg'], SENTINEL)
+    dt_rows = ws['dt_rows'] if eng.kind == 'T' else None
+    if dims is None:
+        ops.heads_fused_x3(ws['outs'], cp, rp, ws['ref'], cls, reg, M, L, eng.pc_range_h, out['dt'], dt_rows=dt_rows, num_classes=eng.num_classes)
+    else:
+        ops.heads_cls_x3(ws['outs'], cp, cls, M, L, num_classes=eng.num_classes)
+        ops.reg_layer_x3(ws['outs'], rp, ws['ref'], reg, M, L, dims, eng.pc_range_h, out['dt'], dt_rows=dt_rows)
+    assert bool(torch.isfinite(out['cls']).all()) and bool(torch.isfinite(out['reg']).all())
+    assert torch.equal(cls[:, :R], out['cls']) and torch.equal(reg[:, :R], out['reg'])
+
+
 @pytest.mark.parametrize('problem', ['cfg1_s', 'cfg1_t'])
 def test_engine_depth_2_is_the_engine_without_the_argument(problem):
     from mv2d_amd.engine import HeadEngine
@@ -401,12 +442,25 @@ def test_engine_depth_2_is_the_engine_without_the_argument(problem):
     sd = synthetic.make_head_state(seed=0)
     a = HeadEngine(sd, prob['kind'], torch.device(DEV), num_views=prob['views_per_frame'])
     b = HeadEngine(sd, prob['kind'], torch.device(DEV), num_views=prob['views_per_frame'], num_reg_fcs=2)
-    assert a.num_reg_fcs == b.num_reg_fcs == 2 and 'heads_depth_tables' not in b.w
+    assert a.num_reg_fcs == b.num_reg_fcs == 2
+    # one table layout for every depth: both engines hold the same table keys, and the same tables
+    assert set(a.w) == set(b.w) and 'head_tables' in a.w
+    for ta, tb in zip(a.w['head_tables'], b.w['head_tables']):
+        assert len(ta) == len(tb) and all(torch.equal(x, y) for x, y in zip(ta, tb))
     feat, props, metas = _inputs(prob)
     oa = {k: v.clone() for k, v in a.run(feat, props, metas).items() if torch.is_tensor(v)}
     ob = b.run(feat, props, metas)
     for k in ('cls', 'reg', 'boxes', 'scores', 'labels', 'bbox_index', 'count'):
         assert torch.equal(oa[k], ob[k]), k
+    _assert_per_layer_entries_write_the_engines_bits(b, ob, sd)
+
+
+def test_reg_layer_engine_writes_the_bits_of_the_per_layer_entries():
+    """use_reg_layer at the shipped depth: the engine's class-only + RegLayer launches on stacked tables against heads_cls_x3 + reg_layer_x3"""
+    prob = synthetic.make_problem('cfg1_s', seed=0)
+    eng = _engine(prob, 2, DEFAULT)
+    out = eng.run(*_inputs(prob))
+    _assert_per_layer_entries_write_the_engines_bits(eng, out, _state(2, DEFAULT))
 
 
 # ---------------------------------------------------------------------------------------------------------- 6. plugin head

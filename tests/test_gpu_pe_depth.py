@@ -59,6 +59,17 @@ def _pe_inputs(D, M, gather):
     return A, A1, Xmap, ri
 
 
+def pe_fused_x3_no_size(A1, Xmap, wx, tab, period, pe, Xk, Xv, M, ri):
+    """mv2d_pe_fused_x3_fmt, the entry of the 64 bins that has no size argument, called through the library itself (ops.pe_fused_x3 calls the
+    size-taking entry for every depth): fp32 / fp16 / bf16 map, rows gathered through ri, (hi, lo) row pairs Xk / Xv with key16 or e4m3 lo rows."""
+    from mv2d_amd import _lib, ops
+    weights = [wx[k][i].data_ptr() if i < 2 else wx['b' + k[1:]].data_ptr() for k in ('w1a', 'w1b', 'wr', 'we') for i in range(3)]
+    assert Xk[1].dtype == Xv[1].dtype
+    _lib.check(_lib.load().mv2d_pe_fused_x3_fmt(A1.data_ptr(), Xmap.data_ptr(), ri.data_ptr(), None, M, *weights, tab.data_ptr(), period, pe.data_ptr(),
+                                                Xk[0].data_ptr(), Xk[1].data_ptr(), Xv[0].data_ptr(), Xv[1].data_ptr(), int(Xk[1].dtype == torch.uint8), 0, None,
+                                                ops.map_format(Xmap.dtype), ops._stream()), 'mv2d_pe_fused_x3_fmt')
+
+
 @pytest.mark.parametrize('M,gather', [(1, False), (70, True), (200, False), (200, True)])
 @pytest.mark.parametrize('D', [8, 24, 32, 40, 64, 80])
 def test_pe_fused_x3_depth_against_fp64(D, M, gather):
@@ -121,14 +132,17 @@ def test_pe_fused_x3_depth_64_is_the_shipped_kernel(map_dtype):
         _, A1, Xmap, ri = _pe_inputs(64, M, True)
         Xmap = Xmap.to(map_dtype)
         outs = []
-        for kw in ({}, dict(Kp=192)):
+        for sized in (False, True, None):
             pe = torch.zeros((M, 256), device=DEV)
             pairs = [(torch.zeros((M, 256), device=DEV, dtype=k16), torch.zeros((M, 256), device=DEV, dtype=torch.uint8)) for _ in range(2)]
-            ops.pe_fused_x3(A1, Xmap, None, wx, tab, 41, pe=pe, Xk=pairs[0], Xv=pairs[1], M=M, row_index=ri, **kw)
+            if sized is False:
+                pe_fused_x3_no_size(A1, Xmap, wx, tab, 41, pe, pairs[0], pairs[1], M, ri)
+            else:                                       # (Kp stated, and Kp read from A1's columns)
+                ops.pe_fused_x3(A1, Xmap, None, wx, tab, 41, pe=pe, Xk=pairs[0], Xv=pairs[1], M=M, row_index=ri, **(dict(Kp=192) if sized else {}))
             outs.append([pe, *pairs[0], *pairs[1]])
         assert float(outs[0][0].abs().sum()) > 0
-        for a, b in zip(*outs):
-            assert torch.equal(a, b)
+        for a, b, c in zip(*outs):
+            assert torch.equal(a, b) and torch.equal(a, c)
 
 
 @pytest.mark.parametrize('D', [32, 40])
@@ -214,9 +228,16 @@ def test_pe_frustum_rows_with_pitch(D, start, rng):
         assert float((d16 / ref.abs().clamp_min(1.0)).max()) < ulp
     # without padding (ld = 3 D) the pitch-taking entries run the kernels of the entries without a pitch
     if 3 * D == Kp:
+        from mv2d_amd import _lib
         plain = torch.full((P, Kp), nan, device=DEV)
-        ops.pe_frustum_f32(s2pos, S_dev, P, T['img2lidar'], T['coords_w'], T['coords_h'], T['coords_d'], plain, V, h, w, D, pr)
+        # (mv2d_pe_frustum_f32 through the library itself: ops.pe_frustum_f32 calls the pitch-taking entry, with or without ld)
+        _lib.check(_lib.load().mv2d_pe_frustum_f32(s2pos.data_ptr(), S_dev.data_ptr(), P, T['img2lidar'].data_ptr(), T['coords_w'].data_ptr(),
+                                                   T['coords_h'].data_ptr(), T['coords_d'].data_ptr(), plain.data_ptr(), V, h, w, D, pr.data_ptr(),
+                                                   ops._stream()), 'mv2d_pe_frustum_f32')
         assert torch.equal(plain[:S], fast[:S])
+        no_ld = torch.full((P, Kp), nan, device=DEV)
+        ops.pe_frustum_f32(s2pos, S_dev, P, T['img2lidar'], T['coords_w'], T['coords_h'], T['coords_d'], no_ld, V, h, w, D, pr)      # ld=None: 3 D
+        assert torch.equal(no_ld[:S], fast[:S])
 
 
 # ---------------------------------------------------------------------------------------------------------- 3. engine vs the reference goldens

@@ -158,8 +158,9 @@ def test_pe_fused_x3_nogate_has_the_shipped_p1_bits(D):
         for a, b in zip(*outs):
             assert torch.equal(a, b)
     if D == 64:                                     # ... and through the shipped entry without a size argument (pe_x3_kernel<MT> itself)
+        from test_gpu_pe_depth import pe_fused_x3_no_size
         pe, pairs = _outs(M, k16, k16 == torch.float16)
-        ops.pe_fused_x3(A1, Xmap, None, one, tab, 41, pe=pe, Xk=pairs[0], Xv=pairs[1], M=M, row_index=ri)
+        pe_fused_x3_no_size(A1, Xmap, one, tab, 41, pe, pairs[0], pairs[1], M, ri)
         for a, b in zip([pe, *pairs[0], *pairs[1]], outs[1]):
             assert torch.equal(a, b)
 

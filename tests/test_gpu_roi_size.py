@@ -70,9 +70,15 @@ def test_roi_align_forward_roi_size(s):
     assert relerr(o1, want1) < 1e-6
     assert torch.equal(k0, ops.f32_to_key16(o0))           # the key16 output is the rounded fp32 output
     if s == 7:                                              # the 7x7 entry and the size-taking one agree bit for bit
+        from mv2d_amd import _lib
         o7 = torch.empty_like(o0)
-        ops.roi_align(m0, rd, h, w, out0_f32=o7, R=R)
+        # (mv2d_roi_align_ex through the library itself: ops.roi_align calls mv2d_roi_align_fmt for every size)
+        _lib.check(_lib.load().mv2d_roi_align_ex(m0.data_ptr(), None, rd.data_ptr(), None, None, o7.data_ptr(), None, R, h, w, 256, 1.0 / 16, -1, None, 0,
+                                                 None, None, None, None, None, ops._stream()), 'mv2d_roi_align_ex')
         assert torch.equal(o7, o0)
+        od = torch.empty_like(o0)
+        ops.roi_align(m0, rd, h, w, out0_f32=od, R=R)       # roi_size left at its default
+        assert torch.equal(od, o0)
 
 
 @pytest.mark.parametrize('s', [1, 2, 5, 9, 14])

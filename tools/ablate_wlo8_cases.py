@@ -50,6 +50,8 @@ def patched(self, *a, **k):
     if self.exact:
         for key, v in self.w.items():
             walk(key, v)
+        for i, table in enumerate(self.w['head_tables']):          # (class table, regression table): each starts with the hidden layers' (hi, lo) pair
+            walk(f'head_tables.{i}', table[:2])
 
 
 HeadEngine.__init__ = patched

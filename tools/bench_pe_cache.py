@@ -88,7 +88,7 @@ def kernel(workload, samples, launches, runs):
         def launch(form):          # HeadEngine._exact_pe's calls
             if form == 'full':
                 ops.pe_frustum_f32(ws['s2pos'], ws['S_dev'], P, T['img2lidar'], T['coords_w'], T['coords_h'], T['coords_d'], ws['xa1'], V, h, w, eng.depth_num,
-                                   eng.pe_range_h64, ld=eng._pe_ld())
+                                   eng.pe_range_h64, ld=eng.pe_kp)
                 ops.pe_fused_x3(ws['xa1'], ws['featcl_cur'], ws['S_dev'], eng.w['pe_x3'], sh['sine_tab'], sh['sine_period'], pe=bufs[form], M=P, row_index=ws['s2pos'],
                                 pe_at_index=True)
             else:

@@ -3,9 +3,9 @@
 
     python tools/bench_reg_layer.py [--samples 16] [--rounds 30]
 
-1. Launch times at the rows of cfg2_s with --samples samples per launch (R = 300 each): today's one launch mv2d_heads_fused_x3 against the
-   pair mv2d_heads_cls_x3_nc + mv2d_reg_layer_x3, each as a captured graph of 20 launches, the variants ALTERNATING inside one process
-   (median and minimum over --rounds rounds).
+1. Launch times at the rows of cfg2_s with --samples samples per launch (R = 300 each): today's one launch mv2d_heads_depth_x3 against the
+   pair mv2d_heads_cls_depth_x3 + mv2d_reg_layer_depth_x3 (n = 2, on the engines' own tables), each as a captured graph of 20 launches, the
+   variants ALTERNATING inside one process (median and minimum over --rounds rounds).
 2. Samples/s of one engine on one stream (run_batch of --samples cfg2_s samples, graph replay) with the switch off and on, alternating.
    Not bench.py's number: that runs four streams with rotating inputs."""
 import argparse
@@ -65,11 +65,11 @@ def main():
     cls, reg = torch.empty((L, M, 10), device=DEV), torch.empty((L, M, 10), device=DEV)
     pcr = plain.pc_range_h
     variants = {
-        'heads_fused_x3 (cls + Sequential reg, one launch)': lambda: ops.heads_fused_x3(outs, plain.cls_ptrs_x3, plain.reg_ptrs_x3, ref, cls, reg, M, L, pcr),
-        'heads_cls_x3 (cls alone)': lambda: ops.heads_cls_x3(outs, regl.cls_ptrs_x3, cls, M, L),
-        'reg_layer_x3 (RegLayer reg alone)': lambda: ops.reg_layer_x3(outs, regl.reg_ptrs_x3, ref, reg, M, L, DIMS, pcr),
-        'heads_cls_x3 + reg_layer_x3 (the pair)': lambda: (ops.heads_cls_x3(outs, regl.cls_ptrs_x3, cls, M, L),
-                                                           ops.reg_layer_x3(outs, regl.reg_ptrs_x3, ref, reg, M, L, DIMS, pcr)),
+        'heads_depth_x3 (cls + Sequential reg, one launch)': lambda: ops.heads_depth_x3(outs, plain.cls_ptrs_x3, plain.reg_ptrs_x3, ref, cls, reg, M, L, 2, pcr),
+        'heads_cls_depth_x3 (cls alone)': lambda: ops.heads_cls_depth_x3(outs, regl.cls_ptrs_x3, cls, M, L, 2),
+        'reg_layer_depth_x3 (RegLayer reg alone)': lambda: ops.reg_layer_depth_x3(outs, regl.reg_ptrs_x3, ref, reg, M, L, 2, DIMS, pcr),
+        'heads_cls_depth_x3 + reg_layer_depth_x3 (the pair)': lambda: (ops.heads_cls_depth_x3(outs, regl.cls_ptrs_x3, cls, M, L, 2),
+                                                                       ops.reg_layer_depth_x3(outs, regl.reg_ptrs_x3, ref, reg, M, L, 2, DIMS, pcr)),
     }
     graphs = {k: graph_of(fn) for k, fn in variants.items()}
     times = {k: [] for k in variants}
