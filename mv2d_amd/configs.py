@@ -138,8 +138,19 @@ def _set_num_reg_fcs(d, num_reg_fcs):
     return d
 
 
+def _set_decoder_shape(d, num_layers, feedforward_channels):
+    # ``bbox_head.transformer.decoder.num_layers`` and ``...transformerlayers.feedforward_channels`` (ops.check_decoder_shape lists what is accepted).
+    # The shipped configs set 6 and 2048: the defaults here give exactly that dict
+    from . import ops
+    num_layers, feedforward_channels = ops.check_decoder_shape(num_layers, feedforward_channels, 'configs')
+    dec = d['bbox_head']['transformer']['decoder']
+    dec['num_layers'] = num_layers
+    dec['transformerlayers']['feedforward_channels'] = feedforward_channels
+    return d
+
+
 def roi_head_cfg_s(num_classes=10, roi_size=ROI_SIZE, reg_layer_dims=None, depth_num=64, depth_start=1, position_range=None, query_generator=None,
-                   num_reg_fcs=2, with_fpe=True, no_sin_enc=False, adapt_pos3d=True, LID=True):
+                   num_reg_fcs=2, with_fpe=True, no_sin_enc=False, adapt_pos3d=True, LID=True, num_layers=6, feedforward_channels=2048):
     """CFG-S:40-121 (MV2D-S single frame); ``num_classes`` sets ``bbox_head.num_classes`` and ``bbox_head.bbox_coder.num_classes``,
     ``roi_size`` sets ``bbox_roi_extractor.roi_layer.output_size`` and ``query_generator.roi_feat_size``; ``reg_layer_dims`` (a tuple of
     group widths) sets ``bbox_head.use_reg_layer=True`` with that ``group_reg_dims``; ``depth_num`` (a multiple of 8 in [8, 80]), ``depth_start``
@@ -147,23 +158,26 @@ def roi_head_cfg_s(num_classes=10, roi_size=ROI_SIZE, reg_layer_dims=None, depth
     QueryGenerator's own keys: mv2d_amd/qg_shape.py lists the accepted values) is laid over the ``query_generator`` subtree; ``num_reg_fcs`` (1, 2
     or 3) sets ``bbox_head.num_reg_fcs``, alone or together with ``reg_layer_dims`` (2, the head's default: no key); ``with_fpe``, ``no_sin_enc``,
     ``adapt_pos3d`` and ``LID`` set the ``pe`` keys of the same names (a key left at the shipped value is not added; ``adapt_pos3d=False`` needs
-    ``no_sin_enc=True``)."""
+    ``no_sin_enc=True``); ``num_layers`` (1 to 8) and ``feedforward_channels`` (a multiple of 64 in [64, 4096]) set
+    ``bbox_head.transformer.decoder.num_layers`` and ``...transformerlayers.feedforward_channels``."""
     d = dict(type='MV2DSHead', use_denoise=False)
     d.update(_common(with_cp=False))
     d['box_correlation'] = dict(correlation_mode='topk_matched:1:0.0:0.0')
     d = _set_query_generator(_set_pe_options(_set_pe_depth(d, depth_num, depth_start, position_range), with_fpe, no_sin_enc, adapt_pos3d, LID), query_generator)
+    d = _set_decoder_shape(d, num_layers, feedforward_channels)
     return copy.deepcopy(_set_num_reg_fcs(_set_reg_layer(_set_roi_size(_set_num_classes(d, num_classes), roi_size), reg_layer_dims), num_reg_fcs))
 
 
 def roi_head_cfg_t(num_classes=10, roi_size=ROI_SIZE, reg_layer_dims=None, depth_num=64, depth_start=1, position_range=None, query_generator=None,
-                   num_reg_fcs=2, with_fpe=True, no_sin_enc=False, adapt_pos3d=True, LID=True):
+                   num_reg_fcs=2, with_fpe=True, no_sin_enc=False, adapt_pos3d=True, LID=True, num_layers=6, feedforward_channels=2048):
     """CFG-T:40-125 (MV2D-T two frames); ``num_classes``, ``roi_size``, ``reg_layer_dims``, the three ``pe`` keys, ``query_generator``, ``num_reg_fcs``
-    and the PE's four switches as in ``roi_head_cfg_s``."""
+    the PE's four switches and the decoder's ``num_layers`` / ``feedforward_channels`` as in ``roi_head_cfg_s``."""
     d = dict(type='MV2DTHead', use_denoise=True, neg_bbox_loss=True,
              denoise_noise_scale=1.25, denoise_split=0.6)
     d.update(_common(with_cp=True))
     d['box_correlation'] = dict(expand_stride=2, correlation_mode='topk_matched:20:0.0:0.0')
     d = _set_query_generator(_set_pe_options(_set_pe_depth(d, depth_num, depth_start, position_range), with_fpe, no_sin_enc, adapt_pos3d, LID), query_generator)
+    d = _set_decoder_shape(d, num_layers, feedforward_channels)
     return copy.deepcopy(_set_num_reg_fcs(_set_reg_layer(_set_roi_size(_set_num_classes(d, num_classes), roi_size), reg_layer_dims), num_reg_fcs))
 
 

@@ -36,11 +36,19 @@ __device__ __forceinline__ void split2(float a, float b, unsigned int& hi, unsig
 // the 512 two-per-CU slots, i.e. two rounds (49.8 us); 400 blocks of 48 rows run in one (42.8 us; 2400 rows: 31.0 -> 27.8; 320 rows: 17.3 -> 22.3, so
 // small launches keep 32).  A row's arithmetic does not depend on RTB (ONE accumulator per output tile, slices and products in a fixed order), so
 // the choice by row count keeps "a sample's result does not depend on its batch" bit for bit.
-template <int G, int RTB>
+//
+// RAGGED (G = 8 only): hidden/64 is no multiple of 8 and the LAST slab's block accumulates the remaining hidden/64 - 8 slab slices (1 to 7); every other
+// block, and every block of a launch whose width is a multiple of 512, runs the full eight.  The count `ng` is block-uniform (a function of blockIdx.x
+// and hidden alone) and the loop leaves IN FRONT of an iteration's loads and barriers, so no wave waits at a barrier another one skipped, and no weight
+// fragment or bias of a slice at or past hidden/64 is addressed: neither the W2 loads at the top of an iteration nor the W1 prefetch of slice + 1.
+// The slices a block does run keep their order, their H buffer (g & 1) and their one accumulator, so a ragged slab equals the slab of the same
+// weights zero-padded to eight slices value for value (a zero slice adds exact zeros), at every row count.
+template <int G, int RTB, bool RAGGED = false>
 __global__ __launch_bounds__(256, 2) void ffn_x3_kernel(const float* __restrict__ X, const unsigned short* __restrict__ W1h,
                                                         const unsigned short* __restrict__ W1l, const float* __restrict__ b1,
                                                         const unsigned short* __restrict__ W2h, const unsigned short* __restrict__ W2l,
                                                         float* __restrict__ slabs, int M, int hidden) {
+    static_assert(!RAGGED || G == 8, "the ragged form exists for the engine's eight slices per block only");
     constexpr int BR = 16 * RTB, NXR = BR / 8;           // rows per block, X staging rounds
     constexpr int NHB = G > 1 ? 2 : 1;                   // H buffers (they alternate between the slices of a block)
     __shared__ __attribute__((aligned(16))) unsigned char xh[BR * C * 2], xl[BR * C * 2], hh[NHB][BR * HS * 2], hl[NHB][BR * HS * 2];
@@ -49,6 +57,7 @@ __global__ __launch_bounds__(256, 2) void ffn_x3_kernel(const float* __restrict_
     //  of linear_x3 / heads -- all slabs of a row block on one XCD -- fetched 71 instead of 29 MB per launch here, round 4)
     const int slab = blockIdx.x, m0 = blockIdx.y * BR;
     const int nt = hidden / 16;
+    const int ng = RAGGED ? min(G, hidden / HS - slab * G) : G;      // slices of this block (>= 1: the grid has ceil(hidden / 64 / G) slabs)
     // ---- issue everything that does not depend on LDS: X rows (coalesced), W1 fragments (hi, lo) of the first slice
     float4 xr[NXR][2];
 #pragma unroll
@@ -92,6 +101,7 @@ __global__ __launch_bounds__(256, 2) void ffn_x3_kernel(const float* __restrict_
             for (int t = 0; t < 4; ++t) acc[n][r][t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int g = 0; g < G; ++g) {
+        if (RAGGED && g >= ng) break;                    // block-uniform, in front of this iteration's loads and barriers
         const int slice = slab * G + g;
         unsigned char* hhg = hh[g & (NHB - 1)];
         unsigned char* hlg = hl[g & (NHB - 1)];
@@ -123,7 +133,7 @@ __global__ __launch_bounds__(256, 2) void ffn_x3_kernel(const float* __restrict_
                 h1[r] = mfma_q16_16x16x32(w1l[s].v, ah.v, h1[r], 0, 0, 0);
             }
         }
-        if (g + 1 < G) load_w1(slice + 1);               // the next slice's W1: in flight during the epilogue and phase 2
+        if (g + 1 < G && (!RAGGED || g + 1 < ng)) load_w1(slice + 1);               // the next slice's W1: in flight during the epilogue and phase 2
         {
             const int col = wave * 16 + 4 * fg;                                         // first of 4 hidden columns (local to the slice)
             const float4 bb = *reinterpret_cast<const float4*>(b1 + slice * HS + col);
@@ -190,11 +200,21 @@ extern "C" int mv2d_ffn_fused_x3(const float* X, const void* W1hi, const void* W
                        ((uintptr_t)W2lo & 15) == 0 && ((uintptr_t)slabs & 15) == 0 && ((uintptr_t)b1 & 15) == 0,
                    "mv2d_ffn_fused_x3: operands must be 16-byte aligned");
     const int G = slices_per_block;
-    MV2D_CHECK_ARG((G == 1 || G == 2 || G == 4 || G == 8) && (hidden / HS) % G == 0, "mv2d_ffn_fused_x3: slices_per_block must be 1, 2, 4 or 8 and divide hidden/64");
+    const int ns = hidden / HS;
+    // eight slices per block take any width: a last slab of ns % 8 slices runs the RAGGED instance
+    MV2D_CHECK_ARG(G == 1 || G == 2 || G == 4 || G == 8, "mv2d_ffn_fused_x3: slices_per_block must be 1, 2, 4 or 8");
+    MV2D_CHECK_ARG(G == 8 || ns % G == 0, "mv2d_ffn_fused_x3: slices_per_block 1, 2 and 4 must divide hidden/64");
     if (M == 0) return MV2D_OK;
     const unsigned short *w1h = (const unsigned short*)W1hi, *w1l = (const unsigned short*)W1lo, *w2h = (const unsigned short*)W2hi, *w2l = (const unsigned short*)W2lo;
     const int rtb = M > 1024 ? 3 : 2;
-    const dim3 grid(hidden / HS / G, cdiv(M, 16 * rtb));
+    const dim3 grid(cdiv(ns, G), cdiv(M, 16 * rtb));
+#define MV2D_FFN_RAGGED(R_) hipLaunchKernelGGL((ffn_x3_kernel<8, R_, true>), grid, dim3(256), 0, (hipStream_t)stream, X, w1h, w1l, b1, w2h, w2l, slabs, M, hidden)
+    if (ns % G != 0) {                                   // G == 8 (checked above): a width that is a multiple of 512 never comes here
+        if (rtb == 3) MV2D_FFN_RAGGED(3); else MV2D_FFN_RAGGED(2);
+        MV2D_LAUNCH_CHECK();
+        return MV2D_OK;
+    }
+#undef MV2D_FFN_RAGGED
 #define MV2D_FFN(G_, R_) hipLaunchKernelGGL((ffn_x3_kernel<G_, R_>), grid, dim3(256), 0, (hipStream_t)stream, X, w1h, w1l, b1, w2h, w2l, slabs, M, hidden)
     if (rtb == 3) { if (G == 1) MV2D_FFN(1, 3); else if (G == 2) MV2D_FFN(2, 3); else if (G == 4) MV2D_FFN(4, 3); else MV2D_FFN(8, 3); }
     else { if (G == 1) MV2D_FFN(1, 2); else if (G == 2) MV2D_FFN(2, 2); else if (G == 4) MV2D_FFN(4, 2); else MV2D_FFN(8, 2); }

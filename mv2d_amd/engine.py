@@ -50,11 +50,16 @@ class HeadEngine:
                  post_range=(-61.2, -61.2, -10.0, 61.2, 61.2, 10.0), depth_num=64, stride=16, col_cap_per_query=2048,
                  iou_thr=0.0, ratio=0.0, masked_row='nan', exact=None, num_classes=10, roi_size=7, use_reg_layer=False,
                  group_reg_dims=(2, 2, 1, 1, 2, 2), depth_start=1, position_range=None, query_generator=None, num_reg_fcs=2,
-                 with_fpe=True, no_sin_enc=False, adapt_pos3d=True, LID=True):
+                 with_fpe=True, no_sin_enc=False, adapt_pos3d=True, LID=True, feedforward_channels=2048):
         assert kind in ('S', 'T')
         self.kind = kind
         self.dev = torch.device(device)
-        self.L = num_layers
+        # the decoder's shape (ops.check_decoder_shape: 1 to 8 layers, an FFN width that is a multiple of 64 in [64, 4096]).  Fixed per engine: the
+        # state dict has to agree (load_state).  The FFN always accumulates ops.FFN_GROUPS = 8 hidden slices per block, so a width gives
+        # ceil(F / 512) slabs -- exactly what the workspaces allocate and the FFN tail sums; a width that is no multiple of 512 launches the ragged
+        # instance of the FFN kernel (csrc/ffn_x3.hip), the shipped 2048 allocates, packs and launches what it always did.
+        self.L, self.ffn_dim = ops.check_decoder_shape(num_layers, feedforward_channels, 'HeadEngine')
+        self.ffn_slabs = ops.ffn_slabs(self.ffn_dim)
         self.num_views = num_views
         self.topk = topk if topk is not None else (1 if kind == 'S' else 20)
         self.expand = float(expand_stride if expand_stride is not None else (0 if kind == 'S' else 2))
@@ -124,6 +129,7 @@ class HeadEngine:
     # ------------------------------------------------------------------------------------------ weights
     def load_state(self, sd):
         d, L, nf = self.dev, self.L, self.num_reg_fcs
+        self.check_decoder_shape(sd, L, self.ffn_dim)
         self.check_reg_layout(sd, self.use_reg_layer, self.group_reg_dims)
         self.check_branch_depth(sd, nf, self.use_reg_layer)
         self.check_pe_layout(sd, self.with_fpe, self.no_sin_enc)
@@ -279,6 +285,22 @@ class HeadEngine:
             w['qg_c_wx'] = ops.pack_x3(padded(w['qg_c_w'], 16))
             w['qg_c_b16'] = torch.zeros(16, device=d, dtype=F32)
             w['qg_c_b16'][:3] = w['qg_c_b']
+
+    @staticmethod
+    def check_decoder_shape(sd, num_layers, feedforward_channels):
+        """ValueError naming the key unless the state dict holds exactly ``num_layers`` ``bbox_head.transformer.decoder.layers.{i}`` and every
+        layer's FFN is ``feedforward_channels`` wide (``ffns.0.layers.0.0.weight`` [F, 256], ``ffns.0.layers.1.weight`` [256, F])."""
+        dec = 'bbox_head.transformer.decoder.layers.'
+        have = sorted({int(k[len(dec):].split('.')[0]) for k in sd if k.startswith(dec)})
+        if have != list(range(num_layers)):
+            raise ValueError(f'HeadEngine: num_layers={num_layers}, the state dict holds {len(have)} decoder layers ({dec}{{i}}, i in {have})')
+        F = feedforward_channels
+        for i in range(num_layers):
+            for name, want in (('ffns.0.layers.0.0.weight', (F, C)), ('ffns.0.layers.1.weight', (C, F))):
+                k = f'{dec}{i}.{name}'
+                if k not in sd or tuple(sd[k].shape) != want:
+                    got = tuple(sd[k].shape) if k in sd else 'missing'
+                    raise ValueError(f'HeadEngine: feedforward_channels={F} expects {k} to be {want}, the state dict has {got}')
 
     @staticmethod
     def check_reg_layout(sd, use_reg_layer, group_reg_dims):
@@ -528,7 +550,7 @@ class HeadEngine:
             ws[n] = e((R, C))
         ws['zero_rows'] = z((R, C))                              # never written
         ws['sa0_ctx'] = e((R, C))                                # rows of the layer-0 self-attention value bias (fold_sa0), filled per weights version
-        ws['qkv'] = e((R, 3 * C)); ws['parts'] = e((2048 // 64, R, C)); ws['outs'] = e((L, R, C))
+        ws['qkv'] = e((R, 3 * C)); ws['parts'] = e((self.ffn_slabs, R, C)); ws['outs'] = e((L, R, C))
         ws['cls'] = e((L, R, self.num_classes)); ws['reg'] = e((L, R, 10))
         ws['boxes'] = z((B, self.max_num, 9)); ws['scores'] = z((B, self.max_num))
         ws['labels'] = z((B, self.max_num), torch.int64); ws['bbox_index'] = z((B, self.max_num), torch.int64); ws['count'] = z(B, torch.int32)
@@ -1032,11 +1054,12 @@ class HeadEngine:
                     tile_attn(i)
                     o.xattn_ctxmap(ws['zh'], mapB, bv, ws['row_ptr'], ws['ctx'], R, empty_nan=self.empty_nan)
                 o.attn_out_fused_x3(ws['ctx'], *out_args, M=R)
-            # eight hidden slices accumulated per block: 4 slabs to write and re-read instead of 32 (round 3: 8371 vs 8289 samples/s for
-            # 8 vs 4 slices, and half the slab traffic).  It fixes the summation order, so it is NOT chosen by the row count: a sample's
-            # result must not depend on the batch it is in.
-            G = 8
-            parts = ws['parts'][:ws['parts'].shape[0] // G]
+            # eight hidden slices accumulated per block: 4 slabs to write and re-read instead of 32 at the shipped width (round 3: 8371 vs 8289
+            # samples/s for 8 vs 4 slices, and half the slab traffic).  It fixes the summation order, so it is NOT chosen by the row count or the
+            # width: a sample's result must not depend on the batch it is in.  ws['parts'] holds exactly the ceil(F / 512) slabs the kernel writes
+            # (ops.ffn_fused_x3 checks it), and the tail sums exactly those.
+            G = ops.FFN_GROUPS
+            parts = ws['parts']
             o.ffn_fused_x3(ws['x2'], W_[f'ffn_w1x{i}'], W_[f'ffn_b1{i}'], W_[f'ffn_w2x{i}'], parts, R, groups=G)
             nxt = i + 1 < L
             o.ffn_out_fused_x3(parts, W_[f'ffn_b2{i}'], ws['x2'], (W_[f'ln2_w{i}'], W_[f'ln2_b{i}']), (W_['post_w'], W_['post_b']),
@@ -1249,7 +1272,7 @@ class HeadEngine:
                    row_ptr=torch.cat([torch.arange(pad, device=d, dtype=torch.int32) * nk, row_ptr + pad * nk]),
                    col_idx=torch.cat([keys.repeat(pad), col]).contiguous(),
                    ref=torch.cat([dn_ref.to(F32), ws['ref'][:R]]).contiguous(), qpos=torch.cat([qdn, ws['qpos'][:R]]).contiguous(),
-                   zero_rows=torch.zeros(T, C, device=d), qkv=e(T, 3 * C), parts=e(2048 // 64, T, C), outs=e(L, T, C), cls=e(L, T, self.num_classes),
+                   zero_rows=torch.zeros(T, C, device=d), qkv=e(T, 3 * C), parts=e(self.ffn_slabs, T, C), outs=e(L, T, C), cls=e(L, T, self.num_classes),
                    reg=e(L, T, 10), dt_rows=torch.cat([torch.zeros(pad, device=d), torch.full((R,), float(out.get('dt', 0.0)), device=d)]))
         for n in ('x', 'x1', 'x2', 'ctx', 'q'):
             tws[n] = e(T, C)

@@ -417,6 +417,29 @@ def check_num_reg_fcs(v, who):
     return int(v)
 
 
+FFN_GROUPS = 8           # hidden slices of 64 the engine's fused FFN accumulates per block (it fixes the summation order: never chosen per launch)
+DECODER_LAYERS_MAX = 8   # the bound of the training entries (csrc/train_decoder.hip)
+FFN_CHANNELS_MAX = 4096  # 8 slabs of 512
+
+
+def check_decoder_shape(num_layers, feedforward_channels, who):
+    """``bbox_head.transformer.decoder.num_layers`` and ``...transformerlayers.feedforward_channels`` as ints, the one accepted set: num_layers in
+    [1, 8] (the bound of the training entries), feedforward_channels a multiple of 64 in [64, 4096] (the fused FFN's hidden slice; at most 8 slabs).
+    bools, floats and strings are refused, not converted.  Returns (num_layers, feedforward_channels)."""
+    v = num_layers
+    if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not 1 <= int(v) <= DECODER_LAYERS_MAX:
+        raise ValueError(f'{who}: num_layers must be an int in [1, {DECODER_LAYERS_MAX}] (decoder layers), got {v!r}')
+    f = feedforward_channels
+    if isinstance(f, bool) or not isinstance(f, numbers.Integral) or not 64 <= int(f) <= FFN_CHANNELS_MAX or int(f) % 64:
+        raise ValueError(f'{who}: feedforward_channels must be an int, a multiple of 64 in [64, {FFN_CHANNELS_MAX}], got {f!r}')
+    return int(v), int(f)
+
+
+def ffn_slabs(hidden, groups=FFN_GROUPS):
+    """Slabs ffn_fused_x3 writes for a hidden width: ceil(hidden / 64 / groups)."""
+    return -(-(int(hidden) // 64) // int(groups))
+
+
 def _pack_x3_depth(W):
     """fp32 [L,n,256,256] -> (hi, lo), each [L, n * 65536]: pack_x3 of every matrix, stacked layer-major"""
     L, n = W.shape[0], W.shape[1]
@@ -499,15 +522,20 @@ def ffn_fused(x, W1, b1, W2, slabs=None, M=None):
 
 
 def ffn_fused_x3(x, W1hl, b1, W2hl, slabs=None, M=None, groups=1):
-    """ffn_fused in bf16x3 split precision; W1hl / W2hl = pack_x3(W1) / pack_x3(W2).  groups (1, 2, 4) consecutive hidden slices are
-    accumulated per block: hidden/64/groups slabs come out."""
+    """ffn_fused in bf16x3 split precision; W1hl / W2hl = pack_x3(W1) / pack_x3(W2).  groups (1, 2, 4, 8) consecutive hidden slices are
+    accumulated per block: ceil(hidden/64/groups) slabs come out.  groups 1, 2 and 4 must divide hidden/64; groups=8 takes any hidden that is a
+    multiple of 64 (the last slab then holds the remaining hidden/64 % 8 slices).  ``slabs``, when given, has exactly that many slabs."""
     _req(x, torch.float32, 'x'); _req(b1, torch.float32, 'b1')
     for t in (*W1hl, *W2hl):
         _req(t, q16_dtype(), 'W')
     M = x.shape[0] if M is None else M
     hidden = W1hl[0].numel() // 256                  # packed (fragment-major) copies are flat
+    n_slabs = ffn_slabs(hidden, groups)
     if slabs is None:
-        slabs = torch.empty((hidden // 64 // groups, M, 256), device=x.device, dtype=torch.float32)
+        slabs = torch.empty((n_slabs, M, 256), device=x.device, dtype=torch.float32)
+    elif slabs.shape[0] != n_slabs or (M > 0 and slabs.stride(0) != M * 256):
+        # (the kernel writes slab s at s * M * 256: exactly the slabs it writes, M rows each)
+        raise ValueError(f'ffn_fused_x3: slabs must be [{n_slabs}, {M}, 256] for hidden={hidden}, groups={groups}, got {tuple(slabs.shape)}')
     check(_lib.load().mv2d_ffn_fused_x3(_p(x), _p(W1hl[0]), _p(W1hl[1]), _p(b1), _p(W2hl[0]), _p(W2hl[1]), _p(slabs), M, hidden, groups,
                                         _stream()), 'mv2d_ffn_fused_x3')
     return slabs

@@ -245,6 +245,10 @@ class MV2DHead(nn.Module):
         self.box_corr_module = BoxCorrelation(**box_correlation)
         self.pc_range, self.intrins_feat_scale, self.feat_lvl, self.force_fp32 = pc_range, intrins_feat_scale, feat_lvl, force_fp32
         self.stage_loss_weights = train_cfg.get('stage_loss_weights') if train_cfg else None
+        # one weight per decoder layer (the reference indexes the list per layer and would raise IndexError in its first loss, mv2d_head.py:243)
+        if self.stage_loss_weights is not None and len(self.stage_loss_weights) < self.bbox_head.num_pred:
+            raise ValueError(f'MV2DHead: train_cfg.stage_loss_weights has {len(self.stage_loss_weights)} entries, '
+                             f'bbox_head.transformer.decoder.num_layers = {self.bbox_head.num_pred}')
         self._engine, self._engine_ver = None, None
 
     with_bbox = True
@@ -258,6 +262,17 @@ class MV2DHead(nn.Module):
         return self.bbox_head.num_classes
 
     # ---- engine plumbing ------------------------------------------------------------------------------
+    def decoder_shape(self):
+        """(num_layers, feedforward_channels) of the built decoder (ops.check_decoder_shape: the accepted values), the width read off the layers'
+        own FFN modules; ValueError if the layers disagree with each other or with ``num_layers``."""
+        layers = self.bbox_head.transformer.decoder.layers
+        widths = [int(l.ffns[0].layers[0][0].out_features) for l in layers]
+        if len(set(widths)) != 1:
+            raise ValueError(f'MV2DHead: the decoder layers\' feedforward_channels disagree ({widths}); the engine runs one width in every layer')
+        if len(layers) != self.bbox_head.num_pred:
+            raise ValueError(f'MV2DHead: the decoder has {len(layers)} layers, bbox_head.transformer.decoder.num_layers = {self.bbox_head.num_pred}')
+        return ops.check_decoder_shape(len(layers), widths[0], 'MV2DHead')
+
     def _engine_num_views(self, img_metas):
         return len(img_metas)
 
@@ -274,8 +289,9 @@ class MV2DHead(nn.Module):
             sd = {k: v for k, v in self.state_dict().items()}
             bc = self.box_corr_module
             coder = self.bbox_head.bbox_coder
+            num_layers, ffn_channels = self.decoder_shape()
             self._engine = HeadEngine(sd, self.KIND, device, num_views=self._engine_num_views(img_metas), topk=bc.topk,
-                                      expand_stride=bc.expand_stride, num_layers=self.bbox_head.num_pred, max_num=coder.max_num,
+                                      expand_stride=bc.expand_stride, num_layers=num_layers, feedforward_channels=ffn_channels, max_num=coder.max_num,
                                       pc_range=tuple(self.pc_range), post_range=tuple(coder.post_center_range),
                                       depth_num=self.position_encoding.depth_num, depth_start=self.position_encoding.depth_start,
                                       position_range=tuple(self.position_encoding.position_range),

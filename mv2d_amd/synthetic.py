@@ -305,6 +305,75 @@ def with_qg_shape_state(sd, seed=0, query_generator=None, roi_size=7):
     return out
 
 
+def with_decoder_shape_state(sd, seed=0, num_layers=NUM_LAYERS, feedforward_channels=FFN_DIM):
+    """A copy of a head state dict for a decoder of ``num_layers`` layers with ``feedforward_channels``-wide FFNs (ops.check_decoder_shape): the
+    layer list ``bbox_head.transformer.decoder.layers.{i}`` and the per-layer prediction branches ``bbox_head.{cls,reg}_branches.{i}`` are cut to the
+    first ``num_layers`` or extended (a new layer and its branches get tensors of layer 0's names and shapes), and at a width other than the
+    input's every layer's four FFN tensors are redrawn.  Its own stream of draws: make_head_state is untouched, every tensor that is kept is the
+    input's bit for bit, and at the input's own shape the copy equals the input."""
+    from . import ops
+    n, F = ops.check_decoder_shape(num_layers, feedforward_channels, 'with_decoder_shape_state')
+    g = _rng(seed + 32452843)
+    C = EMBED
+    dec = 'bbox_head.transformer.decoder.layers.'
+    heads = ('bbox_head.cls_branches.', 'bbox_head.reg_branches.')
+    old_n = len({k[len(dec):].split('.')[0] for k in sd if k.startswith(dec)})
+    old_F = int(sd[dec + '0.ffns.0.layers.0.0.weight'].shape[0])
+    ffn = ('ffns.0.layers.0.0.weight', 'ffns.0.layers.0.0.bias', 'ffns.0.layers.1.weight', 'ffns.0.layers.1.bias')
+
+    def draw_ffn(p):
+        return {p + ffn[0]: _xavier(g, (F, C)), p + ffn[1]: _bias(g, F), p + ffn[2]: _xavier(g, (C, F)), p + ffn[3]: _bias(g, C)}
+
+    def draw_like(name, like, out_bias=False):
+        # a tensor of layer 0's shape: matrices Xavier, LayerNorm weights around 1 (a 1-d ``weight``), biases small; the class output layer's bias
+        # as make_head_state draws it
+        if like.ndim > 1:
+            return _xavier(g, like.shape)
+        if name.endswith('.weight'):
+            return (0.8 + 0.4 * g.random(like.shape[0], dtype=np.float32)).astype(np.float32)
+        if out_bias:
+            return np.full(like.shape[0], -math.log((1 - 0.01) / 0.01), np.float32) + _bias(g, like.shape[0], 0.5)
+        return _bias(g, like.shape[0])
+
+    layers = OrderedDict()
+    for l in range(n):
+        p = f'{dec}{l}.'
+        if l < old_n:
+            for k, v in sd.items():
+                if k.startswith(p):
+                    layers[k] = v
+            if F != old_F:
+                layers.update(draw_ffn(p))
+        else:
+            for k, v in sd.items():
+                if k.startswith(dec + '0.'):
+                    name = p + k[len(dec) + 2:]
+                    layers[name] = None if name[len(p):] in ffn else draw_like(name, v)
+            layers.update(draw_ffn(p))
+    branches = {h: OrderedDict() for h in heads}
+    for h in heads:
+        # (the class branch is a Sequential: its output layer has the highest index)
+        last = max(int(k[len(h):].split('.')[1]) for k in sd if k.startswith(h + '0.')) if h == heads[0] else -1
+        for l in range(n):
+            for k, v in sd.items():
+                if l < old_n and k.startswith(f'{h}{l}.'):
+                    branches[h][k] = v
+                elif l >= old_n and k.startswith(h + '0.'):
+                    name = f'{h}{l}.' + k[len(h) + 2:]
+                    branches[h][name] = draw_like(name, v, out_bias=h == heads[0] and k == f'{h}0.{last}.bias')
+    out, placed = OrderedDict(), set()
+    for k, v in sd.items():
+        for prefix, new in ((dec, layers), (heads[0], branches[heads[0]]), (heads[1], branches[heads[1]])):
+            if k.startswith(prefix):
+                if prefix not in placed:
+                    out.update(new)
+                    placed.add(prefix)
+                break
+        else:
+            out[k] = v
+    return out
+
+
 WORKLOADS = {
     # name: (head kind, views/frame, frames, img_h, img_w, pad_w, boxes/view)
     'micro_t': ('T', 2, 1, 128, 192, None, 6),

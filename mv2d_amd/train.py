@@ -125,6 +125,8 @@ class HeadLoss:
         cache = self.__dict__.setdefault('_lw', {})
         if key not in cache:
             w = self.stage_loss_weights or [1.0] * L
+            if len(w) < L:
+                raise ValueError(f'HeadLoss: train_cfg.stage_loss_weights has {len(w)} entries for {L} decoder layers')
             cache[key] = torch.tensor([float(x) * scale for x in w[:L]], dtype=torch.float32, device=self.device)
         return cache[key]
 
