@@ -167,6 +167,30 @@ int mv2d_pe_gate_x3(const float* Q, const void* Xmap, const int* row_index, cons
                     const void* Wr_hi, const void* Wr_lo, const float* br, const void* We_hi, const void* We_lo, const float* be,
                     const float* sine_tab, int tab_period, float* pe, void* Xk_hi, void* Xk_lo, void* Xv_hi, void* Xv_lo, int pe_at_index,
                     int map_fmt, void* stream);
+/* THE VIEW FILTER of the split-precision PE kernels (two-frame head, route option pe_cache_views; csrc/pe_x3_sel.h).  Row m lies at map position
+ * pos = row_index[m] (m without a row_index) in view (pos % tab_period) / hw of its sample: tab_period = views * hw, at most 32 views, hw = cells of one
+ * view's map.  view_mask: ONE 32-bit word in DEVICE memory, read by the kernel, so that a captured graph does not depend on its value.  take_set != 0:
+ * the launch writes only the rows whose view bit is set; take_set == 0: only the rows whose bit is clear.  A block none of whose 64 rows is taken
+ * returns at once, a mixed tile is computed whole and its stores are masked per row: any row order is correct, a list sorted by position makes the
+ * skip effective.  Rows that are not taken keep what they held.  A missing mask, hw <= 0, tab_period % hw != 0 or more than 32 views is an argument
+ * error naming the entry.
+ *
+ * mv2d_pe_gate_rows_x3: the gate of mv2d_pe_gate_x3 on the cached table Q with the KEY / VALUE ROW outputs of mv2d_pe_fused_x3_k: Xk = pe + feature
+ * row, Xv = feature row, hi rows key16 [M,256], lo rows key16 (lo_fmt 0) or e4m3 bytes (lo_fmt 1, lo8_flag as above), written at row m.  Every row it
+ * writes is bit for bit the row mv2d_pe_fused_x3_k writes on the frustum rows Q was built from (same exception: a Q value of -0.0f was stored as
+ * +0.0f).  The four row outputs are required, pe [M,256] (row m) is optional.  One instance per map format, none per depth. */
+int mv2d_pe_gate_rows_x3(const float* Q, const void* Xmap, const int* row_index, const int* m_dev, int M,
+                         const void* Wr_hi, const void* Wr_lo, const float* br, const void* We_hi, const void* We_lo, const float* be,
+                         const float* sine_tab, int tab_period, float* pe, void* Xk_hi, void* Xk_lo, void* Xv_hi, void* Xv_lo, int lo_fmt,
+                         int* lo8_flag, int map_fmt, const unsigned* view_mask, int hw, int take_set, void* stream);
+/* mv2d_pe_fused_x3_k with the view filter: the same schedule and arithmetic per Kp / 32 in 1 .. 8 and map format (kernel instances of their own; the
+ * unfiltered entry keeps its kernels), rows that are not taken are not written.  The four row outputs are required, pe (row m) is optional.  The
+ * frustum rows A1 of rows that are not taken are read but never used (they may hold anything: mv2d_pe_frustum_f32_sel leaves them unwritten). */
+int mv2d_pe_fused_x3_k_sel(const float* A1, const void* Xmap, const int* row_index, const int* m_dev, int M,
+                           const void* W1a_hi, const void* W1a_lo, const float* b1a, const void* W1b_hi, const void* W1b_lo, const float* b1b,
+                           const void* Wr_hi, const void* Wr_lo, const float* br, const void* We_hi, const void* We_lo, const float* be,
+                           const float* sine_tab, int tab_period, float* pe, void* Xk_hi, void* Xk_lo, void* Xv_hi, void* Xv_lo, int lo_fmt,
+                           int* lo8_flag, int map_fmt, int Kp, const unsigned* view_mask, int hw, int take_set, void* stream);
 /* The same block on the second shape of the kernel (round 6, csrc/pe_x3b.hip): a wave owns 16 rows through both layers of each MLP, the hidden layer
  * stays in registers (no LDS image, no barrier between the layers), the weights go through a 4-deep LDS ring (LDS-DMA) shared by the 8 waves of a 128-row
  * block, two waves per SIMD.  Same operands EXCEPT that W1a and Wr (the first layers) are packed from the weight with its rows in the order
@@ -628,6 +652,11 @@ int mv2d_pe_frustum_f32(const int* s2pos, const int* S_dev, int S_max, const dou
  * 3 * depth_num .. ld - 1 of every row it writes (no zeroed buffer needed).  mv2d_pe_frustum_f32 is this entry with ld = 3 * depth_num. */
 int mv2d_pe_frustum_f32_ld(const int* s2pos, const int* S_dev, int S_max, const double* img2lidar, const double* coords_w, const double* coords_h,
                            const double* coords_d, float* out, int V, int h, int w, int depth_num, const double* position_range, int ld, void* stream);
+/* mv2d_pe_frustum_f32_ld with the view filter of mv2d_pe_gate_rows_x3 (hw = h * w): rows of the views whose bit of *view_mask is SET are neither
+ * computed nor written (the gate-only launch reads a cached table for them); the other rows are those of mv2d_pe_frustum_f32_ld. */
+int mv2d_pe_frustum_f32_sel(const int* s2pos, const int* S_dev, int S_max, const double* img2lidar, const double* coords_w, const double* coords_h,
+                            const double* coords_d, float* out, int V, int h, int w, int depth_num, const double* position_range, int ld,
+                            const unsigned* view_mask, int tab_period, void* stream);
 
 /* PE inputs at the listed key positions only (MU/pe.py:84-135 frustum, MU/positional_encoding.py:78-95 sine) + feature gather.
  * out: A_frustum [S,3*D] key16, A_sine [S,384] key16, Xf_k16 [S,256] key16, Xf_f32 [S,256] (optional: NULL when mv2d_pe_fused_tab reads the map).

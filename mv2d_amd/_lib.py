@@ -45,6 +45,8 @@ SIGNATURES = {
     'mv2d_pe_fused_x3_k': (I, [P, P, P, P, I] + [P] * 13 + [I] + [P] * 5 + [I, I, P, I, I, P]),
     'mv2d_pe_fused_x3_ng': (I, [P, P, P, P, I] + [P] * 7 + [I] + [P] * 5 + [I, I, P, I, I, P]),
     'mv2d_pe_gate_x3': (I, [P, P, P, P, I] + [P] * 7 + [I] + [P] * 5 + [I, I, P]),
+    'mv2d_pe_gate_rows_x3': (I, [P, P, P, P, I] + [P] * 7 + [I] + [P] * 5 + [I, P, I, P, I, I, P]),
+    'mv2d_pe_fused_x3_k_sel': (I, [P, P, P, P, I] + [P] * 13 + [I] + [P] * 5 + [I, P, I, I, P, I, I, P]),
     'mv2d_pe_fused_x3b': (I, [P, P, P, P, I] + [P] * 13 + [I] + [P] * 5 + [I, I, P, P]),
     'mv2d_key16_format': (I, []),
     'mv2d_f32_to_key16': (I, [P, P, P, LL, P]),
@@ -133,6 +135,7 @@ SIGNATURES = {
     'mv2d_pe_inputs_fmt': (I, [P, P, I, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, P, I, P]),
     'mv2d_pe_frustum_f32': (I, [P, P, I, P, P, P, P, P, I, I, I, I, P, P]),
     'mv2d_pe_frustum_f32_ld': (I, [P, P, I, P, P, P, P, P, I, I, I, I, P, I, P]),
+    'mv2d_pe_frustum_f32_sel': (I, [P, P, I, P, P, P, P, P, I, I, I, I, P, I, P, I, P]),
     'mv2d_pe_inputs_ld': (I, [P, P, I, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, P, I, I, P]),
     'mv2d_result_pack': (I, [P, P, P, P, F, I, P, P, P, P, I, I, P]),
     'mv2d_nms_bev': (I, [P, P, P, P, F, P, I, I, P]),

@@ -966,6 +966,21 @@ __global__ __launch_bounds__(256) void pe_frustum_f32_ld_kernel(const int* __res
 #undef MV2D_FR_PITCHED
 }
 
+// the pitched rows of the views whose bit of *view_mask is CLEAR (route option pe_cache_views: the rows of the other views read a cached table instead)
+__global__ __launch_bounds__(256) void pe_frustum_f32_sel_kernel(const int* __restrict__ s2pos, const int* __restrict__ S_dev, const double* __restrict__ img2lidar,
+                                                             const double* __restrict__ coords_w, const double* __restrict__ coords_h,
+                                                             const double* __restrict__ coords_d, float* __restrict__ out, int h, int w, int D,
+                                                             double pr0, double pr1, double pr2, double ipd0, double ipd1, double ipd2, LogTab lt, int ld,
+                                                             const unsigned* __restrict__ view_mask, int tab_period) {
+#define MV2D_FR_LD ld
+#define MV2D_FR_PITCHED 1
+#define MV2D_FR_SEL 1
+#include "pe_frustum_body.inc"
+#undef MV2D_FR_LD
+#undef MV2D_FR_PITCHED
+#undef MV2D_FR_SEL
+}
+
 // ------------------------------------------------------------------------------------------------
 // a2 inputs: for every key position s of the compacted list build the three PE-MLP input rows and gather
 // the feature row (MU/pe.py:84-135 frustum coords in fp64, MU/positional_encoding.py:78-95 sine features).
@@ -1479,8 +1494,9 @@ extern "C" int mv2d_roi_positions_csr(const float* rois, const unsigned char* pa
 }
 
 // ld: row pitch of `out` in floats (>= 3 * depth_num); the columns 3 * depth_num .. ld - 1 of every written row are set to zero
-extern "C" int mv2d_pe_frustum_f32_ld(const int* s2pos, const int* S_dev, int S_max, const double* img2lidar, const double* coords_w, const double* coords_h,
-                                      const double* coords_d, float* out, int V, int h, int w, int depth_num, const double* position_range, int ld, void* stream) {
+static int pe_frustum_f32_launch(const int* s2pos, const int* S_dev, int S_max, const double* img2lidar, const double* coords_w, const double* coords_h,
+                                 const double* coords_d, float* out, int V, int h, int w, int depth_num, const double* position_range, int ld,
+                                 const unsigned* view_mask, int tab_period, void* stream) {
     MV2D_CHECK_ARG(s2pos && S_dev && img2lidar && coords_w && coords_h && coords_d && out && position_range, "mv2d_pe_frustum_f32: null pointer");
     MV2D_CHECK_ARG(depth_num > 0 && depth_num <= 256 && V > 0 && h > 0 && w > 0, "mv2d_pe_frustum_f32: bad sizes");
     MV2D_CHECK_ARG(ld >= 3 * depth_num && ld <= 1024, "mv2d_pe_frustum_f32_ld: ld must be in [3 * depth_num, 1024]");
@@ -1497,7 +1513,11 @@ extern "C" int mv2d_pe_frustum_f32_ld(const int* s2pos, const int* S_dev, int S_
         return t;
     }();
     const int blocks = cdiv(S_max, 4) < 4096 ? cdiv(S_max, 4) : 4096;
-    if (ld == 3 * depth_num)
+    if (view_mask)
+        hipLaunchKernelGGL(pe_frustum_f32_sel_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, s2pos, S_dev, img2lidar, coords_w, coords_h, coords_d, out, h, w,
+                           depth_num, position_range[0], position_range[1], position_range[2], 1.0 / (position_range[3] - position_range[0]),
+                           1.0 / (position_range[4] - position_range[1]), 1.0 / (position_range[5] - position_range[2]), lt, ld, view_mask, tab_period);
+    else if (ld == 3 * depth_num)
         hipLaunchKernelGGL(pe_frustum_f32_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, s2pos, S_dev, img2lidar, coords_w, coords_h, coords_d, out, h, w,
                            depth_num, position_range[0], position_range[1], position_range[2], 1.0 / (position_range[3] - position_range[0]),
                            1.0 / (position_range[4] - position_range[1]), 1.0 / (position_range[5] - position_range[2]), lt);
@@ -1507,6 +1527,20 @@ extern "C" int mv2d_pe_frustum_f32_ld(const int* s2pos, const int* S_dev, int S_
                            1.0 / (position_range[4] - position_range[1]), 1.0 / (position_range[5] - position_range[2]), lt, ld);
     MV2D_LAUNCH_CHECK();
     return MV2D_OK;
+}
+
+extern "C" int mv2d_pe_frustum_f32_ld(const int* s2pos, const int* S_dev, int S_max, const double* img2lidar, const double* coords_w, const double* coords_h,
+                                      const double* coords_d, float* out, int V, int h, int w, int depth_num, const double* position_range, int ld, void* stream) {
+    return pe_frustum_f32_launch(s2pos, S_dev, S_max, img2lidar, coords_w, coords_h, coords_d, out, V, h, w, depth_num, position_range, ld, nullptr, 0, stream);
+}
+
+// mv2d_pe_frustum_f32_ld without the rows of the views whose bit of *view_mask is set: view (s2pos[s] % tab_period) / (h w) of a sample
+extern "C" int mv2d_pe_frustum_f32_sel(const int* s2pos, const int* S_dev, int S_max, const double* img2lidar, const double* coords_w, const double* coords_h,
+                                       const double* coords_d, float* out, int V, int h, int w, int depth_num, const double* position_range, int ld,
+                                       const unsigned* view_mask, int tab_period, void* stream) {
+    MV2D_CHECK_ARG(view_mask && h > 0 && w > 0 && tab_period > 0 && tab_period % (h * w) == 0 && tab_period / (h * w) <= 32,
+                   "mv2d_pe_frustum_f32_sel: the view filter needs view_mask (one device word), tab_period % (h * w) == 0 and at most 32 views (tab_period / (h * w))");
+    return pe_frustum_f32_launch(s2pos, S_dev, S_max, img2lidar, coords_w, coords_h, coords_d, out, V, h, w, depth_num, position_range, ld, view_mask, tab_period, stream);
 }
 
 extern "C" int mv2d_pe_frustum_f32(const int* s2pos, const int* S_dev, int S_max, const double* img2lidar, const double* coords_w, const double* coords_h,

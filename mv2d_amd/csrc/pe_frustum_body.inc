@@ -1,5 +1,6 @@
 // Body of pe_frustum_f32_kernel / pe_frustum_f32_ld_kernel (geometry.hip includes it once per kernel, so that the kernel without a pitch keeps its
-// instruction stream).  MV2D_FR_LD: the row pitch of `out` -- (3 * D), or the argument ld; MV2D_FR_PITCHED: 1 = the columns 3 D .. ld - 1 are written as zeros.
+// instruction stream).  MV2D_FR_LD: the row pitch of `out` -- (3 * D), or the argument ld; MV2D_FR_PITCHED: 1 = the columns 3 D .. ld - 1 are written as zeros;
+// MV2D_FR_SEL: 1 = rows of the views whose bit of *view_mask is set are skipped (view (pos % tab_period) / (h w) of a sample, pe_x3_sel.h).
     __shared__ double tab[256];
     tab[threadIdx.x] = lt.t[threadIdx.x];
     __syncthreads();
@@ -7,6 +8,9 @@
     const int S = *S_dev;
     for (int s = blockIdx.x * 4 + wave; s < S; s += gridDim.x * 4) {
         const int pos = __builtin_amdgcn_readfirstlane(s2pos[s]);
+#if MV2D_FR_SEL
+        if ((*view_mask >> ((pos % tab_period) / (h * w))) & 1u) continue;      // a cached view's row: neither computed nor written (wave-uniform)
+#endif
         const int v = pos / (h * w), rem = pos - v * h * w, y = rem / w, x = rem - y * w;
         const double* M = img2lidar + v * 16;
         const double cw = coords_w[x], chh = coords_h[y];

@@ -12,6 +12,7 @@
     const int m0 = blockIdx.x * BM;
     if (m0 >= M) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fr = lane & 15, fg = lane >> 4;
+    PX_SEL_BLOCK();                                     // (pe_x3_sel.h: a tile without a taken row returns here; nothing in the unfiltered kernels)
     const long long lo = (long long)lane * 8 + (long long)wave * CT * 512;
     const WBase w{{p.Wr_h + lo, p.Wr_l + lo}, {p.We_h + lo, p.We_l + lo}, {p.W1a_h + lo, p.W1a_l + lo}, {p.W1b_h + lo, p.W1b_l + lo}};
     XFrag wq[RING][CT], a[2][RT];
@@ -113,6 +114,7 @@
         const int m = min(m0 + 8 * k + r0, M - 1);
         ri[k] = p.row_index ? p.row_index[m] : m;
     }
+    PX_SEL_ROWS();
     // the table rows (and, T path, the fp32 feature rows) of the first 32 output columns are requested before the gate's second layer
     const bool rows16 = p.Xk_hi != nullptr;
     float4 tvq[NK];
@@ -163,7 +165,7 @@
             float4 v = *reinterpret_cast<const float4*>(ot + row * OT_PITCH + c4);
             const float4 tv = tvq[k];
             v = make_float4(v.x + tv.x, v.y + tv.y, v.z + tv.z, v.w + tv.w);
-            if (m < M) {
+            if (m < M && PX_SEL_TAKEN(k)) {
                 if (p.pe) *reinterpret_cast<float4*>(p.pe + (long long)(p.pe_at_index ? ri[k] : m) * C + gcol) = v;
                 if (rows16) {
                     const float4 f = MapElem<MT>::widen(fvq[k]);

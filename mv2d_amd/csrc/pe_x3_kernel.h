@@ -251,6 +251,11 @@ struct Stage {
         __builtin_amdgcn_sched_barrier(0);                                                                 \
     } while (0)
 
+// The hooks of the view filter in pe_x3_body.inc (pe_x3_sel.h fills them in for pe_x3_sel_kernel): nothing in the kernels of this header
+#define PX_SEL_BLOCK() do {} while (0)
+#define PX_SEL_ROWS() do {} while (0)
+#define PX_SEL_TAKEN(k) true
+
 // KS1 = 6 (the shipped 64 bins, A1 rows of 192 columns) keeps the kernel's name; the other depths are pe_x3_depth_kernel<MT, KS1> (A1 rows of pitch 32 KS1)
 template <class MT>
 __global__ __launch_bounds__(NTHR, 1) void pe_x3_kernel(PeX3ParamsT<MT> p) {

@@ -121,7 +121,7 @@ class HeadEngine:
         # adapt_pos3d(sine) (MU/pe.py:164-166) depends only on the weights and on the padding geometry of the rig, not on features, boxes
         # or calibration: it is constant-folded into a per-(weights version, geometry) table that the fused PE kernel adds in its epilogue
         self._weights_version = 0     # bumped by every load_state(): invalidates whatever was folded from the weights
-        self.pe_cache_builds = 0      # tables of the cached frustum MLP this engine built (route option pe_cache, _build_pe_q)
+        self.pe_cache_builds = 0      # tables of the cached frustum MLP this engine built (route options pe_cache / pe_cache_views: _build_pe_q / _build_pe_q_views, once per frame that builds)
         self.exact = (os.environ.get('MV2D_EXACT', '1') != '0') if exact is None else bool(exact)
         self.K16 = ops.key16_dtype()  # dtype of the key side's 16-bit buffers (csrc/common.h "key16": fp16 since round 4)
         self.load_state(state_dict)
@@ -695,6 +695,29 @@ class HeadEngine:
             if ws.get('pe_q_gen') != sh.get('pe_q_gen'):
                 ws['pe_q_gen'] = sh.get('pe_q_gen')
                 ws['graph_stale'] = True                                 # (a re-allocated table: captured graphs hold the old pointer)
+        # the two-frame head keeps that table PER VIEW (route option pe_cache_views): the views whose matrices repeat (the current frame of a fixed
+        # calibration) read their slice of Q, the others (ego motion) run the full kernel; the mask of cached views is DATA, uploaded here
+        ws['pe_views'] = ()
+        if rt.pe_cache_views:
+            Pt = (V * h * w) // B
+            usable = sh['sine_period'] == Pt and Vg <= 32                # (Q and the sine table share the kernel's one period; one mask word)
+            pol = sh.get('pe_qv_policy')
+            if pol is None and Vg <= 32:
+                pol = sh['pe_qv_policy'] = pe_cache.PeViewCachePolicy(Vg)
+            mask, build, state = 0, (), 'miss'
+            if pol is not None:                                          # (an unusable frame drops every slice)
+                mask, build, state = pol.observe(pe_cache.view_keys(self._weights_version, shape_key, mats, B) if usable else [None] * Vg)
+            if build:
+                self._build_pe_q_views(ws, sh, Pt, V, h, w, build)
+            ws['pe_hit'], ws['pe_cache_state'], ws['pe_views'] = mask != 0, state, pe_cache.mask_views(mask)
+            if ws.get('pe_q_gen') != sh.get('pe_q_gen'):
+                ws['pe_q_gen'] = sh.get('pe_q_gen')
+                ws['graph_stale'] = True                                 # (a re-allocated table: captured graphs hold the old pointer)
+            if sh.get('pe_vmask') is None:
+                sh['pe_vmask_h'] = torch.zeros(1, dtype=torch.int32).pin_memory()
+                sh['pe_vmask'] = torch.zeros(1, dtype=torch.int32, device=self.dev)
+            sh['pe_vmask_h'].numpy().view(np.uint32)[0] = mask
+            sh['pe_vmask'].copy_(sh['pe_vmask_h'], non_blocking=True)    # stream-ordered in front of the frame, outside any captured graph
         ws['view_start_h'].numpy()[:] = np.concatenate([[0], np.cumsum(counts)])
         ws['grp_start_h'].numpy()[:] = grp
         if self.kind == 'T':
@@ -871,6 +894,20 @@ class HeadEngine:
         1.09 ms (S) / 2.17 ms (T) per 16-sample launch.  No host synchronisation, no allocation: graph-replayable."""
         o, W_, T, rt = ops, self.w, ws['tab'], ws['route']
         md = ws['S_dev']
+        if ws.get('pe_hit') and rt.pe_cache_views:
+            # some views' matrices repeat (route option pe_cache_views): the frustum rows and the full kernel on the rows of the OTHER views, the gate alone
+            # on the table Q for the rows of the repeated ones -- three launches into the same row buffers, every row bit for bit the full kernel's.  The
+            # mask is read from device memory (sh['pe_vmask'], uploaded by _host_prepare): one captured graph serves every mask but 0
+            sh = ws['shared']
+            hw, period, vm = h * w, sh['sine_period'], sh['pe_vmask']
+            flag = ws['lo8_flag'] if rt.lo8 else None
+            o.pe_frustum_f32(ws['s2pos'], md, P, T['img2lidar'], T['coords_w'], T['coords_h'], T['coords_d'], ws['xa1'], V, h, w, self.depth_num,
+                             self.pe_range_h64, ld=self.pe_kp, view_mask=vm, tab_period=period)
+            o.pe_fused_x3(ws['xa1'], featcl, md, W_['pe_x3'], sh['sine_tab'], period, Xk=(ws['Xk'], ws['xk_lo']), Xv=(ws['Xf_b'], ws['xv_lo']), M=P,
+                          row_index=ws['s2pos'], lo8_flag=flag, Kp=self.pe_kp, view_mask=vm, hw=hw)
+            o.pe_gate_rows_x3(sh['pe_q'], featcl, md, W_['pe_x3'], sh['sine_tab'], period, (ws['Xk'], ws['xk_lo']), (ws['Xf_b'], ws['xv_lo']), P, vm, hw,
+                              row_index=ws['s2pos'], lo8_flag=flag)
+            return
         if ws.get('pe_hit'):
             # the rig's matrices repeat (route option pe_cache): no frustum rows, no frustum MLP -- the gate alone on the table Q, same pe bits
             sh = ws['shared']
@@ -913,6 +950,26 @@ class HeadEngine:
         if sh.get('pe_q_zero') is None:
             sh['pe_q_zero'] = torch.zeros((1, C), device=d, dtype=F32)
         o.pe_fused_x3(a1, None, None, self.w['pe_x3'], sh['pe_q_zero'], 1, pe=q, M=Pt, Kp=self.pe_kp, gate=False)
+        self.pe_cache_builds = getattr(self, 'pe_cache_builds', 0) + 1
+
+    def _build_pe_q_views(self, ws, sh, Pt, V, h, w, views):
+        """The slices of the per-view table Q [Pt,256] (route option pe_cache_views) of the given views of ONE sample, with the matrices this frame
+        uploaded: _build_pe_q's launches on the positions of those views only, each row written in place at its position (pe_at_index).  Enqueued on
+        the current stream in front of the frame, outside any captured graph; the slices of the other views are not touched."""
+        T, o, d, hw = ws['tab'], ops, self.dev, h * w
+        pos = torch.cat([torch.arange(v * hw, (v + 1) * hw, dtype=torch.int32) for v in views]).to(d)
+        n = int(pos.numel())
+        a1 = torch.empty((n, self.pe_kp), device=d, dtype=F32)
+        o.pe_frustum_f32(pos, torch.tensor([n], dtype=torch.int32, device=d), n, T['img2lidar'], T['coords_w'], T['coords_h'], T['coords_d'], a1, V, h, w,
+                         self.depth_num, self.pe_range_h64, ld=self.pe_kp)
+        q = sh.get('pe_q')
+        if q is None or tuple(q.shape) != (Pt, C):
+            if q is not None:
+                sh['pe_q_gen'] = sh.get('pe_q_gen', 0) + 1
+            q = sh['pe_q'] = torch.zeros((Pt, C), device=d, dtype=F32)
+        if sh.get('pe_q_zero') is None:
+            sh['pe_q_zero'] = torch.zeros((1, C), device=d, dtype=F32)
+        o.pe_fused_x3(a1, None, None, self.w['pe_x3'], sh['pe_q_zero'], 1, pe=q, M=n, row_index=pos, pe_at_index=True, Kp=self.pe_kp, gate=False)
         self.pe_cache_builds = getattr(self, 'pe_cache_builds', 0) + 1
 
     def pe_input_rows(self, ws, positions, V, h, w, f32=False):
@@ -1087,7 +1144,8 @@ class HeadEngine:
         sel = (lambda t: t) if batch else (lambda t: t[0])
         out = dict(R=R, ws=ws, cls=ws['cls'][:, :R], reg=ws['reg'][:, :R], boxes=sel(ws['boxes']), scores=sel(ws['scores']), labels=sel(ws['labels']),
                    bbox_index=sel(ws['bbox_index']), count=ws['count'] if batch else ws['count'][:1], grp_start=ws['grp_start_h'].clone(),
-                   pe_cache=ws.get('pe_cache_state', 'off'))     # 'off' | 'miss' | 'build' | 'hit': what this frame's PE launch was (route option pe_cache)
+                   pe_cache=ws.get('pe_cache_state', 'off'),     # 'off' | 'miss' | 'build' | 'hit': what this frame's PE launch was (route options pe_cache, pe_cache_views)
+                   pe_cache_views=ws.get('pe_views', ()))        # the views of a sample whose rows read the cached table (pe_cache_views; () otherwise)
         if ws['route'].stages:
             # copies of the intermediate buffers restricted to the REAL rows (the launches run on the bucket size, see _host_prepare)
             rows0 = ('rois', 'minv', 'enc', 'roi_feat', 'center', 'xyz', 'ref', 'posemb', 'qpos', 'match')
@@ -1173,7 +1231,8 @@ class HeadEngine:
                 self.use_reg_layer, self.group_reg_dims, self.num_reg_fcs, self._weights_version, rt)
         graphs = ws.setdefault('graphs', {})             # one graph per (input buffers, frame scalars): a producer that alternates between
         g = graphs.get(gkey)                             # a few static output buffers replays a few graphs, it does not re-capture
-        # A key's graph exists in up to two FORMS: with the full PE launches, or with the gate-only one (pe_hit, route option pe_cache).  ws['graphs']
+        # A key's graph exists in up to two FORMS: with the full PE launches, or with the gate-only one (pe_hit, route option pe_cache; pe_cache_views: the
+        # three split launches, whatever the mask's value).  ws['graphs']
         # holds the form the key's last frame ran, the other one is parked beside it and swapped back in when the form flips (a rig's first frame
         # captures the full form, its second the hit form; a stream never re-captures a form it has)
         hit, parked = ws['pe_hit'], ws.setdefault('graphs_other_pe_form', {})

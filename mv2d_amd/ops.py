@@ -671,14 +671,28 @@ def pad_pe_w1a(W, depth_num=None):
     return Wp
 
 
+def _view_sel(name, view_mask, hw, tab_period):
+    """The view filter of the PE entries (include/mv2d_hip.h "THE VIEW FILTER"): view_mask = ONE int32 word on the GPU, hw = cells of one view's map,
+    at most 32 views per sample (tab_period / hw).  Returns (pointer, hw)."""
+    _req(view_mask, torch.int32, name + ': view_mask')
+    if view_mask.numel() != 1:
+        raise _lib.Mv2dHipError(f'{name}: view_mask is one int32 word on the GPU, got {tuple(view_mask.shape)}')
+    hw, tab_period = int(hw or 0), int(tab_period)
+    if hw <= 0 or tab_period <= 0 or tab_period % hw != 0 or tab_period // hw > 32:
+        raise _lib.Mv2dHipError(f'{name}: a view mask needs tab_period % hw == 0 and at most 32 views (Vg <= 32), got tab_period = {tab_period}, hw = {hw}')
+    return _p(view_mask), hw
+
+
 def pe_fused_x3(A1, Xmap, m_dev, wx, sine_tab, tab_period, pe=None, Xk=None, Xv=None, M=None, row_index=None, pe_at_index=False, lo8_flag=None,
-                map_fmt=None, Kp=None, gate=True):
+                map_fmt=None, Kp=None, gate=True, view_mask=None, hw=None, take_set=False):
     """The PE block in split precision on unrounded inputs (index-exact route, csrc/pe_x3.hip).  gate=False: the PE without the feature-guided gate
     (with_fpe=False; mv2d_pe_fused_x3_ng): wx needs no 'wr','we','br','be', and Xmap may be None when neither Xk nor Xv is asked for.  A1 [M,Kp] fp32 (Kp = pe_kp(depth_num): frustum rows with zero
     pad columns, wx['w1a'] packed from pad_pe_w1a(weight); Kp=None: the columns of A1; the library picks the kernel instance from Kp); Xmap feature rows, fp32, fp16 or
     bf16 (widened in the kernel; indexed by row_index when given); wx: dict 'w1a','w1b','wr','we' = pack_x3(weight) pairs + fp32 biases 'b1a','b1b','br','be'; pe [M,256]
     fp32 and / or Xk = (hi, lo), Xv = (hi, lo) key16 [M,256] pairs (key rows pe + feat, value rows feat).  pe_at_index: pe row m goes to row
-    row_index[m] of `pe` (a position-indexed map for roi_align without map1_index)."""
+    row_index[m] of `pe` (a position-indexed map for roi_align without map1_index).
+    view_mask (one int32 word on the GPU) + hw: the FILTERED form (mv2d_pe_fused_x3_k_sel) -- only the rows of the views whose bit is clear are written
+    (take_set=True: whose bit is set), view of row m = (row_index[m] % tab_period) // hw; gated, with Xk and Xv, pe in row order."""
     _req(A1, torch.float32, 'A1'); _req(sine_tab, torch.float32, 'sine_tab'); _req(pe, torch.float32, 'pe')
     fmt = 0 if (Xmap is None and not gate) else _req_map(Xmap, 'Xmap', map_fmt)
     _req(row_index, torch.int32, 'row_index'); _req(m_dev, torch.int32, 'm_dev')
@@ -694,6 +708,15 @@ def pe_fused_x3(A1, Xmap, m_dev, wx, sine_tab, tab_period, pe=None, Xk=None, Xv=
     if A1.dim() != 2 or A1.shape[1] != Kp or wx['w1a'][0].numel() != 1024 * Kp:
         raise _lib.Mv2dHipError(f'pe_fused_x3: A1 {tuple(A1.shape)} / w1a ({wx["w1a"][0].numel()} elements) do not have Kp = {Kp} columns')
     rows = (_p(A1), _p(Xmap), _p(row_index), _p(m_dev), M, _p(wx['w1a'][0]), _p(wx['w1a'][1]), _p(wx['b1a']), _p(wx['w1b'][0]), _p(wx['w1b'][1]), _p(wx['b1b']))
+    if view_mask is not None:
+        name = 'mv2d_pe_fused_x3_k_sel'
+        vm, hw = _view_sel(name, view_mask, hw, tab_period)
+        if not gate or Xk is None or Xv is None or pe_at_index:
+            raise _lib.Mv2dHipError(name + ': the filtered form is the gated kernel with key / value row outputs (Xk and Xv), pe in row order')
+        check(_lib.load().mv2d_pe_fused_x3_k_sel(*rows, _p(wx['wr'][0]), _p(wx['wr'][1]), _p(wx['br']), _p(wx['we'][0]), _p(wx['we'][1]), _p(wx['be']),
+                                                 _p(sine_tab), int(tab_period), _p(pe), _p(xk[0]), _p(xk[1]), _p(xv[0]), _p(xv[1]), lo_fmt, _p(lo8_flag), fmt,
+                                                 int(Kp), vm, hw, 1 if take_set else 0, _stream()), name)
+        return pe
     outs = (_p(sine_tab), int(tab_period), _p(pe), _p(xk[0]), _p(xk[1]), _p(xv[0]), _p(xv[1]), lo_fmt, 1 if (pe_at_index and row_index is not None) else 0,
             _p(lo8_flag), fmt, int(Kp), _stream())
     if gate:
@@ -723,6 +746,30 @@ def pe_gate_x3(Q, Xmap, m_dev, wx, sine_tab, tab_period, pe, M, row_index=None, 
                                       _p(wx['we'][1]), _p(wx['be']), _p(sine_tab), int(tab_period), _p(pe), _p(xk[0]), _p(xk[1]), _p(xv[0]), _p(xv[1]),
                                       1 if (pe_at_index and row_index is not None) else 0, fmt, _stream()), name)
     return pe
+
+
+def pe_gate_rows_x3(Q, Xmap, m_dev, wx, sine_tab, tab_period, Xk, Xv, M, view_mask, hw, row_index=None, pe=None, lo8_flag=None, map_fmt=None, take_set=True):
+    """pe_gate_x3 with the key / value row outputs of pe_fused_x3 and a view filter (csrc/pe_x3_gate.hip pe_x3_gate_rows_kernel, two-frame head): for the
+    rows of the views whose bit of view_mask (one int32 word on the GPU) is set, Xk = (hi, lo) rows of pe + feature row and Xv = (hi, lo) rows of the
+    feature row, bit for bit what pe_fused_x3 writes for them on the frustum rows Q was built from; the other rows are left alone (the filtered
+    pe_fused_x3 writes them).  View of row m = (row_index[m] % tab_period) // hw.  pe [M,256] (optional) in row order."""
+    name = 'mv2d_pe_gate_rows_x3'
+    _req(Q, torch.float32, name + ': Q'); _req(sine_tab, torch.float32, name + ': sine_tab'); _req(pe, torch.float32, name + ': pe')
+    if Q is None or Xmap is None or Xk is None or Xv is None:
+        raise _lib.Mv2dHipError(name + ': Q, Xmap, Xk and Xv are required')
+    fmt = _req_map(Xmap, name + ': Xmap', map_fmt)
+    _req(row_index, torch.int32, name + ': row_index'); _req(m_dev, torch.int32, name + ': m_dev')
+    for pair in (Xk, Xv):
+        _req16(pair[0], name + ': hi rows')
+    lo_fmt = _lo_fmt(Xk[1], Xv[1])
+    for k in ('wr', 'we'):
+        _req(wx[k][0], q16_dtype(), name + ': ' + k); _req(wx[k][1], q16_dtype(), name + ': ' + k)
+    vm, hw = _view_sel(name, view_mask, hw, tab_period)
+    if tuple(Q.shape) != (int(tab_period), 256) or sine_tab.dim() != 2 or sine_tab.shape[0] < int(tab_period) or sine_tab.shape[1] != 256:
+        raise _lib.Mv2dHipError(f'{name}: Q {tuple(Q.shape)} / sine_tab {tuple(sine_tab.shape)} do not hold tab_period = {tab_period} rows of 256')
+    check(_lib.load().mv2d_pe_gate_rows_x3(_p(Q), _p(Xmap), _p(row_index), _p(m_dev), int(M), _p(wx['wr'][0]), _p(wx['wr'][1]), _p(wx['br']), _p(wx['we'][0]),
+                                           _p(wx['we'][1]), _p(wx['be']), _p(sine_tab), int(tab_period), _p(pe), _p(Xk[0]), _p(Xk[1]), _p(Xv[0]), _p(Xv[1]),
+                                           lo_fmt, _p(lo8_flag), fmt, vm, hw, 1 if take_set else 0, _stream()), name)
 
 
 def pe_fused_x3b(A1, Xmap, m_dev, wx, sine_tab, tab_period, pe=None, Xk=None, Xv=None, M=None, row_index=None, pe_at_index=False, lo8_flag=None):
@@ -1259,15 +1306,24 @@ def pe_inputs(s2pos, S_dev, S_max, featcl, img2lidar, coords_w, coords_h, coords
                                         _p(A_sine_f32), V, h, w, depth_num, position_range_host.data_ptr(), fmt, ld, _stream()), 'mv2d_pe_inputs')
 
 
-def pe_frustum_f32(s2pos, S_dev, S_max, img2lidar, coords_w, coords_h, coords_d, out, V, h, w, depth_num, position_range_host, ld=None):
+def pe_frustum_f32(s2pos, S_dev, S_max, img2lidar, coords_w, coords_h, coords_d, out, V, h, w, depth_num, position_range_host, ld=None,
+                   view_mask=None, tab_period=None):
     """out [S, 3 D] fp32: the unrounded frustum rows of the PE block at the listed positions (index-exact route; fp64 arithmetic, fast form).
-    ld: row pitch (out [S, ld], ld >= 3 D; the kernel zeroes the pad columns); None = 3 D."""
+    ld: row pitch (out [S, ld], ld >= 3 D; the kernel zeroes the pad columns); None = 3 D.
+    view_mask (one int32 word on the GPU) + tab_period: the FILTERED form (mv2d_pe_frustum_f32_sel) -- rows of the views whose bit is set, view =
+    (s2pos[s] % tab_period) // (h w), are neither computed nor written."""
     _req(s2pos, torch.int32, 's2pos'); _req(S_dev, torch.int32, 'S_dev'); _req(out, torch.float32, 'out')
     for t, n_ in ((img2lidar, 'img2lidar'), (coords_w, 'coords_w'), (coords_h, 'coords_h'), (coords_d, 'coords_d')):
         _req(t, torch.float64, n_)
     ld = 3 * depth_num if ld is None else int(ld)
     if out.dim() != 2 or out.shape[1] != ld:
         raise _lib.Mv2dHipError(f'pe_frustum_f32: out {tuple(out.shape)} does not have {ld} columns')
+    if view_mask is not None:
+        name = 'mv2d_pe_frustum_f32_sel'
+        vm, _ = _view_sel(name, view_mask, h * w, 0 if tab_period is None else tab_period)
+        check(_lib.load().mv2d_pe_frustum_f32_sel(_p(s2pos), _p(S_dev), S_max, _p(img2lidar), _p(coords_w), _p(coords_h), _p(coords_d), _p(out), V, h, w,
+                                                  depth_num, position_range_host.data_ptr(), ld, vm, int(tab_period), _stream()), name)
+        return out
     check(_lib.load().mv2d_pe_frustum_f32_ld(_p(s2pos), _p(S_dev), S_max, _p(img2lidar), _p(coords_w), _p(coords_h), _p(coords_d), _p(out), V, h, w,
                                              depth_num, position_range_host.data_ptr(), ld, _stream()), 'mv2d_pe_frustum_f32')
     return out

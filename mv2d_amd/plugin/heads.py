@@ -306,6 +306,8 @@ class MV2DHead(nn.Module):
                                       exact=(self.test_cfg or {}).get('index_exact', None))      # None: MV2D_EXACT decides
             if 'lo8_rows' in (self.test_cfg or {}):                              # test_cfg.lo8_rows=False: fp16 lo halves of the key / value rows (engine.py; default: e4m3 bytes)
                 self._engine.lo8_rows = bool(self.test_cfg['lo8_rows'])
+            if 'pe_cache_views' in (self.test_cfg or {}):                        # test_cfg.pe_cache_views=True: the per-view PE cache of the two-frame head (route.py; default off)
+                self._engine.pe_cache_views = bool(self.test_cfg['pe_cache_views'])
             self._engine_ver = ver
         return self._engine
 

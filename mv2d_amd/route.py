@@ -17,7 +17,7 @@ def default_options():
         xattn_waves=int(env('MV2D_XATTN_WAVES', '2')), q_order=True, fold_sa0=True, masked_transpose=True, last_stage_heads=False,
         exact_skip=frozenset({'conv'}), lo8_rows=True, pe_at_positions=env('MV2D_PE_AT_POS', '1') != '0', pe_rows_in_waves=False,
         ablate_zero_lo=frozenset(), keep_sine_rows=False, stop_before_decoder=False, force_nc=None, debug_attn=False,
-        fuse_qg_tail=env('MV2D_QG_TAIL', '1') != '0', pe_cache=env('MV2D_PE_CACHE', '1') != '0')
+        fuse_qg_tail=env('MV2D_QG_TAIL', '1') != '0', pe_cache=env('MV2D_PE_CACHE', '1') != '0', pe_cache_views=env('MV2D_PE_CACHE_VIEWS', '0') == '1')
 
 
 OPTIONS = tuple(default_options())
@@ -131,6 +131,14 @@ class Route(NamedTuple):
     # sine rows, not the rows-in-waves shape.  Whether a frame does use the table is decided per frame from its matrices (mv2d_amd/pe_cache.py) and is
     # part of the graph key next to the route.  MV2D_PE_CACHE=0 turns it off (A/B runs).
     pe_cache: bool
+    # option pe_cache_views, OPT-IN (default off; MV2D_PE_CACHE_VIEWS=1 or test_cfg.pe_cache_views turns it on): the same cache PER VIEW on the two-frame
+    # head.  A sample has 2 * num_views views; the current-frame views of a fixed calibration repeat their matrices, the previous-frame views carry the
+    # ego motion.  The table Q holds one slice per view; a frame whose mask of repeated views is not 0 runs three launches into the same key / value row
+    # buffers -- the frustum rows of the other views (mv2d_pe_frustum_f32_sel), the full kernel on them (csrc/pe_x3_sel.h) and the gate with row outputs on
+    # the repeated views (csrc/pe_x3_gate.hip pe_x3_gate_rows_kernel), every row bit for bit the full kernel's.  The mask is read from device memory: it is
+    # not part of the graph key, only "full launches" / "split launches" is.  This field: the route ALLOWS it -- T path, and the conditions of pe_cache.
+    # The S path ignores the option.
+    pe_cache_views: bool
 
     @property
     def storage(self):
@@ -174,8 +182,10 @@ def resolve(opts, kind, exact, depth_num, map_dtype=torch.float32, keep_stages=F
     assert not (debug and use_graph), 'debug_attn: eager runs only'
     pe_pos = kind == 'S' and exact and bool(o.pe_at_positions)
     pe_opt = lambda key, shipped: (pe_options or {}).get(key, shipped)      # noqa: E731
-    pe_cache = (bool(o.pe_cache) and kind == 'S' and pe_x3 and bool(pe_opt('with_fpe', True)) and not pe_opt('no_sin_enc', False) and not stages
-                and not o.keep_sine_rows and not o.pe_rows_in_waves)
+    pe_cache_ok = (pe_x3 and bool(pe_opt('with_fpe', True)) and not pe_opt('no_sin_enc', False) and not stages and not o.keep_sine_rows
+                   and not o.pe_rows_in_waves)
+    pe_cache = bool(o.pe_cache) and kind == 'S' and pe_cache_ok
+    pe_cache_views = bool(o.pe_cache_views) and kind == 'T' and pe_cache_ok
     forked = kind == 'T' and (o.prof is None or use_graph) and bool(o.fork_qg) and not exact        # (a graph is captured with stage timing off)
     return Route(
         kind=kind, exact=exact, lo8=lo8, pe_pos=pe_pos, group_tab=group, q_order=bool(o.q_order), map_dtype=map_dtype, stages=stages,
@@ -186,4 +196,4 @@ def resolve(opts, kind, exact, depth_num, map_dtype=torch.float32, keep_stages=F
         masked=bool(o.masked_transpose) and not forked and not o.keep_sine_rows and not stages,
         last_stage_heads=bool(o.last_stage_heads) and not stages, debug_attn=debug, stop_before_decoder=bool(o.stop_before_decoder),
         force_nc=o.force_nc, ablate_zero_lo=frozenset(o.ablate_zero_lo) if exact else frozenset(),
-        qg_tail_fused=bool(o.fuse_qg_tail) and not stages, pe_cache=pe_cache)
+        qg_tail_fused=bool(o.fuse_qg_tail) and not stages, pe_cache=pe_cache, pe_cache_views=pe_cache_views)
