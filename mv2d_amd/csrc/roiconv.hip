@@ -17,13 +17,11 @@
 // k order = (tap, channel) like the implicit GEMM, so the conv sums are bit-identical; only the 49-term pooling sum is
 // re-associated (fp32, ~1e-7).  Every output is bit for bit what the one-launch form with four row tiles per RoI wrote: each output element
 // keeps its MFMA sequence and its single accumulator, and the pooling sum keeps its order (tests/test_gpu_conv_cell48.py).
-#include "common.h"
+#include "roiconv_walk.h"
 
 namespace {
 
-constexpr int C = 256, CELLS = 49, KT = 9 * C;
-struct Frag { uint4 u; };                     // one MFMA operand fragment: 8 key16 values (common.h: fp16 since round 4)
-typedef unsigned int cv_u32x4 __attribute__((ext_vector_type(4)));
+constexpr int CELLS = 49, KT = 9 * C;
 
 // Keeps already requested loads where they were issued: the values count as used here, so hipcc cannot sink the loads to their first use
 // in the epilogue (an exposed round trip there).
@@ -363,119 +361,17 @@ __global__ __launch_bounds__(256, 2) void roi_conv_pool_x3_kernel(const unsigned
     }
 }
 
-// Any RoI size s x s, 1 <= s <= 14 (the 7 x 7 kernels above stay the shipped instances).  One RoI per block, its s * s cells in chunks of 64
-// output cells (four row tiles, ceil(s * s / 64) chunks): a chunk stages only the cell rows its taps read (its own rows and one above and
-// below: at most 112 cells, s = 14) plus a zero row into LDS, then runs the same 72 k-steps as the kernels above (weights fragment-major
-// through a 4-deep register ring, the same tap remapping, k order (tap, channel); a rolled loop over the 9 taps, 8 unrolled k-steps each), and
-// adds bias + ReLU of its cells to the per-column sums.
-// X3: the split-precision products of roi_conv_pool_x3_kernel (two LDS images, 2 x 60 KB: one block per CU); otherwise key16 x key16.
-// Not tuned: the weights are streamed once per chunk.
-constexpr int GW_ROWS = 120, GW_ZERO = GW_ROWS - 1;     // LDS rows of a window (<= 112 cells) and the index of its zero row
-
+// Any RoI size s x s, 1 <= s <= 14 (the 7 x 7 kernels above stay the shipped instances): the chunked window walk of roiconv_walk.inc, one RoI per
+// block; every chunk adds bias + ReLU of its cells to the per-column sums, which are pooled behind the last one.
+// X3: the split-precision products of roi_conv_pool_x3_kernel; otherwise key16 x key16.
 template <bool X3>
 __global__ __launch_bounds__(256, X3 ? 1 : 2) void roi_conv_pool_s_kernel(const unsigned short* __restrict__ feat_hi, const unsigned short* __restrict__ feat_lo,
                                                                          const unsigned short* __restrict__ Wh, const unsigned short* __restrict__ Wl,
                                                                          const float* __restrict__ bias, float* __restrict__ out, int ld_out, int R, int s) {
-    constexpr int RING = 4, NIMG = X3 ? 2 : 1;           // ring depth 4 divides the 8 k-steps of a tap: compile-time ring slots in the tap loop
-    __shared__ __attribute__((aligned(16))) unsigned char xs[NIMG][GW_ROWS * C * 2];
-    __shared__ float bs[C];
-    const int roi = blockIdx.x;
-    if (roi >= R) return;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fr = lane & 15, fg = lane >> 4;
-    const int S2 = s * s;
-    const long long w_off = ((long long)(wave * 4) * 64 + lane) * 8;
-    constexpr int KS_STRIDE = 16 * 64 * 8, JT_STRIDE = 64 * 8;
-    bs[tid] = bias[tid];
     float psum[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int c0 = 0; c0 < S2; c0 += 64) {
-        const int last = min(c0 + 63, S2 - 1);
-        const int ylo = max(c0 / s - 1, 0), yhi = min(last / s + 1, s - 1);
-        const int wb = ylo * s, nwin = (yhi - ylo + 1) * s;          // window: cells [wb, wb + nwin) of the RoI, nwin <= 112
-        Frag wqh[RING][4], wql[RING][4];
-#pragma unroll
-        for (int p = 0; p < RING - 1; ++p)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                wqh[p][j].u = *reinterpret_cast<const uint4*>(Wh + w_off + p * KS_STRIDE + j * JT_STRIDE);
-                if (X3) wql[p][j].u = *reinterpret_cast<const uint4*>(Wl + w_off + p * KS_STRIDE + j * JT_STRIDE);
-            }
-        __syncthreads();                                 // the previous chunk's LDS reads are done
-        for (int c = tid; c < nwin * 32; c += 256) {
-            const int row = c >> 5, slot = c & 31;
-            const long long src = ((long long)roi * S2 + wb + row) * C + slot * 8;
-            const int dst = row * (C * 2) + ((slot ^ (row & 15)) << 4);
-            *reinterpret_cast<cv_u32x4*>(&xs[0][dst]) = *reinterpret_cast<const cv_u32x4*>(feat_hi + src);
-            if (X3) *reinterpret_cast<cv_u32x4*>(&xs[NIMG - 1][dst]) = *reinterpret_cast<const cv_u32x4*>(feat_lo + src);
-        }
-        if (tid < 32)
-#pragma unroll
-            for (int m = 0; m < NIMG; ++m) *reinterpret_cast<cv_u32x4*>(&xs[m][GW_ZERO * (C * 2) + (tid << 4)]) = cv_u32x4{0u, 0u, 0u, 0u};
-        // cell coordinates of the chunk's 4 row tiles for this lane (cell = c0 + 16 i + fr)
-        int cy[4], cx[4];
-        bool cv[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { const int cell = c0 + 16 * i + fr; cv[i] = cell < S2; cy[i] = cell / s; cx[i] = cell - cy[i] * s; }
-        f32x4_t acc[4][4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-        __syncthreads();
-#pragma unroll 1
-        for (int tap = 0; tap < 9; ++tap) {
-            const int dy = tap / 3 - 1, dx = tap - (tap / 3) * 3 - 1;
-            int src[4];
-#pragma unroll
-            for (int it = 0; it < 4; ++it) {
-                const int y = cy[it] + dy, x = cx[it] + dx;
-                const bool ok = cv[it] && y >= 0 && y < s && x >= 0 && x < s;
-                src[it] = ok ? y * s + x - wb : GW_ZERO;
-            }
-#pragma unroll
-            for (int sk = 0; sk < 8; ++sk) {
-                const int ks = tap * 8 + sk;
-                if (ks + RING - 1 < 72) {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        wqh[(sk + RING - 1) % RING][j].u = *reinterpret_cast<const uint4*>(Wh + w_off + (ks + RING - 1) * KS_STRIDE + j * JT_STRIDE);
-                        if (X3) wql[(sk + RING - 1) % RING][j].u = *reinterpret_cast<const uint4*>(Wl + w_off + (ks + RING - 1) * KS_STRIDE + j * JT_STRIDE);
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                Frag ah[4], al[4];
-#pragma unroll
-                for (int it = 0; it < 4; ++it) {
-                    const int off = src[it] * (C * 2) + (((4 * sk + fg) ^ (src[it] & 15)) << 4);
-                    ah[it].u = *reinterpret_cast<const uint4*>(&xs[0][off]);
-                    if (X3) al[it].u = *reinterpret_cast<const uint4*>(&xs[NIMG - 1][off]);
-                }
-                if (X3) {
-#pragma unroll
-                    for (int it = 0; it < 4; ++it)
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) acc[it][j] = mfma_k16_16x16x32(al[it].u, wqh[sk % RING][j].u, acc[it][j]);
-#pragma unroll
-                    for (int it = 0; it < 4; ++it)
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) acc[it][j] = mfma_k16_16x16x32(ah[it].u, wql[sk % RING][j].u, acc[it][j]);
-                }
-#pragma unroll
-                for (int it = 0; it < 4; ++it)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) acc[it][j] = mfma_k16_16x16x32(ah[it].u, wqh[sk % RING][j].u, acc[it][j]);
-            }
-        }
-        // bias + ReLU of the chunk's cells: lane holds cells c0 + 16 i + 4 fg + r of column 64 wave + 16 j + fr
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float b = bs[wave * 64 + 16 * j + fr];
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    if (c0 + 16 * i + 4 * fg + r < S2) psum[j] += relu_f(acc[i][j][r] + b);
-        }
-    }
+#define ROI_CONV_WALK_CELL(v, cell, n, j) psum[j] += (v)
+#include "roiconv_walk.inc"
+#undef ROI_CONV_WALK_CELL
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         float sum = psum[j];
@@ -508,40 +404,27 @@ extern "C" int mv2d_pack_wfrag_bf16(const void* W, void* Wp, int N, int K, void*
     return MV2D_OK;
 }
 
-extern "C" int mv2d_qg_conv_pool(const void* roi_feat, const void* W, const float* bias, float* out, int ld_out, int R, void* stream);
-extern "C" int mv2d_qg_conv_pool_x3(const void* roi_feat_hi, const void* roi_feat_lo, const void* W_hi, const void* W_lo, const float* bias, float* out,
-                                    int ld_out, int R, void* stream);
+namespace {
 
-// s x s cells per RoI, 1 <= s <= 14: the 7 x 7 kernels for s = 7, roi_conv_pool_s_kernel otherwise
-extern "C" int mv2d_qg_conv_pool_s(const void* roi_feat, const void* W, const float* bias, float* out, int ld_out, int R, int roi_size, void* stream) {
-    MV2D_CHECK_ARG(roi_size >= 1 && roi_size <= 14, "mv2d_qg_conv_pool_s: roi_size must be in [1, 14]");
-    if (roi_size == 7) return mv2d_qg_conv_pool(roi_feat, W, bias, out, ld_out, R, stream);
+// the argument check of the key16 entries, with or without a RoI size
+int check_pool_args(const void* roi_feat, const void* W, const float* bias, const float* out, int ld_out) {
     MV2D_CHECK_ARG(roi_feat && W && bias && out && ld_out >= C, "mv2d_qg_conv_pool: bad args");
     MV2D_CHECK_ARG(((uintptr_t)roi_feat & 15) == 0 && ((uintptr_t)W & 15) == 0, "mv2d_qg_conv_pool: operands must be 16-byte aligned");
-    if (R == 0) return MV2D_OK;
-    hipLaunchKernelGGL(roi_conv_pool_s_kernel<false>, dim3(R), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)roi_feat, nullptr,
-                       (const unsigned short*)W, nullptr, bias, out, ld_out, R, roi_size);
-    MV2D_LAUNCH_CHECK();
     return MV2D_OK;
 }
 
-extern "C" int mv2d_qg_conv_pool_x3_s(const void* roi_feat_hi, const void* roi_feat_lo, const void* W_hi, const void* W_lo, const float* bias, float* out,
-                                      int ld_out, int R, int roi_size, void* stream) {
-    MV2D_CHECK_ARG(roi_size >= 1 && roi_size <= 14, "mv2d_qg_conv_pool_x3_s: roi_size must be in [1, 14]");
-    if (roi_size == 7) return mv2d_qg_conv_pool_x3(roi_feat_hi, roi_feat_lo, W_hi, W_lo, bias, out, ld_out, R, stream);
+// ... and of the split-precision entries
+int check_pool_x3_args(const void* roi_feat_hi, const void* roi_feat_lo, const void* W_hi, const void* W_lo, const float* bias, const float* out, int ld_out) {
     MV2D_CHECK_ARG(roi_feat_hi && roi_feat_lo && W_hi && W_lo && bias && out && ld_out >= C, "mv2d_qg_conv_pool_x3: bad args");
     MV2D_CHECK_ARG(((uintptr_t)roi_feat_hi & 15) == 0 && ((uintptr_t)roi_feat_lo & 15) == 0 && ((uintptr_t)W_hi & 15) == 0 && ((uintptr_t)W_lo & 15) == 0,
                    "mv2d_qg_conv_pool_x3: operands must be 16-byte aligned");
-    if (R == 0) return MV2D_OK;
-    hipLaunchKernelGGL(roi_conv_pool_s_kernel<true>, dim3(R), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)roi_feat_hi,
-                       (const unsigned short*)roi_feat_lo, (const unsigned short*)W_hi, (const unsigned short*)W_lo, bias, out, ld_out, R, roi_size);
-    MV2D_LAUNCH_CHECK();
     return MV2D_OK;
 }
 
+}  // namespace
+
 extern "C" int mv2d_qg_conv_pool(const void* roi_feat, const void* W, const float* bias, float* out, int ld_out, int R, void* stream) {
-    MV2D_CHECK_ARG(roi_feat && W && bias && out && ld_out >= C, "mv2d_qg_conv_pool: bad args");
-    MV2D_CHECK_ARG(((uintptr_t)roi_feat & 15) == 0 && ((uintptr_t)W & 15) == 0, "mv2d_qg_conv_pool: operands must be 16-byte aligned");
+    if (const int rc = check_pool_args(roi_feat, W, bias, out, ld_out)) return rc;
     if (R == 0) return MV2D_OK;
     // cell 48 of every RoI first (its term travels in out), then the pooling kernel on the other 48 cells
     hipLaunchKernelGGL((roi_conv_cell48_kernel<false, 64>), dim3(cdiv(R, 64), 2), dim3(512), 0, (hipStream_t)stream, (const unsigned short*)roi_feat,
@@ -561,15 +444,37 @@ extern "C" int mv2d_qg_conv_pool(const void* roi_feat, const void* W, const floa
 
 extern "C" int mv2d_qg_conv_pool_x3(const void* roi_feat_hi, const void* roi_feat_lo, const void* W_hi, const void* W_lo, const float* bias, float* out,
                                     int ld_out, int R, void* stream) {
-    MV2D_CHECK_ARG(roi_feat_hi && roi_feat_lo && W_hi && W_lo && bias && out && ld_out >= C, "mv2d_qg_conv_pool_x3: bad args");
-    MV2D_CHECK_ARG(((uintptr_t)roi_feat_hi & 15) == 0 && ((uintptr_t)roi_feat_lo & 15) == 0 && ((uintptr_t)W_hi & 15) == 0 && ((uintptr_t)W_lo & 15) == 0,
-                   "mv2d_qg_conv_pool_x3: operands must be 16-byte aligned");
+    if (const int rc = check_pool_x3_args(roi_feat_hi, roi_feat_lo, W_hi, W_lo, bias, out, ld_out)) return rc;
     if (R == 0) return MV2D_OK;
     hipLaunchKernelGGL((roi_conv_cell48_kernel<true, 32>), dim3(cdiv(R, 32), 2), dim3(512), 0, (hipStream_t)stream, (const unsigned short*)roi_feat_hi,
                        (const unsigned short*)roi_feat_lo, (const unsigned short*)W_hi, (const unsigned short*)W_lo, bias, out, ld_out, R);
     MV2D_LAUNCH_CHECK();
     hipLaunchKernelGGL(roi_conv_pool_x3_kernel, dim3(R), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)roi_feat_hi,
                        (const unsigned short*)roi_feat_lo, (const unsigned short*)W_hi, (const unsigned short*)W_lo, bias, out, ld_out, R);
+    MV2D_LAUNCH_CHECK();
+    return MV2D_OK;
+}
+
+// s x s cells per RoI, 1 <= s <= 14: the 7 x 7 kernels for s = 7, roi_conv_pool_s_kernel otherwise
+extern "C" int mv2d_qg_conv_pool_s(const void* roi_feat, const void* W, const float* bias, float* out, int ld_out, int R, int roi_size, void* stream) {
+    MV2D_CHECK_ARG(roi_size >= 1 && roi_size <= 14, "mv2d_qg_conv_pool_s: roi_size must be in [1, 14]");
+    if (roi_size == 7) return mv2d_qg_conv_pool(roi_feat, W, bias, out, ld_out, R, stream);
+    if (const int rc = check_pool_args(roi_feat, W, bias, out, ld_out)) return rc;
+    if (R == 0) return MV2D_OK;
+    hipLaunchKernelGGL(roi_conv_pool_s_kernel<false>, dim3(R), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)roi_feat, nullptr,
+                       (const unsigned short*)W, nullptr, bias, out, ld_out, R, roi_size);
+    MV2D_LAUNCH_CHECK();
+    return MV2D_OK;
+}
+
+extern "C" int mv2d_qg_conv_pool_x3_s(const void* roi_feat_hi, const void* roi_feat_lo, const void* W_hi, const void* W_lo, const float* bias, float* out,
+                                      int ld_out, int R, int roi_size, void* stream) {
+    MV2D_CHECK_ARG(roi_size >= 1 && roi_size <= 14, "mv2d_qg_conv_pool_x3_s: roi_size must be in [1, 14]");
+    if (roi_size == 7) return mv2d_qg_conv_pool_x3(roi_feat_hi, roi_feat_lo, W_hi, W_lo, bias, out, ld_out, R, stream);
+    if (const int rc = check_pool_x3_args(roi_feat_hi, roi_feat_lo, W_hi, W_lo, bias, out, ld_out)) return rc;
+    if (R == 0) return MV2D_OK;
+    hipLaunchKernelGGL(roi_conv_pool_s_kernel<true>, dim3(R), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)roi_feat_hi,
+                       (const unsigned short*)roi_feat_lo, (const unsigned short*)W_hi, (const unsigned short*)W_lo, bias, out, ld_out, R, roi_size);
     MV2D_LAUNCH_CHECK();
     return MV2D_OK;
 }

@@ -2,10 +2,10 @@
 // the flattened first fc (with_avg_pool=False), and the AvgPool2d(s) of a trunk without convs.
 //
 // roi_conv_cells_kernel: Conv2d(256, 256, 3, padding=1) + bias + ReLU on the s x s cells of a RoI, 1 <= s <= 14, that WRITES the cells instead of
-// pooling them.  The conv is the chunked window walk of roi_conv_pool_s_kernel (csrc/roiconv.hip; a copy: that file's instruction streams stay what
-// they are): one RoI per block, its cells in chunks of 64 output cells, a chunk stages the cell rows its taps read (<= 112) plus a zero row into LDS
-// and runs the 72 k-steps (weights fragment-major through a 4-deep register ring, k order (tap, channel), out-of-range neighbours -> the zero row):
-// the sums of a cell are bit for bit those the pooled kernels add up.  At s = 7 the single chunk holds the whole RoI (the resident shape).
+// pooling them.  The conv is the chunked window walk that roi_conv_pool_s_kernel (csrc/roiconv.hip) runs too: one text, csrc/roiconv_walk.inc
+// (described in csrc/roiconv_walk.h), included by both kernels, so the sums of a cell are those the pooled kernel adds up because they are the same
+// statements; tests/test_gpu_conv_walk_parent_bits.py holds both to the bytes the two spelled-out copies wrote.  One RoI per block, its cells in chunks
+// of 64 output cells; at s = 7 the single chunk holds the whole RoI (the resident shape).
 // X3: the cells come as key16 hi + lo pairs, three MFMAs per product (a_lo w_hi + a_hi w_lo + a_hi w_hi); otherwise key16 x key16.
 // Outputs (each optional): key16 hi rows [R, s*s, 256] (+ their lo halves: x ~ hi + lo, the split of split_k16x2) for a following conv, fp32 rows
 // [R, s*s, 256] = the cell-major flattening the first fc of an un-pooled trunk reads.
@@ -13,131 +13,30 @@
 //
 // avgpool_cells_kernel: mean over `cells` consecutive key16 rows (hi, or hi + lo) of 256 channels -> fp32.  cells = s * s: AvgPool2d(s) of the RoI
 // cells (num_shared_convs = 0); cells = 1: the fp32 copy of hi + lo rows (the flattened input of a trunk without convs).
-#include "common.h"
+#include "roiconv_walk.h"
 
 namespace {
-
-constexpr int C = 256;
-struct Frag { uint4 u; };
-typedef unsigned int cv_u32x4 __attribute__((ext_vector_type(4)));
-constexpr int GW_ROWS = 120, GW_ZERO = GW_ROWS - 1;     // LDS rows of a window (<= 112 cells) and the index of its zero row
 
 template <bool X3>
 __global__ __launch_bounds__(256, X3 ? 1 : 2) void roi_conv_cells_kernel(const unsigned short* __restrict__ feat_hi, const unsigned short* __restrict__ feat_lo,
                                                                         const unsigned short* __restrict__ Wh, const unsigned short* __restrict__ Wl,
                                                                         const float* __restrict__ bias, unsigned short* __restrict__ out_hi,
                                                                         unsigned short* __restrict__ out_lo, float* __restrict__ out_f32, int R, int s) {
-    constexpr int RING = 4, NIMG = X3 ? 2 : 1;
-    __shared__ __attribute__((aligned(16))) unsigned char xs[NIMG][GW_ROWS * C * 2];
-    __shared__ float bs[C];
-    const int roi = blockIdx.x;
-    if (roi >= R) return;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fr = lane & 15, fg = lane >> 4;
-    const int S2 = s * s;
-    const long long w_off = ((long long)(wave * 4) * 64 + lane) * 8;
-    constexpr int KS_STRIDE = 16 * 64 * 8, JT_STRIDE = 64 * 8;
-    bs[tid] = bias[tid];
-    for (int c0 = 0; c0 < S2; c0 += 64) {
-        const int last = min(c0 + 63, S2 - 1);
-        const int ylo = max(c0 / s - 1, 0), yhi = min(last / s + 1, s - 1);
-        const int wb = ylo * s, nwin = (yhi - ylo + 1) * s;          // window: cells [wb, wb + nwin) of the RoI, nwin <= 112
-        Frag wqh[RING][4], wql[RING][4];
-#pragma unroll
-        for (int p = 0; p < RING - 1; ++p)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                wqh[p][j].u = *reinterpret_cast<const uint4*>(Wh + w_off + p * KS_STRIDE + j * JT_STRIDE);
-                if (X3) wql[p][j].u = *reinterpret_cast<const uint4*>(Wl + w_off + p * KS_STRIDE + j * JT_STRIDE);
-            }
-        __syncthreads();                                 // the previous chunk's LDS reads are done
-        for (int c = tid; c < nwin * 32; c += 256) {
-            const int row = c >> 5, slot = c & 31;
-            const long long src = ((long long)roi * S2 + wb + row) * C + slot * 8;
-            const int dst = row * (C * 2) + ((slot ^ (row & 15)) << 4);
-            *reinterpret_cast<cv_u32x4*>(&xs[0][dst]) = *reinterpret_cast<const cv_u32x4*>(feat_hi + src);
-            if (X3) *reinterpret_cast<cv_u32x4*>(&xs[NIMG - 1][dst]) = *reinterpret_cast<const cv_u32x4*>(feat_lo + src);
-        }
-        if (tid < 32)
-#pragma unroll
-            for (int m = 0; m < NIMG; ++m) *reinterpret_cast<cv_u32x4*>(&xs[m][GW_ZERO * (C * 2) + (tid << 4)]) = cv_u32x4{0u, 0u, 0u, 0u};
-        // cell coordinates of the chunk's 4 row tiles for this lane (cell = c0 + 16 i + fr)
-        int cy[4], cx[4];
-        bool cv[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { const int cell = c0 + 16 * i + fr; cv[i] = cell < S2; cy[i] = cell / s; cx[i] = cell - cy[i] * s; }
-        f32x4_t acc[4][4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-        __syncthreads();
-#pragma unroll 1
-        for (int tap = 0; tap < 9; ++tap) {
-            const int dy = tap / 3 - 1, dx = tap - (tap / 3) * 3 - 1;
-            int src[4];
-#pragma unroll
-            for (int it = 0; it < 4; ++it) {
-                const int y = cy[it] + dy, x = cx[it] + dx;
-                const bool ok = cv[it] && y >= 0 && y < s && x >= 0 && x < s;
-                src[it] = ok ? y * s + x - wb : GW_ZERO;
-            }
-#pragma unroll
-            for (int sk = 0; sk < 8; ++sk) {
-                const int ks = tap * 8 + sk;
-                if (ks + RING - 1 < 72) {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        wqh[(sk + RING - 1) % RING][j].u = *reinterpret_cast<const uint4*>(Wh + w_off + (ks + RING - 1) * KS_STRIDE + j * JT_STRIDE);
-                        if (X3) wql[(sk + RING - 1) % RING][j].u = *reinterpret_cast<const uint4*>(Wl + w_off + (ks + RING - 1) * KS_STRIDE + j * JT_STRIDE);
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                Frag ah[4], al[4];
-#pragma unroll
-                for (int it = 0; it < 4; ++it) {
-                    const int off = src[it] * (C * 2) + (((4 * sk + fg) ^ (src[it] & 15)) << 4);
-                    ah[it].u = *reinterpret_cast<const uint4*>(&xs[0][off]);
-                    if (X3) al[it].u = *reinterpret_cast<const uint4*>(&xs[NIMG - 1][off]);
-                }
-                if (X3) {
-#pragma unroll
-                    for (int it = 0; it < 4; ++it)
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) acc[it][j] = mfma_k16_16x16x32(al[it].u, wqh[sk % RING][j].u, acc[it][j]);
-#pragma unroll
-                    for (int it = 0; it < 4; ++it)
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) acc[it][j] = mfma_k16_16x16x32(ah[it].u, wql[sk % RING][j].u, acc[it][j]);
-                }
-#pragma unroll
-                for (int it = 0; it < 4; ++it)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) acc[it][j] = mfma_k16_16x16x32(ah[it].u, wqh[sk % RING][j].u, acc[it][j]);
-            }
-        }
-        // bias + ReLU, one store per output form: lane holds cells c0 + 16 i + 4 fg + r of column 64 wave + 16 j + fr
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int n = wave * 64 + 16 * j + fr;
-            const float b = bs[n];
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int cell = c0 + 16 * i + 4 * fg + r;
-                    if (cell >= S2) continue;
-                    const float v = relu_f(acc[i][j][r] + b);
-                    const long long o = ((long long)roi * S2 + cell) * C + n;
-                    if (out_f32) out_f32[o] = v;
-                    if (out_hi) {
-                        unsigned int h, l;
-                        split_k16x2(v, v, h, l);
-                        out_hi[o] = (unsigned short)(h & 0xffffu);
-                        if (out_lo) out_lo[o] = (unsigned short)(l & 0xffffu);
-                    }
-                }
-        }
-    }
+// one store per output form
+#define ROI_CONV_WALK_CELL(val, cell, n, j)                            \
+    do {                                                               \
+        const float v = (val);                                         \
+        const long long o = ((long long)roi * S2 + (cell)) * C + (n);  \
+        if (out_f32) out_f32[o] = v;                                   \
+        if (out_hi) {                                                  \
+            unsigned int h, l;                                         \
+            split_k16x2(v, v, h, l);                                   \
+            out_hi[o] = (unsigned short)(h & 0xffffu);                 \
+            if (out_lo) out_lo[o] = (unsigned short)(l & 0xffffu);     \
+        }                                                              \
+    } while (0)
+#include "roiconv_walk.inc"
+#undef ROI_CONV_WALK_CELL
 }
 
 // one block per output row, one channel per thread; four partial sums (cells 4 k + a), added pairwise

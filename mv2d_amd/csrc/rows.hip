@@ -149,9 +149,29 @@ __global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const T* x, T* y, int
 
 // same, 64 channels x 64 positions per block with 16-byte accesses on both sides (needs HW % 4 == 0, Cn % 4 == 0):
 // every global row segment is 256 B, 4 loads + 4 stores in flight per thread instead of 4-byte accesses.
-__global__ __launch_bounds__(256) void nchw_to_nhwc64_kernel(const float* __restrict__ x, float* __restrict__ y, int V, int Cn, int HW) {
+// MASKED: the same transposition restricted to the positions somebody reads (round 5): mask [V * HW] bytes, 1 = the position is inside some RoI's
+// rectangle (the engine's roi_mask: every RoIAlign tap, every key position and every row the PE block reads lies there).  A 64-position block without a
+// listed position is skipped, a row is only written where the mask is set; the other rows of y keep whatever they held.  37 % (S path) / 50 % (T path)
+// of the rows are listed: the 277 MB written per 16-sample cfg2_s frame become ~100 MB.
+template <bool MASKED>
+__device__ __forceinline__ void nchw_to_nhwc64_body(const float* __restrict__ x, float* __restrict__ y, const unsigned char* __restrict__ mask, int V, int Cn,
+                                                    int HW) {
     __shared__ float tile[64][65];
+    __shared__ unsigned char m[64];
+    __shared__ int any;
     const int v = blockIdx.z, c0 = blockIdx.y * 64, p0 = blockIdx.x * 64;
+    if constexpr (MASKED) {
+        if (threadIdx.x == 0) any = 0;
+        __syncthreads();
+        if (threadIdx.x < 64) {
+            const int p = p0 + threadIdx.x;
+            const unsigned char b = p < HW ? mask[(long long)v * HW + p] : 0;
+            m[threadIdx.x] = b;
+            if (b) any = 1;
+        }
+        __syncthreads();
+        if (!any) return;
+    }
     const int tq = threadIdx.x & 15, ty = threadIdx.x >> 4;   // 16 x 16
     float4 in[4];
 #pragma unroll
@@ -168,52 +188,21 @@ __global__ __launch_bounds__(256) void nchw_to_nhwc64_kernel(const float* __rest
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int pl = ty + 16 * i, p = p0 + pl, c = c0 + tq * 4;
-        if (p < HW && c < Cn)
+        bool on = p < HW && c < Cn;
+        if constexpr (MASKED) on = on && m[pl];
+        if (on)
             *reinterpret_cast<float4*>(y + ((long long)v * HW + p) * Cn + c) =
                 make_float4(tile[tq * 4][pl], tile[tq * 4 + 1][pl], tile[tq * 4 + 2][pl], tile[tq * 4 + 3][pl]);
     }
 }
 
-// The same transposition restricted to the positions somebody reads (round 5): mask [V * HW] bytes, 1 = the position is inside some RoI's rectangle
-// (the engine's roi_mask: every RoIAlign tap, every key position and every row the PE block reads lies there).  A 64-position block without a listed
-// position is skipped, a row is only written where the mask is set; the other rows of y keep whatever they held.  37 % (S path) / 50 % (T path) of
-// the rows are listed: the 277 MB written per 16-sample cfg2_s frame become ~100 MB.
+__global__ __launch_bounds__(256) void nchw_to_nhwc64_kernel(const float* __restrict__ x, float* __restrict__ y, int V, int Cn, int HW) {
+    nchw_to_nhwc64_body<false>(x, y, nullptr, V, Cn, HW);
+}
+
 __global__ __launch_bounds__(256) void nchw_to_nhwc64_masked_kernel(const float* __restrict__ x, float* __restrict__ y, const unsigned char* __restrict__ mask,
                                                                    int V, int Cn, int HW) {
-    __shared__ float tile[64][65];
-    __shared__ unsigned char m[64];
-    __shared__ int any;
-    const int v = blockIdx.z, c0 = blockIdx.y * 64, p0 = blockIdx.x * 64;
-    if (threadIdx.x == 0) any = 0;
-    __syncthreads();
-    if (threadIdx.x < 64) {
-        const int p = p0 + threadIdx.x;
-        const unsigned char b = p < HW ? mask[(long long)v * HW + p] : 0;
-        m[threadIdx.x] = b;
-        if (b) any = 1;
-    }
-    __syncthreads();
-    if (!any) return;
-    const int tq = threadIdx.x & 15, ty = threadIdx.x >> 4;
-    float4 in[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = c0 + ty + 16 * i, p = p0 + tq * 4;
-        in[i] = (c < Cn && p < HW) ? *reinterpret_cast<const float4*>(x + ((long long)v * Cn + c) * HW + p) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        float* t = &tile[ty + 16 * i][tq * 4];
-        t[0] = in[i].x; t[1] = in[i].y; t[2] = in[i].z; t[3] = in[i].w;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int pl = ty + 16 * i, p = p0 + pl, c = c0 + tq * 4;
-        if (p < HW && c < Cn && m[pl])
-            *reinterpret_cast<float4*>(y + ((long long)v * HW + p) * Cn + c) =
-                make_float4(tile[tq * 4][pl], tile[tq * 4 + 1][pl], tile[tq * 4 + 2][pl], tile[tq * 4 + 3][pl]);
-    }
+    nchw_to_nhwc64_body<true>(x, y, mask, V, Cn, HW);
 }
 
 // The 64 x 64 transposition for 16-BIT maps (fp16 / bf16: 2-byte elements moved as they are), full and masked (MASKED: see above).  Needs HW % 4 == 0,

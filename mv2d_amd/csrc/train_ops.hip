@@ -213,39 +213,11 @@ extern "C" int mv2d_linear_bwd_x3(const float* x, const float* W, const float* y
 // ---------------------------------------------------------------------------------------------------------------------------------------
 namespace {
 
-// cols[(r, y, x), tap, c] = x[r, (y + ky - 1, x + kx - 1), c] or 0 outside the 7 x 7 cell grid
-__global__ __launch_bounds__(256) void im2col3x3_kernel(const float* __restrict__ in, float* __restrict__ cols, int R) {
-    const int pos = blockIdx.x * 4 + (threadIdx.x >> 6), c = 4 * (threadIdx.x & 63);
-    if (pos >= R * 49) return;
-    const int r = pos / 49, p = pos % 49, y = p / 7, x = p % 7;
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap) {
-        const int yy = y + tap / 3 - 1, xx = x + tap % 3 - 1;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (yy >= 0 && yy < 7 && xx >= 0 && xx < 7) v = *reinterpret_cast<const float4*>(in + ((long long)r * 49 + yy * 7 + xx) * 256 + c);
-        *reinterpret_cast<float4*>(cols + (long long)pos * 2304 + tap * 256 + c) = v;
-    }
-}
-// dx[r, (y, x), c] = sum over the taps of dcols[(r, y - ky + 1, x - kx + 1), tap, c] (fixed order)
-__global__ __launch_bounds__(256) void col2im3x3_kernel(const float* __restrict__ dcols, float* __restrict__ dx, int R) {
-    const int pos = blockIdx.x * 4 + (threadIdx.x >> 6), c = 4 * (threadIdx.x & 63);
-    if (pos >= R * 49) return;
-    const int r = pos / 49, p = pos % 49, y = p / 7, x = p % 7;
-    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap) {
-        const int yy = y - tap / 3 + 1, xx = x - tap % 3 + 1;
-        if (yy >= 0 && yy < 7 && xx >= 0 && xx < 7) {
-            const float4 v = *reinterpret_cast<const float4*>(dcols + ((long long)r * 49 + yy * 7 + xx) * 2304 + tap * 256 + c);
-            s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-        }
-    }
-    *reinterpret_cast<float4*>(dx + (long long)pos * 256 + c) = s;
-}
-
-// the same pair for s x s cells, 1 <= s <= 14 (the 7 x 7 kernels above stay the shipped instances)
-__global__ __launch_bounds__(256) void im2col3x3_s_kernel(const float* __restrict__ in, float* __restrict__ cols, int R, int s) {
-    const int S2 = s * s;
+// SB = 7: the 7 x 7 cell grid of the shipped instances at compile time; SB = 0: s x s cells, 1 <= s <= 14, at run time
+// cols[(r, y, x), tap, c] = x[r, (y + ky - 1, x + kx - 1), c] or 0 outside the s x s cell grid
+template <int SB>
+__device__ __forceinline__ void im2col3x3_body(const float* __restrict__ in, float* __restrict__ cols, int R, int s_rt) {
+    const int s = SB ? SB : s_rt, S2 = s * s;
     const int pos = blockIdx.x * 4 + (threadIdx.x >> 6), c = 4 * (threadIdx.x & 63);
     if (pos >= R * S2) return;
     const int r = pos / S2, p = pos % S2, y = p / s, x = p % s;
@@ -257,8 +229,10 @@ __global__ __launch_bounds__(256) void im2col3x3_s_kernel(const float* __restric
         *reinterpret_cast<float4*>(cols + (long long)pos * 2304 + tap * 256 + c) = v;
     }
 }
-__global__ __launch_bounds__(256) void col2im3x3_s_kernel(const float* __restrict__ dcols, float* __restrict__ dx, int R, int s) {
-    const int S2 = s * s;
+// dx[r, (y, x), c] = sum over the taps of dcols[(r, y - ky + 1, x - kx + 1), tap, c] (fixed order)
+template <int SB>
+__device__ __forceinline__ void col2im3x3_body(const float* __restrict__ dcols, float* __restrict__ dx, int R, int s_rt) {
+    const int s = SB ? SB : s_rt, S2 = s * s;
     const int pos = blockIdx.x * 4 + (threadIdx.x >> 6), c = 4 * (threadIdx.x & 63);
     if (pos >= R * S2) return;
     const int r = pos / S2, p = pos % S2, y = p / s, x = p % s;
@@ -272,6 +246,16 @@ __global__ __launch_bounds__(256) void col2im3x3_s_kernel(const float* __restric
         }
     }
     *reinterpret_cast<float4*>(dx + (long long)pos * 256 + c) = acc;
+}
+
+__global__ __launch_bounds__(256) void im2col3x3_kernel(const float* __restrict__ in, float* __restrict__ cols, int R) { im2col3x3_body<7>(in, cols, R, 7); }
+__global__ __launch_bounds__(256) void col2im3x3_kernel(const float* __restrict__ dcols, float* __restrict__ dx, int R) { col2im3x3_body<7>(dcols, dx, R, 7); }
+// the same pair for s x s cells (the 7 x 7 kernels above stay the shipped instances)
+__global__ __launch_bounds__(256) void im2col3x3_s_kernel(const float* __restrict__ in, float* __restrict__ cols, int R, int s) {
+    im2col3x3_body<0>(in, cols, R, s);
+}
+__global__ __launch_bounds__(256) void col2im3x3_s_kernel(const float* __restrict__ dcols, float* __restrict__ dx, int R, int s) {
+    col2im3x3_body<0>(dcols, dx, R, s);
 }
 
 }  // namespace

@@ -23,6 +23,7 @@ sys.path.insert(0, ROOT)
 from mv2d_amd.build import FLAGS, _hipcc  # noqa: E402
 
 LLVM = os.path.join(os.environ.get('ROCM_PATH', '/opt/rocm'), 'llvm', 'bin')
+ZERO_DWORD = 'v_cndmask_b32_e32 v0, s0, v0, vcc'             # what llvm-objdump makes of 0x00000000
 
 
 def kernels(src, tmp, tag):
@@ -41,6 +42,10 @@ def kernels(src, tmp, tag):
         if cur is None or not ins or ins == '...':           # (padding behind s_endpgm)
             continue
         cur.append(re.sub(r'<[^>]+>', '<sym>', ins))
+    for ins in out.values():             # (one dword of zero padding behind the last s_endpgm is printed as an instruction, not as `...`; whether it
+        end = max((i for i, s in enumerate(ins) if s == 's_endpgm'), default=len(ins) - 1)       # is there depends on where the next kernel starts)
+        if all(s == ZERO_DWORD for s in ins[end + 1:]):
+            del ins[end + 1:]
     names = subprocess.run(['c++filt'], input='\n'.join(out), capture_output=True, text=True, check=True).stdout.split('\n')
     res = {}
     for mangled, name in zip(out, names):
