@@ -605,6 +605,17 @@ int mv2d_frame_geometry(const float* rois, const double* viewK, const double* vi
                         float roi_size, float intr_scale, float min_size, const int* view_start, const double* trans, const float* lin,
                         const float* depths, int* match, int R, int V, int sample_size, int num_depth, int topk, int pad_h, int pad_w,
                         float depth_start, float iou_thr, float ratio, int max_per_view, void* zero_ptr, long long zero_bytes, void* stream);
+/* The two entries above with depth_start as a double, as the reference compares it (cam_z < depth_start in fp64), for 1 <= sample_size <= 8 and
+ * 1 <= num_depth <= 64 (anything else: -1 through mv2d_last_error); lin / depths stay caller-built tables (LID or uniform bins).  Up to 128
+ * samples per (RoI, view) with an fp32-representable depth_start launch the kernels of the entries above; more samples (up to 8 * 8 * 64 = 4096)
+ * or any other depth_start launch a second instance in which every thread walks samples tid, tid + 128, ...  The entries above forward here. */
+int mv2d_box_correlation_ex(const float* rois, const int* view_start, const double* trans, const float* lin, const float* depths,
+                            int* match, int R, int V, int sample_size, int num_depth, int topk, int pad_h, int pad_w,
+                            double depth_start, float iou_thr, float ratio, int max_per_view, void* stream);
+int mv2d_frame_geometry_ex(const float* rois, const double* viewK, const double* viewE, double* K_roi, float* intr, int ld_intr, float* minv,
+                           float roi_size, float intr_scale, float min_size, const int* view_start, const double* trans, const float* lin,
+                           const float* depths, int* match, int R, int V, int sample_size, int num_depth, int topk, int pad_h, int pad_w,
+                           double depth_start, float iou_thr, float ratio, int max_per_view, void* zero_ptr, long long zero_bytes, void* stream);
 
 long long mv2d_csr_workspace_bytes(int R, int V, int h, int w);
 

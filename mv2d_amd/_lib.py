@@ -123,6 +123,7 @@ SIGNATURES = {
     'mv2d_roi_align_s': (I, [P, P, P, P, P, P, P, I, I, I, I, F, I, P, I, P, P, P, P, P, I, P]),
     'mv2d_roi_align_fmt': (I, [P, P, P, P, P, P, P, I, I, I, I, F, I, P, I, P, P, P, P, P, I, I, P]),
     'mv2d_box_correlation': (I, [P, P, P, P, P, P, I, I, I, I, I, I, I, F, F, F, I, P]),
+    'mv2d_box_correlation_ex': (I, [P, P, P, P, P, P, I, I, I, I, I, I, I, D, F, F, I, P]),
     'mv2d_csr_workspace_bytes': (LL, [I, I, I, I]),
     'mv2d_mask_compact': (I, [P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, F, F, I, P]),
     'mv2d_roi_positions': (I, [P, P, P, P, P, P, P, I, I, I, I, F, F, P]),
@@ -131,6 +132,7 @@ SIGNATURES = {
     'mv2d_roi_positions_csr': (I, [P, P, P, P, P, P, P, I, I, I, I, F, F, P, P, P, P, I, I, P, I, P, P, P]),
     'mv2d_roi_positions_csr_s': (I, [P, P, P, P, P, P, P, I, I, I, I, F, F, P, P, P, P, I, I, P, I, P, P, I, P]),
     'mv2d_frame_geometry': (I, [P, P, P, P, P, I, P, F, F, F, P, P, P, P, P, I, I, I, I, I, I, I, F, F, F, I, P, LL, P]),
+    'mv2d_frame_geometry_ex': (I, [P, P, P, P, P, I, P, F, F, F, P, P, P, P, P, I, I, I, I, I, I, I, D, F, F, I, P, LL, P]),
     'mv2d_pe_inputs': (I, [P, P, I, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, P, P]),
     'mv2d_pe_inputs_fmt': (I, [P, P, I, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, P, I, P]),
     'mv2d_pe_frustum_f32': (I, [P, P, I, P, P, P, P, P, I, I, I, I, P, P]),

@@ -9,7 +9,7 @@ frame with the SAME operations and dtypes, then shipped to the GPU in one pinned
 * frustum pixel-centre / LID depth tables fp64 (MU/pe.py:93-104),
 * padding mask (nearest interpolation, RH/mv2d_t_head.py:69-76) and the normalised (view, y, x) cumsum embeds of
   SinePositionalEncoding3D (MU/positional_encoding.py:62-77),
-* constant tables: linspace(0,1,4), LID depths of BoxCorrelation (RH/utils/box_correlation.py:198,221-225),
+* constant tables: linspace(0,1,sample_size), LID or uniform depths of BoxCorrelation (RH/utils/box_correlation.py:198,221-227),
   dim_t = 10000 ** (2*(i//2)/128) (MU/pe.py:24-25).
 """
 import math
@@ -19,11 +19,16 @@ import torch
 import torch.nn.functional as F
 
 
-def constant_tables(sample_size=4, num_depth=8, depth_start=0.5, depth_end=70.0, num_pos_feats=128, temperature=10000):
+def constant_tables(sample_size=4, num_depth=8, depth_start=0.5, depth_end=70.0, num_pos_feats=128, temperature=10000, lid=True):
+    """lin / depths: BoxCorrelation's sample grid and depth bins (fp32, RH/utils/box_correlation.py:198,221-227) -- lid: its ``LID`` key, True =
+    linear-increasing bins, False = torch.linspace(depth_start, depth_end, num_depth); dim_t: the sine embedding's periods."""
     lin = torch.linspace(0, 1, sample_size)
-    index = torch.arange(0, num_depth, 1).float()
-    bin_size = (depth_end - depth_start) / (num_depth * (1 + num_depth))
-    depths = depth_start + bin_size * index * (index + 1)
+    if lid:
+        index = torch.arange(0, num_depth, 1).float()
+        bin_size = (depth_end - depth_start) / (num_depth * (1 + num_depth))
+        depths = depth_start + bin_size * index * (index + 1)
+    else:
+        depths = torch.linspace(depth_start, depth_end, num_depth)
     dim_t = torch.arange(num_pos_feats, dtype=torch.float32)
     dim_t = temperature ** (2 * (dim_t // 2) / num_pos_feats)
     return dict(lin=lin.contiguous(), depths=depths.contiguous(), dim_t=dim_t.contiguous())

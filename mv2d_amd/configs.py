@@ -122,6 +122,29 @@ def _set_query_generator(d, query_generator):
     return d
 
 
+BOX_CORRELATION_KEYS = ('sample_size', 'num_depth', 'depth_start', 'depth_end', 'LID', 'correlation_mode', 'expand_stride', 'force_cpu')
+
+
+def _set_box_correlation(d, box_correlation, intrins_feat_scale):
+    # keys of the reference BoxCorrelation (RH/utils/box_correlation.py:12-13) laid over the shipped subtree, and the head's own ``intrins_feat_scale``
+    # (RH/mv2d_head.py).  ops.check_box_correlation / check_intrins_feat_scale list what is accepted.  The shipped configs leave the five sampling
+    # keys and the scale at the classes' defaults (no key): a key left at that value is not added, so the defaults here give exactly that dict
+    from . import ops
+    bc = dict(box_correlation or {})
+    unknown = sorted(set(bc) - set(BOX_CORRELATION_KEYS))
+    if unknown:
+        raise ValueError(f'configs: box_correlation has no key {unknown[0]!r} (its keys: {", ".join(BOX_CORRELATION_KEYS)})')
+    keys = {k: bc.get(k, v) for k, v in ops.BOX_CORR_DEFAULTS.items()}
+    ops.check_box_correlation(who='configs', **keys)
+    for k, v in bc.items():
+        if k in ops.BOX_CORR_DEFAULTS and v == ops.BOX_CORR_DEFAULTS[k] and k not in d['box_correlation']:
+            continue
+        d['box_correlation'][k] = v
+    if ops.check_intrins_feat_scale(intrins_feat_scale, 'configs') != 0.1:
+        d['intrins_feat_scale'] = intrins_feat_scale
+    return d
+
+
 def _set_reg_layer(d, group_reg_dims):
     # ``bbox_head.use_reg_layer`` / ``group_reg_dims`` of the reference head; None leaves the shipped Sequential regression branches (no key added)
     if group_reg_dims is not None:
@@ -150,7 +173,8 @@ def _set_decoder_shape(d, num_layers, feedforward_channels):
 
 
 def roi_head_cfg_s(num_classes=10, roi_size=ROI_SIZE, reg_layer_dims=None, depth_num=64, depth_start=1, position_range=None, query_generator=None,
-                   num_reg_fcs=2, with_fpe=True, no_sin_enc=False, adapt_pos3d=True, LID=True, num_layers=6, feedforward_channels=2048):
+                   num_reg_fcs=2, with_fpe=True, no_sin_enc=False, adapt_pos3d=True, LID=True, num_layers=6, feedforward_channels=2048,
+                   box_correlation=None, intrins_feat_scale=0.1):
     """CFG-S:40-121 (MV2D-S single frame); ``num_classes`` sets ``bbox_head.num_classes`` and ``bbox_head.bbox_coder.num_classes``,
     ``roi_size`` sets ``bbox_roi_extractor.roi_layer.output_size`` and ``query_generator.roi_feat_size``; ``reg_layer_dims`` (a tuple of
     group widths) sets ``bbox_head.use_reg_layer=True`` with that ``group_reg_dims``; ``depth_num`` (a multiple of 8 in [8, 80]), ``depth_start``
@@ -159,25 +183,30 @@ def roi_head_cfg_s(num_classes=10, roi_size=ROI_SIZE, reg_layer_dims=None, depth
     or 3) sets ``bbox_head.num_reg_fcs``, alone or together with ``reg_layer_dims`` (2, the head's default: no key); ``with_fpe``, ``no_sin_enc``,
     ``adapt_pos3d`` and ``LID`` set the ``pe`` keys of the same names (a key left at the shipped value is not added; ``adapt_pos3d=False`` needs
     ``no_sin_enc=True``); ``num_layers`` (1 to 8) and ``feedforward_channels`` (a multiple of 64 in [64, 4096]) set
-    ``bbox_head.transformer.decoder.num_layers`` and ``...transformerlayers.feedforward_channels``."""
+    ``bbox_head.transformer.decoder.num_layers`` and ``...transformerlayers.feedforward_channels``; ``box_correlation`` (a dict of the reference
+    BoxCorrelation's own keys: ``sample_size`` 1 to 8, ``num_depth`` 1 to 64, ``depth_start`` < ``depth_end``, ``LID``) is laid over the
+    ``box_correlation`` subtree and ``intrins_feat_scale`` sets the head's key of that name (a key left at the shipped value is not added; an
+    unknown ``box_correlation`` key raises ``ValueError``)."""
     d = dict(type='MV2DSHead', use_denoise=False)
     d.update(_common(with_cp=False))
     d['box_correlation'] = dict(correlation_mode='topk_matched:1:0.0:0.0')
     d = _set_query_generator(_set_pe_options(_set_pe_depth(d, depth_num, depth_start, position_range), with_fpe, no_sin_enc, adapt_pos3d, LID), query_generator)
-    d = _set_decoder_shape(d, num_layers, feedforward_channels)
+    d = _set_box_correlation(_set_decoder_shape(d, num_layers, feedforward_channels), box_correlation, intrins_feat_scale)
     return copy.deepcopy(_set_num_reg_fcs(_set_reg_layer(_set_roi_size(_set_num_classes(d, num_classes), roi_size), reg_layer_dims), num_reg_fcs))
 
 
 def roi_head_cfg_t(num_classes=10, roi_size=ROI_SIZE, reg_layer_dims=None, depth_num=64, depth_start=1, position_range=None, query_generator=None,
-                   num_reg_fcs=2, with_fpe=True, no_sin_enc=False, adapt_pos3d=True, LID=True, num_layers=6, feedforward_channels=2048):
+                   num_reg_fcs=2, with_fpe=True, no_sin_enc=False, adapt_pos3d=True, LID=True, num_layers=6, feedforward_channels=2048,
+                   box_correlation=None, intrins_feat_scale=0.1):
     """CFG-T:40-125 (MV2D-T two frames); ``num_classes``, ``roi_size``, ``reg_layer_dims``, the three ``pe`` keys, ``query_generator``, ``num_reg_fcs``
-    the PE's four switches and the decoder's ``num_layers`` / ``feedforward_channels`` as in ``roi_head_cfg_s``."""
+    the PE's four switches, the decoder's ``num_layers`` / ``feedforward_channels``, ``box_correlation`` and ``intrins_feat_scale`` as in
+    ``roi_head_cfg_s``."""
     d = dict(type='MV2DTHead', use_denoise=True, neg_bbox_loss=True,
              denoise_noise_scale=1.25, denoise_split=0.6)
     d.update(_common(with_cp=True))
     d['box_correlation'] = dict(expand_stride=2, correlation_mode='topk_matched:20:0.0:0.0')
     d = _set_query_generator(_set_pe_options(_set_pe_depth(d, depth_num, depth_start, position_range), with_fpe, no_sin_enc, adapt_pos3d, LID), query_generator)
-    d = _set_decoder_shape(d, num_layers, feedforward_channels)
+    d = _set_box_correlation(_set_decoder_shape(d, num_layers, feedforward_channels), box_correlation, intrins_feat_scale)
     return copy.deepcopy(_set_num_reg_fcs(_set_reg_layer(_set_roi_size(_set_num_classes(d, num_classes), roi_size), reg_layer_dims), num_reg_fcs))
 
 

@@ -333,6 +333,49 @@ __global__ __launch_bounds__(256) void roi_align_bwd_s_kernel(const float* __res
 // ------------------------------------------------------------------------------------------------
 constexpr int MAX_PER_VIEW = 1024;
 
+// The part of box_corr_block behind its two early exits, as a function of its own for the second instance (box_corr_wide_block): each thread
+// brings the rectangle of its own valid samples (sentinels +-1e4 without one); block reduction of the rectangle, IoU against every RoI of
+// view b, rank and keep rule.  box_corr_block keeps its own copy: calling this from it changes the shipped kernels' instruction streams
+// (tools/cmp_kernel_isa.py: 971 -> 985 instructions in box_corr_kernel), and the shipped keys must launch what they always launched.
+__device__ __forceinline__ void box_corr_rank(float umin, float vmin, float umax, float vmax, const float* __restrict__ rois, int start, int nb,
+                                              int* __restrict__ out, int topk, float iou_thr, float ratio) {
+    __shared__ float siou[MAX_PER_VIEW];
+    __shared__ float red[4][2];
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        umin = fminf(umin, __shfl_xor(umin, o, 64)); vmin = fminf(vmin, __shfl_xor(vmin, o, 64));
+        umax = fmaxf(umax, __shfl_xor(umax, o, 64)); vmax = fmaxf(vmax, __shfl_xor(vmax, o, 64));
+    }
+    if ((tid & 63) == 0) { red[0][tid >> 6] = umin; red[1][tid >> 6] = vmin; red[2][tid >> 6] = umax; red[3][tid >> 6] = vmax; }
+    __syncthreads();
+    const float a0 = fminf(red[0][0], red[0][1]), a1 = fminf(red[1][0], red[1][1]);
+    const float a2 = fmaxf(red[2][0], red[2][1]), a3 = fmaxf(red[3][0], red[3][1]);
+    // ---- IoU against every RoI of view b (:385-398)
+    for (int m = tid; m < nb; m += 128) {
+        const float* mb = rois + (long long)(start + m) * 5;
+        const float xs = fmaxf(a0, mb[1]), ys = fmaxf(a1, mb[2]), xe = fminf(a2, mb[3]), ye = fminf(a3, mb[4]);
+        const float w = fmaxf(xe - xs, 0.f), h = fmaxf(ye - ys, 0.f);
+        const float inter = w * h;
+        const float area_a = (a2 - a0) * (a3 - a1), area_b = (mb[3] - mb[1]) * (mb[4] - mb[2]);
+        const float uni = area_a + area_b - inter;
+        siou[m] = inter / (uni + 1e-4f);
+    }
+    __syncthreads();
+    // ---- top-k by IoU, descending, stable (lower index first among equals); keep rule of :374
+    float top = 0.f;
+    for (int j = 0; j < nb; ++j) top = fmaxf(top, siou[j]);
+    for (int m = tid; m < nb; m += 128) {
+        const float x = siou[m];
+        int rank = 0;
+        for (int j = 0; j < nb; ++j) { const float y = siou[j]; rank += (y > x || (y == x && j < m)) ? 1 : 0; }
+        if (rank < topk) {
+            const bool keep = ((x > ratio * top) || (x > iou_thr)) && (x > 0.f);
+            out[rank] = keep ? (start + m) : -1;
+        }
+    }
+}
+
 struct BoxCorrArgs {
     const float* rois; const int* view_start; const double* trans; const float* lin; const float* depths; int* match;
     int V, ss, D, topk; float img_w_m1, img_h_m1, depth_start, iou_thr, ratio;
@@ -438,6 +481,75 @@ __device__ __forceinline__ void box_corr_block(int r, int bl, const BoxCorrArgs&
 
 __global__ __launch_bounds__(128) void box_corr_kernel(BoxCorrArgs A) { box_corr_block(blockIdx.x, blockIdx.y, A); }
 
+// The second instance: any ns = ss * ss * D (the entries bound it at 8 * 8 * 64 = 4096) and depth_start as a double, as the reference compares
+// it (:247).  Thread t walks the samples t, t + 128, ... and keeps in registers whether one was valid, whether a valid one fell inside a RoI of
+// view b, and the rectangle of its valid samples: no per-sample LDS, no scratch.  Per sample the arithmetic is box_corr_block's, the exits
+// are block-uniform (flags in LDS, one barrier for both), box_corr_rank does the rest.  Launched where box_corr_block cannot serve: ns > 128 or
+// a depth_start that is no fp32 number.
+__device__ __forceinline__ void box_corr_wide_block(int r, int bl, const BoxCorrArgs& A, double depth_start) {
+    const float* __restrict__ rois = A.rois; const int* __restrict__ view_start = A.view_start; const double* __restrict__ trans = A.trans;
+    const float* __restrict__ lin = A.lin; const float* __restrict__ depths = A.depths; int* __restrict__ match = A.match;
+    const int V = A.V, ss = A.ss, D = A.D, topk = A.topk;
+    const double img_w_m1 = (double)A.img_w_m1, img_h_m1 = (double)A.img_h_m1;
+    __shared__ int flag[2];
+    const int tid = threadIdx.x;
+    int* out = match + ((long long)r * V + bl) * topk;
+    for (int i = tid; i < topk; i += 128) out[i] = -1;
+    const float* rb = rois + r * 5;
+    const int a = (int)rb[0];
+    const int b = (a / V) * V + bl;                        // destination view (global index)
+    const int start = view_start[b], nb = view_start[b + 1] - start;
+    if (a == b || nb == 0) return;
+    if (tid < 2) flag[tid] = 0;
+    __syncthreads();
+    const int ns = ss * ss * D;
+    const float x0 = rb[1], y0 = rb[2], wbox = rb[3] - rb[1], hbox = rb[4] - rb[2];
+    double T[12];
+    {
+        const double* Tg = trans + ((long long)a * V + bl) * 16;
+#pragma unroll
+        for (int i = 0; i < 12; ++i) T[i] = Tg[i];
+    }
+    bool any = false, hit = false;
+    float umin = 1e4f, vmin = 1e4f, umax = -1e4f, vmax = -1e4f;
+    for (int s = tid; s < ns; s += 128) {
+        const int pt = s / D, dk = s - pt * D;
+        const int iy = pt / ss, ix = pt - iy * ss;
+        const float x = x0 + wbox * lin[ix], y = y0 + hbox * lin[iy];
+        const double d = (double)depths[dk];
+        const double hx = (double)x * d, hy = (double)y * d;
+        double cam[3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            double acc = 0.0;
+            acc = acc + T[i * 4 + 0] * hx;
+            acc = acc + T[i * 4 + 1] * hy;
+            acc = acc + T[i * 4 + 2] * d;
+            acc = acc + T[i * 4 + 3] * 1.0;
+            cam[i] = acc;
+        }
+        const double zc = cam[2] < 1e-2 ? 1e-2 : cam[2];      // clamp_min(1e-2); NaN stays NaN like torch
+        const double u = cam[0] / zc, vv = cam[1] / zc;
+        const bool valid = !(cam[2] < depth_start) && (0.0 <= u) && (u <= img_w_m1) && (0.0 <= vv) && (vv <= img_h_m1);
+        if (!valid) continue;
+        const float u32 = (float)u, v32 = (float)vv;
+        any = true;
+        umin = fminf(umin, u32); vmin = fminf(vmin, v32); umax = fmaxf(umax, u32); vmax = fmaxf(vmax, v32);
+        // ---- inside any RoI of view b? (closed intervals, :299-300)  One hit per thread is enough.
+        for (int m = 0; m < nb && !hit; ++m) {
+            const float* mb = rois + (long long)(start + m) * 5;
+            hit = (mb[1] <= u32) && (u32 <= mb[3]) && (mb[2] <= v32) && (v32 <= mb[4]);
+        }
+    }
+    if (any) flag[0] = 1;
+    if (hit) flag[1] = 1;
+    __syncthreads();
+    if (!flag[0] || !flag[1]) return;
+    box_corr_rank(umin, vmin, umax, vmax, rois, start, nb, out, topk, A.iou_thr, A.ratio);
+}
+
+__global__ __launch_bounds__(128) void box_corr_wide_kernel(BoxCorrArgs A, double depth_start) { box_corr_wide_block(blockIdx.x, blockIdx.y, A, depth_start); }
+
 // The feature-independent geometry of a frame in ONE launch (round 4: a one-sample frame is bound by its NUMBER of kernels, 4.6 us per
 // dispatch): blocks (r < R, b) = box correlation of RoI r with view b; then, in row y = 0, ceil(R / 128) blocks of per-RoI cameras
 // (box_params_row) and the blocks that clear the per-frame flag / mask bytes (the engine's zbuf).  The three parts are independent.
@@ -465,6 +577,31 @@ __global__ __launch_bounds__(128) void frame_geometry_kernel(FrameGeoArgs G) {
         const long long i = z0 + k * 128 + threadIdx.x;
         if (i < G.zero_vec16) G.zero_ptr[i] = make_uint4(0u, 0u, 0u, 0u);
     }
+}
+
+// the blocks behind the correlation blocks (bx >= G.R) for the second instance: per-RoI cameras and clearing, frame_geometry_kernel's own lines
+// (which stay in that kernel: moving them out re-schedules its instruction stream)
+__device__ __forceinline__ void frame_geometry_rest(const FrameGeoArgs& G, int bx) {
+    if (blockIdx.y != 0) return;
+    const int np = (G.R + 127) / 128;
+    if (bx < G.R + np) {
+        box_params_row((bx - G.R) * 128 + threadIdx.x, G.corr.rois, G.viewK, G.viewE, G.K_roi, G.intr, G.ld_intr, G.minv, G.R, G.roi_size, G.intr_scale,
+                       G.min_size);
+        return;
+    }
+    const long long z0 = (long long)(bx - G.R - np) * GEO_ZERO_PER_BLOCK;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const long long i = z0 + k * 128 + threadIdx.x;
+        if (i < G.zero_vec16) G.zero_ptr[i] = make_uint4(0u, 0u, 0u, 0u);
+    }
+}
+
+// the same launch with the second instance of the correlation block (box_corr_wide_block)
+__global__ __launch_bounds__(128) void frame_geometry_wide_kernel(FrameGeoArgs G, double depth_start) {
+    const int bx = blockIdx.x;
+    if (bx < G.R) { box_corr_wide_block(bx, blockIdx.y, G.corr, depth_start); return; }
+    frame_geometry_rest(G, bx);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1364,28 +1501,46 @@ extern "C" int mv2d_roi_align_bwd(const float* grad_out, const float* rois, floa
     return mv2d_roi_align_bwd_s(grad_out, rois, grad_map, index, R, H, W, channels, spatial_scale, sampling_ratio, 7, stream);
 }
 
-extern "C" int mv2d_box_correlation(const float* rois, const int* view_start, const double* trans, const float* lin, const float* depths,
-                                    int* match, int R, int V, int sample_size, int num_depth, int topk, int pad_h, int pad_w,
-                                    float depth_start, float iou_thr, float ratio, int max_per_view, void* stream) {
+// the launch rule of the two correlation instances: the first takes at most 128 samples per (RoI, view) and compares with an fp32 depth_start
+static inline bool box_corr_narrow(int sample_size, int num_depth, double depth_start) {
+    return sample_size * sample_size * num_depth <= 128 && (double)(float)depth_start == depth_start;
+}
+
+extern "C" int mv2d_box_correlation_ex(const float* rois, const int* view_start, const double* trans, const float* lin, const float* depths,
+                                       int* match, int R, int V, int sample_size, int num_depth, int topk, int pad_h, int pad_w,
+                                       double depth_start, float iou_thr, float ratio, int max_per_view, void* stream) {
     MV2D_CHECK_ARG(rois && view_start && trans && lin && depths && match, "mv2d_box_correlation: null pointer");
-    MV2D_CHECK_ARG(sample_size * sample_size * num_depth <= 128, "mv2d_box_correlation: sample_size^2*num_depth must be <= 128");
+    MV2D_CHECK_ARG(sample_size >= 1 && sample_size <= 8, "mv2d_box_correlation: sample_size must be in [1, 8]");
+    MV2D_CHECK_ARG(num_depth >= 1 && num_depth <= 64, "mv2d_box_correlation: num_depth must be in [1, 64]");
     MV2D_CHECK_ARG(max_per_view <= MAX_PER_VIEW && topk >= 1, "mv2d_box_correlation: too many RoIs in one view (max 1024)");
     if (R == 0) return MV2D_OK;
-    const BoxCorrArgs A{rois, view_start, trans, lin, depths, match, V, sample_size, num_depth, topk, (float)(pad_w - 1), (float)(pad_h - 1), depth_start,
-                        iou_thr, ratio};
-    hipLaunchKernelGGL(box_corr_kernel, dim3(R, V), dim3(128), 0, (hipStream_t)stream, A);
+    const BoxCorrArgs A{rois, view_start, trans, lin, depths, match, V, sample_size, num_depth, topk, (float)(pad_w - 1), (float)(pad_h - 1),
+                        (float)depth_start, iou_thr, ratio};
+    if (box_corr_narrow(sample_size, num_depth, depth_start))
+        hipLaunchKernelGGL(box_corr_kernel, dim3(R, V), dim3(128), 0, (hipStream_t)stream, A);
+    else
+        hipLaunchKernelGGL(box_corr_wide_kernel, dim3(R, V), dim3(128), 0, (hipStream_t)stream, A, depth_start);
     MV2D_LAUNCH_CHECK();
     return MV2D_OK;
 }
 
-// mv2d_box_params + mv2d_box_correlation + the clearing of `zero_bytes` bytes at zero_ptr (16-byte aligned, a multiple of 16; may be NULL)
+extern "C" int mv2d_box_correlation(const float* rois, const int* view_start, const double* trans, const float* lin, const float* depths,
+                                    int* match, int R, int V, int sample_size, int num_depth, int topk, int pad_h, int pad_w,
+                                    float depth_start, float iou_thr, float ratio, int max_per_view, void* stream) {
+    return mv2d_box_correlation_ex(rois, view_start, trans, lin, depths, match, R, V, sample_size, num_depth, topk, pad_h, pad_w, (double)depth_start,
+                                   iou_thr, ratio, max_per_view, stream);
+}
+
+// mv2d_box_params + mv2d_box_correlation_ex + the clearing of `zero_bytes` bytes at zero_ptr (16-byte aligned, a multiple of 16; may be NULL)
 // in ONE launch: see frame_geometry_kernel
-extern "C" int mv2d_frame_geometry(const float* rois, const double* viewK, const double* viewE, double* K_roi, float* intr, int ld_intr, float* minv,
-                                   float roi_size, float intr_scale, float min_size, const int* view_start, const double* trans, const float* lin,
-                                   const float* depths, int* match, int R, int V, int sample_size, int num_depth, int topk, int pad_h, int pad_w,
-                                   float depth_start, float iou_thr, float ratio, int max_per_view, void* zero_ptr, long long zero_bytes, void* stream) {
+extern "C" int mv2d_frame_geometry_ex(const float* rois, const double* viewK, const double* viewE, double* K_roi, float* intr, int ld_intr, float* minv,
+                                      float roi_size, float intr_scale, float min_size, const int* view_start, const double* trans, const float* lin,
+                                      const float* depths, int* match, int R, int V, int sample_size, int num_depth, int topk, int pad_h, int pad_w,
+                                      double depth_start, float iou_thr, float ratio, int max_per_view, void* zero_ptr, long long zero_bytes,
+                                      void* stream) {
     MV2D_CHECK_ARG(rois && viewK && viewE && intr && minv && ld_intr >= 16 && view_start && trans && lin && depths && match, "mv2d_frame_geometry: null pointer");
-    MV2D_CHECK_ARG(sample_size * sample_size * num_depth <= 128, "mv2d_frame_geometry: sample_size^2*num_depth must be <= 128");
+    MV2D_CHECK_ARG(sample_size >= 1 && sample_size <= 8, "mv2d_frame_geometry: sample_size must be in [1, 8]");
+    MV2D_CHECK_ARG(num_depth >= 1 && num_depth <= 64, "mv2d_frame_geometry: num_depth must be in [1, 64]");
     MV2D_CHECK_ARG(max_per_view <= MAX_PER_VIEW && topk >= 1, "mv2d_frame_geometry: too many RoIs in one view (max 1024)");
     MV2D_CHECK_ARG(zero_bytes >= 0 && (zero_bytes % 16) == 0 && ((uintptr_t)zero_ptr & 15) == 0 && (zero_ptr || zero_bytes == 0),
                    "mv2d_frame_geometry: the region to clear must be 16-byte aligned and a multiple of 16 bytes");
@@ -1398,12 +1553,26 @@ extern "C" int mv2d_frame_geometry(const float* rois, const double* viewK, const
         }
         return MV2D_OK;
     }
-    FrameGeoArgs G{{rois, view_start, trans, lin, depths, match, V, sample_size, num_depth, topk, (float)(pad_w - 1), (float)(pad_h - 1), depth_start,
-                    iou_thr, ratio}, viewK, viewE, K_roi, intr, ld_intr, minv, roi_size, intr_scale, min_size, (uint4*)zero_ptr, zero_bytes / 16, R};
+    FrameGeoArgs G{{rois, view_start, trans, lin, depths, match, V, sample_size, num_depth, topk, (float)(pad_w - 1), (float)(pad_h - 1),
+                    (float)depth_start, iou_thr, ratio}, viewK, viewE, K_roi, intr, ld_intr, minv, roi_size, intr_scale, min_size, (uint4*)zero_ptr,
+                   zero_bytes / 16, R};
     const int nz = (int)((zero_bytes / 16 + GEO_ZERO_PER_BLOCK - 1) / GEO_ZERO_PER_BLOCK);
-    hipLaunchKernelGGL(frame_geometry_kernel, dim3(R + cdiv(R, 128) + nz, V), dim3(128), 0, (hipStream_t)stream, G);
+    const dim3 grid(R + cdiv(R, 128) + nz, V);
+    if (box_corr_narrow(sample_size, num_depth, depth_start))
+        hipLaunchKernelGGL(frame_geometry_kernel, grid, dim3(128), 0, (hipStream_t)stream, G);
+    else
+        hipLaunchKernelGGL(frame_geometry_wide_kernel, grid, dim3(128), 0, (hipStream_t)stream, G, depth_start);
     MV2D_LAUNCH_CHECK();
     return MV2D_OK;
+}
+
+extern "C" int mv2d_frame_geometry(const float* rois, const double* viewK, const double* viewE, double* K_roi, float* intr, int ld_intr, float* minv,
+                                   float roi_size, float intr_scale, float min_size, const int* view_start, const double* trans, const float* lin,
+                                   const float* depths, int* match, int R, int V, int sample_size, int num_depth, int topk, int pad_h, int pad_w,
+                                   float depth_start, float iou_thr, float ratio, int max_per_view, void* zero_ptr, long long zero_bytes, void* stream) {
+    return mv2d_frame_geometry_ex(rois, viewK, viewE, K_roi, intr, ld_intr, minv, roi_size, intr_scale, min_size, view_start, trans, lin, depths, match,
+                                  R, V, sample_size, num_depth, topk, pad_h, pad_w, (double)depth_start, iou_thr, ratio, max_per_view, zero_ptr,
+                                  zero_bytes, stream);
 }
 
 // words of the per-query key bitmask: the cells of one sample (V views) plus one word of slack for a window that starts mid-word

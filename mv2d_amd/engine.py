@@ -50,7 +50,8 @@ class HeadEngine:
                  post_range=(-61.2, -61.2, -10.0, 61.2, 61.2, 10.0), depth_num=64, stride=16, col_cap_per_query=2048,
                  iou_thr=0.0, ratio=0.0, masked_row='nan', exact=None, num_classes=10, roi_size=7, use_reg_layer=False,
                  group_reg_dims=(2, 2, 1, 1, 2, 2), depth_start=1, position_range=None, query_generator=None, num_reg_fcs=2,
-                 with_fpe=True, no_sin_enc=False, adapt_pos3d=True, LID=True, feedforward_channels=2048):
+                 with_fpe=True, no_sin_enc=False, adapt_pos3d=True, LID=True, feedforward_channels=2048, sample_size=4, num_depth=8,
+                 corr_depth_start=0.5, corr_depth_end=70, corr_LID=True, intrins_feat_scale=0.1):
         assert kind in ('S', 'T')
         self.kind = kind
         self.dev = torch.device(device)
@@ -106,7 +107,15 @@ class HeadEngine:
         self.pc_range_h = torch.tensor(pc_range, dtype=F32)
         self.post_range_h = torch.tensor(post_range, dtype=F32)
         self.post_range_h64 = torch.tensor(post_range, dtype=torch.float64)
-        self.const = {k: v.to(self.dev) for k, v in calib.constant_tables().items()}
+        # box_correlation's sampling keys (RH/utils/box_correlation.py:12-21; ops.check_box_correlation: the accepted values) and the head's
+        # intrins_feat_scale.  Fixed per engine, like depth_num: self.const holds their sample grid and depth table, the frame launch gets them with
+        # every frame.  The shipped values build and launch what they always did; more than 128 samples per (RoI, view), or a depth_start that is no
+        # fp32 number, launch the second instance of the correlation block (csrc/geometry.hip).
+        self.sample_size, self.num_depth, self.corr_depth_start, self.corr_depth_end, self.corr_LID = ops.check_box_correlation(
+            sample_size, num_depth, corr_depth_start, corr_depth_end, corr_LID, 'HeadEngine')
+        self.intrins_feat_scale = ops.check_intrins_feat_scale(intrins_feat_scale, 'HeadEngine')
+        self.const = {k: v.to(self.dev) for k, v in calib.constant_tables(self.sample_size, self.num_depth, self.corr_depth_start, self.corr_depth_end,
+                                                                          lid=self.corr_LID).items()}
         self._ws = {}
         self._ws_base = {}
         self._shape_cache = {}
@@ -782,7 +791,8 @@ class HeadEngine:
         # bytes: one launch (round 4; a one-sample frame is bound by its NUMBER of kernels)
         o.frame_geometry(rois, T['viewK'], T['viewE'], ws['intr'], ws['ld_intr'], ws['minv'], ws['view_start'], T['trans'], self.const['lin'],
                          self.const['depths'], ws['match'], Vg, self.topk, sc['pad_h'], sc['pad_w'], sc['max_per_view'], iou_thr=self.iou_thr,
-                         ratio=self.ratio, zero=ws['zbuf'], roi_size=float(self.roi_size))
+                         ratio=self.ratio, zero=ws['zbuf'], roi_size=float(self.roi_size), intr_scale=self.intrins_feat_scale,
+                         sample_size=self.sample_size, num_depth=self.num_depth, depth_start=self.corr_depth_start)
         tk('csr')
         # T path: the query-generator chain (RoIAlign -> conv -> fcs -> ref points -> query_pos) only needs the feature map and
         # the per-RoI cameras, the key chain (correlation -> key list -> PE -> K/V) only the boxes: run them on two streams

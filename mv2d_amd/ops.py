@@ -6,6 +6,7 @@ There is no CPU path here: tensors must live on a HIP device and the extension m
 import math
 import numbers
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -636,6 +637,39 @@ def check_pe_range(depth_start, position_range, who):
     return ds, pr
 
 
+BOX_CORR_DEFAULTS = dict(sample_size=4, num_depth=8, depth_start=0.5, depth_end=70, LID=True)      # BoxCorrelation's own defaults = the shipped configs' values
+MAX_SAMPLE_SIZE, MAX_NUM_DEPTH = 8, 64      # what mv2d_box_correlation_ex / mv2d_frame_geometry_ex take
+
+
+def _is_number(v):
+    return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_)) and math.isfinite(v)
+
+
+def check_box_correlation(sample_size=4, num_depth=8, depth_start=0.5, depth_end=70, LID=True, who='BoxCorrelation'):
+    """The reference BoxCorrelation's sampling keys (RH/utils/box_correlation.py:12-21) as the one accepted set, or ValueError naming the key:
+    sample_size an int in [1, 8], num_depth an int in [1, 64] (bools, floats and strings are refused), depth_start / depth_end finite numbers with
+    0 < depth_start < depth_end, LID a bool (False = uniform depth bins).  Returns (sample_size, num_depth, depth_start, depth_end, LID) with the
+    depths as Python floats."""
+    for key, v, hi in (('sample_size', sample_size, MAX_SAMPLE_SIZE), ('num_depth', num_depth, MAX_NUM_DEPTH)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not 1 <= v <= hi:
+            raise ValueError(f'{who}: box_correlation.{key} must be an int in [1, {hi}], got {v!r}')
+    if not _is_number(depth_start) or not depth_start > 0:
+        raise ValueError(f'{who}: box_correlation.depth_start must be a finite number > 0, got {depth_start!r}')
+    if not _is_number(depth_end) or not depth_end > depth_start:
+        raise ValueError(f'{who}: box_correlation.depth_end must be a finite number > depth_start = {depth_start!r}, got {depth_end!r}')
+    if not isinstance(LID, bool):
+        raise ValueError(f'{who}: box_correlation.LID must be True or False, got {LID!r}')
+    return int(sample_size), int(num_depth), float(depth_start), float(depth_end), LID
+
+
+def check_intrins_feat_scale(v, who='MV2DHead'):
+    """The RoI head's intrins_feat_scale (RH/mv2d_head.py: the factor on the per-RoI intrinsics fed to the query generator): a finite float or int,
+    no bool; returns it as a float."""
+    if not _is_number(v):
+        raise ValueError(f'{who}: intrins_feat_scale must be a finite number, got {v!r}')
+    return float(v)
+
+
 PE_OPTION_DEFAULTS = dict(with_fpe=True, no_sin_enc=False, adapt_pos3d=True, LID=True)      # the shipped configs' values of the PE's four switches
 
 
@@ -1232,14 +1266,15 @@ def roi_align(map0, rois, H, W, *, map1=None, out0=None, out1=None, out0_f32=Non
 def box_correlation(rois, view_start, trans, lin, depths, match, V, topk, pad_h, pad_w, max_per_view, sample_size=4,
                     num_depth=8, depth_start=0.5, iou_thr=0.0, ratio=0.0):
     """match [R, V, topk] int32: per RoI and view of its sample the RoIs of that view in IoU rank order, -1 where the keep rule drops an entry,
-    behind the list, in the RoI's own view and in a view without RoIs.  lin / depths: calib.constant_tables(sample_size, num_depth, depth_start).
-    depth_start, iou_thr and ratio cross the ABI as fp32, the reference compares the camera depth with depth_start in double: pass an
-    fp32-representable depth_start (0.25, 0.5, 1.0, ...), or a sample whose depth lies between the two values is valid on one side only."""
+    behind the list, in the RoI's own view and in a view without RoIs.  lin / depths: calib.constant_tables(sample_size, num_depth, depth_start,
+    depth_end, lid=LID).  sample_size 1..8, num_depth 1..64 (mv2d_box_correlation_ex refuses anything else).  depth_start crosses the ABI as a
+    double and is compared in double, as the reference compares it; iou_thr and ratio are fp32.  Up to 128 samples per (RoI, view) with an
+    fp32-representable depth_start run the first kernel instance, anything else the second (csrc/geometry.hip)."""
     _req(rois, torch.float32, 'rois'); _req(view_start, torch.int32, 'view_start'); _req(trans, torch.float64, 'trans')
     _req(match, torch.int32, 'match')
-    check(_lib.load().mv2d_box_correlation(_p(rois), _p(view_start), _p(trans), _p(lin), _p(depths), _p(match), rois.shape[0], V,
-                                           sample_size, num_depth, topk, pad_h, pad_w, depth_start, iou_thr, ratio, max_per_view,
-                                           _stream()), 'mv2d_box_correlation')
+    check(_lib.load().mv2d_box_correlation_ex(_p(rois), _p(view_start), _p(trans), _p(lin), _p(depths), _p(match), rois.shape[0], V,
+                                              int(sample_size), int(num_depth), topk, pad_h, pad_w, float(depth_start), iou_thr, ratio, max_per_view,
+                                              _stream()), 'mv2d_box_correlation')
 
 
 def frame_geometry(rois, viewK, viewE, intr, ld_intr, minv, view_start, trans, lin, depths, match, V, topk, pad_h, pad_w, max_per_view,
@@ -1248,10 +1283,10 @@ def frame_geometry(rois, viewK, viewE, intr, ld_intr, minv, view_start, trans, l
     (default: its rows); R = 0 only clears `zero` (the pointers must still be valid: an empty tensor has none)."""
     _req(rois, torch.float32, 'rois'); _req(viewK, torch.float64, 'viewK'); _req(viewE, torch.float64, 'viewE'); _req(view_start, torch.int32, 'view_start')
     _req(trans, torch.float64, 'trans'); _req(match, torch.int32, 'match'); _req(zero, torch.uint8, 'zero')
-    check(_lib.load().mv2d_frame_geometry(_p(rois), _p(viewK), _p(viewE), _p(K_roi), _p(intr), ld_intr, _p(minv), roi_size, intr_scale, min_size,
-                                          _p(view_start), _p(trans), _p(lin), _p(depths), _p(match), rois.shape[0] if R is None else R, V, sample_size,
-                                          num_depth, topk, pad_h, pad_w, depth_start, iou_thr, ratio, max_per_view, _p(zero), zero.numel() if zero is not None else 0,
-                                          _stream()), 'mv2d_frame_geometry')
+    check(_lib.load().mv2d_frame_geometry_ex(_p(rois), _p(viewK), _p(viewE), _p(K_roi), _p(intr), ld_intr, _p(minv), roi_size, intr_scale, min_size,
+                                             _p(view_start), _p(trans), _p(lin), _p(depths), _p(match), rois.shape[0] if R is None else R, V,
+                                             int(sample_size), int(num_depth), topk, pad_h, pad_w, float(depth_start), iou_thr, ratio, max_per_view,
+                                             _p(zero), zero.numel() if zero is not None else 0, _stream()), 'mv2d_frame_geometry')
 
 
 def csr_workspace_bytes(R, V, h, w):

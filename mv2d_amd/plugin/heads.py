@@ -243,7 +243,8 @@ class MV2DHead(nn.Module):
         self.query_generator = QueryGenerator(**query_generator)
         self.position_encoding = PE(**pe)
         self.box_corr_module = BoxCorrelation(**box_correlation)
-        self.pc_range, self.intrins_feat_scale, self.feat_lvl, self.force_fp32 = pc_range, intrins_feat_scale, feat_lvl, force_fp32
+        self.pc_range, self.feat_lvl, self.force_fp32 = pc_range, feat_lvl, force_fp32
+        self.intrins_feat_scale = ops.check_intrins_feat_scale(intrins_feat_scale, type(self).__name__)
         self.stage_loss_weights = train_cfg.get('stage_loss_weights') if train_cfg else None
         # one weight per decoder layer (the reference indexes the list per layer and would raise IndexError in its first loss, mv2d_head.py:243)
         if self.stage_loss_weights is not None and len(self.stage_loss_weights) < self.bbox_head.num_pred:
@@ -303,6 +304,8 @@ class MV2DHead(nn.Module):
                                       num_reg_fcs=getattr(self.bbox_head, 'num_reg_fcs', 2),
                                       masked_row=(self.test_cfg or {}).get('masked_row', 'nan'),
                                       query_generator=self.query_generator.shape,
+                                      sample_size=bc.sample_size, num_depth=bc.num_depth, corr_depth_start=bc.depth_start, corr_depth_end=bc.depth_end,
+                                      corr_LID=bc.LID, intrins_feat_scale=self.intrins_feat_scale,
                                       exact=(self.test_cfg or {}).get('index_exact', None))      # None: MV2D_EXACT decides
             if 'lo8_rows' in (self.test_cfg or {}):                              # test_cfg.lo8_rows=False: fp16 lo halves of the key / value rows (engine.py; default: e4m3 bytes)
                 self._engine.lo8_rows = bool(self.test_cfg['lo8_rows'])

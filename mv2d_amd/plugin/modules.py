@@ -562,7 +562,7 @@ class BoxCorrelation(nn.Module):
     def __init__(self, sample_size=4, num_depth=8, depth_start=0.5, depth_end=70, correlation_mode=None, LID=True, expand_stride=0,
                  force_cpu=False):
         super().__init__()
-        assert LID and correlation_mode is not None and (correlation_mode.startswith('topk_matched') or correlation_mode == 'all_matched'), \
+        assert correlation_mode is not None and (correlation_mode.startswith('topk_matched') or correlation_mode == 'all_matched'), \
             "kernel path implements 'topk_matched:k:thr:ratio' and 'all_matched'"
         self.all_matched = correlation_mode == 'all_matched'
         if self.all_matched:
@@ -570,7 +570,9 @@ class BoxCorrelation(nn.Module):
         else:
             info = correlation_mode.split(':')
             self.topk, self.iou_thr, self.ratio = int(info[1]), float(info[2]), float(info[3])
-        self.sample_size, self.num_depth, self.depth_start, self.depth_end = sample_size, num_depth, depth_start, depth_end
+        # the sampling keys (ops.check_box_correlation: the accepted values); force_cpu is accepted and ignored (there is no CPU path)
+        self.sample_size, self.num_depth, self.depth_start, self.depth_end, self.LID = ops.check_box_correlation(
+            sample_size, num_depth, depth_start, depth_end, LID, 'BoxCorrelation')
         self.correlation_mode, self.expand_stride = correlation_mode, expand_stride
 
     def check_counts(self, num_proposals_per_img):
@@ -584,7 +586,7 @@ class BoxCorrelation(nn.Module):
         R = rois.shape[0]
         l2i = torch.from_numpy(np.stack([np.asarray(m['lidar2img'], dtype=np.float64) for m in img_metas]))
         trans = torch.matmul(l2i[None], torch.inverse(l2i)[:, None]).reshape(V, V, 16).contiguous().to(dev)
-        ct = calib.constant_tables(self.sample_size, self.num_depth, self.depth_start, self.depth_end)
+        ct = calib.constant_tables(self.sample_size, self.num_depth, self.depth_start, self.depth_end, lid=self.LID)
         vs = torch.tensor(np.concatenate([[0], np.cumsum(num_proposals_per_img)]), dtype=torch.int32, device=dev)
         match = torch.empty((R, V, self.topk), dtype=torch.int32, device=dev)
         pad_h, pad_w, _ = img_metas[0]['pad_shape']

@@ -395,9 +395,13 @@ WORKLOADS = {
     'cfg2_s_r450': ('S', 6, 1, 512, 1408, None, 75),
     'cfg2_s_dup': ('S', 6, 1, 512, 1408, None, 50),
     'cfg5_t_dup': ('T', 6, 2, 640, 1600, None, 75),
+    # box_correlation's sampling keys end to end (tests/golden/box_corr_keys_*.npz): the overlapping rig cut to three views, as in
+    # tests/geometry_cases.py, so that other sample counts, depth ranges and depth bins give other match lists
+    'corr3_s': ('S', 3, 1, 224, 400, 416, 12),
+    'corr3_t': ('T', 3, 1, 224, 400, 416, 12),
 }
 # rigs that are not a full ring: yaw step in degrees and lateral camera spacing in metres
-RIG = {'nc6_s': (8.0, 0.35), 'cfg2_s_nc6': (8.0, 0.35), 'cfg2_s_dup': (8.0, 0.35)}       # (the duplicates of cfg2_s_dup on the overlapping rig: matched RoIs exist)
+RIG = {'nc6_s': (8.0, 0.35), 'cfg2_s_nc6': (8.0, 0.35), 'cfg2_s_dup': (8.0, 0.35), 'corr3_s': (8.0, 0.35), 'corr3_t': (8.0, 0.35)}       # (the duplicates of cfg2_s_dup on the overlapping rig: matched RoIs exist)
 
 
 def make_problem(name, seed=0, with_feat=True, ego=0.0):
