@@ -1179,8 +1179,8 @@ __device__ __forceinline__ void decode_rank_emit(const unsigned long long* sel, 
                                                  long long* __restrict__ bbox_index, int* __restrict__ count_out,
                                                  long long* __restrict__ topk_index_dbg, float* __restrict__ payload) {
     const int tid = threadIdx.x;
-    // rank by counting among the survivors (K plus, rarely, a few equal-logit candidates; ties resolved by the low
-    // 32 bits = lower index first); ranks >= K are dropped
+    // rank by counting among the survivors: the K largest keys and, where the caller collected by the logit half alone, the further keys
+    // whose logit equals the K-th (at most 1024 in all).  The keys are distinct (low 32 bits = ~index: lower index first); ranks >= K are dropped
     unsigned long long mine = 0ull;
     int rank = 1 << 30;
     if (tid < ns) {
@@ -1239,6 +1239,43 @@ __device__ __forceinline__ void decode_rank_emit(const unsigned long long* sel, 
     }
 }
 
+// One 8-bit round of the radix select of decode_topk_kernel: among the keys that agree with prefix_s above bit shift + 8, the bin of bits
+// [shift, shift + 8) that holds the want_s-th largest is appended to prefix_s and want_s becomes the count still wanted inside that bin.
+// The bin is found by one wave with a suffix scan over 256 bins (4 bins per lane).  Block-uniform; ends on a barrier.
+template <bool STREAM>
+__device__ __forceinline__ void decode_radix_round(const unsigned long long* keys, const float* __restrict__ cls, int n, int shift, int* hist,
+                                                   unsigned long long* prefix_s, int* want_s) {
+    const int tid = threadIdx.x;
+    if (tid < 256) hist[tid] = 0;
+    __syncthreads();
+    const unsigned long long prefix = *prefix_s;
+    const unsigned long long mask_hi = shift == 56 ? 0ull : (~0ull << (shift + 8));
+    for (int i = tid; i < n; i += 1024) {
+        const unsigned long long k = STREAM ? decode_key(cls, i) : keys[i];
+        if ((k & mask_hi) == prefix) atomicAdd(&hist[(int)((k >> shift) & 0xffull)], 1);
+    }
+    __syncthreads();
+    if (tid < 64) {
+        const int h0 = hist[4 * tid], h1 = hist[4 * tid + 1], h2 = hist[4 * tid + 2], h3 = hist[4 * tid + 3];
+        const int s4 = h0 + h1 + h2 + h3;
+        int suf = s4;                                   // inclusive suffix sum over lanes tid..63
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_down(suf, o, 64); if (tid + o < 64) suf += t; }
+        const int want = *want_s;
+        const unsigned long long bal = __ballot(suf >= want);
+        const int hit = 63 - __clzll(bal);              // highest lane whose suffix still covers `want`
+        if (tid == hit) {
+            int w = want - (suf - s4);                  // still wanted inside this lane's 4 bins
+            int b = 4 * tid + 3;
+            const int hh[4] = {h0, h1, h2, h3};
+            for (int e = 3; e > 0; --e) { if (hh[e] >= w) break; w -= hh[e]; --b; }
+            *prefix_s = prefix | ((unsigned long long)b << shift);
+            *want_s = w;
+        }
+    }
+    __syncthreads();
+}
+
 // STREAM = false: all R*ncls keys live in LDS (n <= 16384).  STREAM = true (n <= 65536): no key array -- every pass of the radix select
 // recomputes the keys from `cls` in global memory (L2-resident: 4 reads of at most 256 KB), only the <= 1024 survivors go to LDS.
 template <bool STREAM>
@@ -1272,44 +1309,30 @@ __global__ __launch_bounds__(1024) void decode_topk_kernel(const float* __restri
         for (int i = tid; i < n; i += 1024) keys[i] = decode_key(cls, i);
     if (tid == 0) { prefix_s = 0ull; want_s = K; nsel = 0; }
     __syncthreads();
-    // radix select over the 32 logit bits (4 rounds); the bin holding the K-th element is found by one wave with a
-    // suffix scan over 256 bins (4 bins per lane)
-    for (int shift = 56; shift >= 32; shift -= 8) {
-        if (tid < 256) hist[tid] = 0;
-        __syncthreads();
-        const unsigned long long prefix = prefix_s;
-        const unsigned long long mask_hi = shift == 56 ? 0ull : (~0ull << (shift + 8));
-        for (int i = tid; i < n; i += 1024) {
-            const unsigned long long k = STREAM ? decode_key(cls, i) : keys[i];
-            if ((k & mask_hi) == prefix) atomicAdd(&hist[(int)((k >> shift) & 0xffull)], 1);
-        }
-        __syncthreads();
-        if (tid < 64) {
-            const int h0 = hist[4 * tid], h1 = hist[4 * tid + 1], h2 = hist[4 * tid + 2], h3 = hist[4 * tid + 3];
-            const int s4 = h0 + h1 + h2 + h3;
-            int suf = s4;                                   // inclusive suffix sum over lanes tid..63
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_down(suf, o, 64); if (tid + o < 64) suf += t; }
-            const int want = want_s;
-            const unsigned long long bal = __ballot(suf >= want);
-            const int hit = 63 - __clzll(bal);              // highest lane whose suffix still covers `want`
-            if (tid == hit) {
-                int w = want - (suf - s4);                  // still wanted inside this lane's 4 bins
-                int b = 4 * tid + 3;
-                const int hh[4] = {h0, h1, h2, h3};
-                for (int e = 3; e > 0; --e) { if (hh[e] >= w) break; w -= hh[e]; --b; }
-                prefix_s = prefix | ((unsigned long long)b << shift);
-                want_s = w;
-            }
-        }
-        __syncthreads();
-    }
+    // radix select over the 32 logit bits (4 rounds)
+    for (int shift = 56; shift >= 32; shift -= 8) decode_radix_round<STREAM>(keys, cls, n, shift, hist, &prefix_s, &want_s);
     const unsigned long long kth_hi = prefix_s;                   // upper 32 bits of the K-th largest key
     for (int i = tid; i < n; i += 1024) {
         const unsigned long long k = STREAM ? decode_key(cls, i) : keys[i];
         if ((k & 0xffffffff00000000ull) >= kth_hi) { const int slot = atomicAdd(&nsel, 1); if (slot < 1024) sel[slot] = k; }
     }
     __syncthreads();
+    // The survivors are the fewer than K keys of a higher logit plus EVERY key whose logit equals the K-th: with many equal logits (a
+    // saturated or all-NaN frame, or max_num = 1024 with one tie at the boundary) they exceed the 1024 slots, and which of them took a slot
+    // is arrival order.  Then (block-uniform) the same select goes on over the index half of the key for the want_s still wanted among the
+    // equal logits: after four more rounds prefix_s IS the K-th largest key, and exactly the K keys >= it are collected.
+    const int nsel_hi = nsel;
+    if (nsel_hi > 1024) {
+        __syncthreads();                                          // every thread has read nsel
+        if (tid == 0) nsel = 0;
+        for (int shift = 24; shift >= 0; shift -= 8) decode_radix_round<STREAM>(keys, cls, n, shift, hist, &prefix_s, &want_s);
+        const unsigned long long kth = prefix_s;
+        for (int i = tid; i < n; i += 1024) {
+            const unsigned long long k = STREAM ? decode_key(cls, i) : keys[i];
+            if (k >= kth) { const int slot = atomicAdd(&nsel, 1); if (slot < 1024) sel[slot] = k; }
+        }
+        __syncthreads();
+    }
     decode_rank_emit(sel, keys, min(nsel, 1024), K, hist, kept_off, cls, reg, ncls, max_num, r0, r1, r2, r3, r4, r5, boxes, scores, labels,
                      bbox_index, count_out, topk_index_dbg, payload);
 }
@@ -1318,7 +1341,8 @@ __global__ __launch_bounds__(1024) void decode_topk_kernel(const float* __restri
 // f1 ("next" row): the caller's post-decoder step (mmdet3d_plugin/models/detectors/mv2d.py:265-287): scores scattered to
 // [K, num_classes+1], mmdet3d box3d_multiclass_nms with nms_thr = 1.0 (rotated IoU can never exceed 1 -> nothing is suppressed):
 // per class, boxes with score > score_thr in descending score order, classes concatenated in ascending order; only if more than
-// max_num survive, the max_num best by score (then globally score-descending).  Single block, rank by counting (n <= 1024).
+// max_num survive, the max_num best by score (then globally score-descending, equal scores in the order of that class-major list).
+// Single block, rank by counting (n <= 1024).
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(1024) void result_pack_kernel(const float* __restrict__ boxes, const float* __restrict__ scores, const long long* __restrict__ labels,
                                                            const int* __restrict__ count, float score_thr, int max_num, float* __restrict__ out_boxes,
@@ -1352,9 +1376,9 @@ __global__ __launch_bounds__(1024) void result_pack_kernel(const float* __restri
             rank += (lj < lb || (lj == lb && (sj > sc || (sj == sc && j < tid)))) ? 1 : 0;
         }
     } else {
-        for (int j = 0; j < n; ++j) {          // global score desc, index asc
-            const float sj = ss[j];
-            rank += (sl[j] < (1 << 20) && (sj > sc || (sj == sc && j < tid))) ? 1 : 0;
+        for (int j = 0; j < n; ++j) {          // global score desc; equal scores keep their class-major order (label asc, index asc):
+            const int lj = sl[j]; const float sj = ss[j];                              // a stable sort of the class-major list
+            rank += (lj < (1 << 20) && (sj > sc || (sj == sc && (lj < lb || (lj == lb && j < tid))))) ? 1 : 0;
         }
     }
     if (rank < max_num) {

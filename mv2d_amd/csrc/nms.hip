@@ -6,6 +6,7 @@
 // rectangle with the four half planes of the other (Sutherland-Hodgman) instead of mmcv's vertex/intersection hull; both are exact for
 // convex quadrilaterals up to rounding.
 // One block: ranks by counting, then one barrier-separated round per box; n <= 1024 (the head returns at most 300).
+// A box with a NaN score takes no part (the caller masks scores > score_thr first): it never suppresses, is never evaluated and comes out -inf.
 #include "common.h"
 
 namespace {
@@ -60,7 +61,7 @@ __global__ __launch_bounds__(1024) void nms_bev_kernel(const float* __restrict__
     boxes += (long long)b * in_stride * 9; scores += (long long)b * in_stride; labels += (long long)b * in_stride; scores_out += (long long)b * in_stride;
     const int n = min(count[b], 1024);
     if (t < n) {
-        sc[t] = scores[t]; lab[t] = (int)labels[t]; dead[t] = 0;
+        sc[t] = scores[t]; lab[t] = (int)labels[t]; dead[t] = isnan(sc[t]) ? 1 : 0;      // a NaN score takes no part (the caller masks score > thr)
         Pt c[4];
         box_corners(boxes + (long long)t * 9, c);
 #pragma unroll
@@ -68,10 +69,14 @@ __global__ __launch_bounds__(1024) void nms_bev_kernel(const float* __restrict__
         area[t] = fabsf(boxes[(long long)t * 9 + 3] * boxes[(long long)t * 9 + 4]);
     }
     __syncthreads();
-    if (t < n) {                                                      // rank: class ascending, score descending, index ascending
-        int r = 0;
-        for (int j = 0; j < n; ++j)
-            r += (lab[j] < lab[t]) || (lab[j] == lab[t] && (sc[j] > sc[t] || (sc[j] == sc[t] && j < t)));
+    if (t < n) {                                                      // rank: class ascending, score descending, index ascending;
+        const bool nan_t = dead[t];                                   // NaN scores (dead from the start) behind all others by index: a total
+        int r = 0;                                                    // order, so every slot of order[] is written
+        for (int j = 0; j < n; ++j) {
+            const bool nan_j = dead[j];
+            r += nan_j != nan_t ? (int)nan_t
+                                : (nan_t ? j < t : (lab[j] < lab[t]) || (lab[j] == lab[t] && (sc[j] > sc[t] || (sc[j] == sc[t] && j < t))));
+        }
         order[r] = t;
     }
     __syncthreads();
