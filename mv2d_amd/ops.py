@@ -1172,9 +1172,10 @@ def attn_drop_mask(nnz, seed, p_drop):
     return np.where(u >= np.uint32(thr), np.float32(1.0) / (np.float32(1.0) - pf), np.float32(0)).reshape(nnz, 8)
 
 
-def sparse_xattn_bwd(q, K, V, row_ptr, col_idx, ctx, dctx, R=None, transposed=None, p_drop=0.0, seed=0):
+def sparse_xattn_bwd(q, K, V, row_ptr, col_idx, ctx, dctx, R=None, transposed=None, p_drop=0.0, seed=0, long_rows=None, dq_scale=1.0):
     """Backward of sparse_xattn: returns (dq [R,256] fp32 w.r.t. the pre-scaled q, dK, dV [S,256] fp32); transposed = csr_transpose(...)
-    of the same CSR when the caller keeps it."""
+    of the same CSR when the caller keeps it.  long_rows: None = chosen from the pattern's density, 0 / 1 = the short-row / long-row kernels
+    (the results differ by summation order only); dq_scale: factor on dq."""
     _req(q, torch.float32, 'q'); _req(K, BF16, 'K'); _req(V, BF16, 'V'); _req(ctx, torch.float32, 'ctx'); _req(dctx, torch.float32, 'dctx')
     R = q.shape[0] if R is None else R
     S = K.shape[0]
@@ -1185,10 +1186,11 @@ def sparse_xattn_bwd(q, K, V, row_ptr, col_idx, ctx, dctx, R=None, transposed=No
     dV = torch.empty((S, 256), device=q.device, dtype=torch.float32)
     pair_ws = torch.empty((max(nnz, 1), 16), device=q.device, dtype=torch.float32)
     # hundreds of keys per query and of queries per key (the self attention over [denoising | matched] queries): the long-row kernels
-    long_rows = 1 if (nnz >= 64 * max(R, 1) and nnz >= 64 * max(S, 1)) else 0
+    if long_rows is None:
+        long_rows = 1 if (nnz >= 64 * max(R, 1) and nnz >= 64 * max(S, 1)) else 0
     check(_lib.load().mv2d_sparse_xattn_bwd_ex(_p(q), _p(K), _p(V), _p(row_ptr), _p(col_idx), _p(ctx), _p(dctx.contiguous()), _p(key_ptr), _p(pair_idx),
-                                               _p(pair_row), _p(pair_ws), _p(dq), _p(dK), _p(dV), R, S, float(p_drop), int(seed) & 0xffffffff, long_rows,
-                                               1.0, _stream()), 'mv2d_sparse_xattn_bwd')
+                                               _p(pair_row), _p(pair_ws), _p(dq), _p(dK), _p(dV), R, S, float(p_drop), int(seed) & 0xffffffff, int(bool(long_rows)),
+                                               float(dq_scale), _stream()), 'mv2d_sparse_xattn_bwd')
     return dq, dK, dV
 
 

@@ -399,6 +399,17 @@ def test_sparse_xattn_backward(dev, R, S, dens):
     assert relerr(K2.grad.float(), Kd.grad) < 8e-3 and relerr(V2.grad.float(), Vd.grad) < 8e-3           # returned in bf16
     d2 = ops.sparse_xattn_bwd(q, K, V, row_ptr.to(dev), col.to(dev), out.detach(), dout)
     assert all(torch.equal(a, b) for a, b in zip((dq, dK, dV), d2))                                    # deterministic (no atomics)
+    # row by row (train_cases.row_err: a short row, a key with one pair count like any other) against the same oracle evaluated in fp32 on the CPU
+    import train_cases as tc
+    qf, Kf, Vf = (t.detach().float().cpu().requires_grad_(True) for t in (q, K, V))
+    O.masked_cross_attention(qf, Kf, Vf, allowed).backward(dout.float().cpu())
+    with torch.no_grad():
+        f32 = dict(out=O.masked_cross_attention(qf, Kf, Vf, allowed), dq=qf.grad, dK=Kf.grad, dV=Vf.grad)
+    want = dict(out=ref.detach(), dq=qd.grad, dK=Kd.grad, dV=Vd.grad)
+    for name, got in (('out', out.detach()), ('dq', dq), ('dK', dK), ('dV', dV)):
+        yard, w = tc.worst(f32[name], want[name]), tc.worst(got, want[name])
+        print(f'train_ratio test_sparse_xattn_backward R={R} S={S} {name}: largest row error {w:.3e} = {w / yard:.2f} x the fp32 evaluation ({yard:.3e})')
+        assert 0.0 < yard < 1e-4 and w <= tc.K['sparse_fwd' if name == 'out' else 'sparse_bwd'] * yard, (name, w / yard)
     if dens > 0:
         assert float(dq[5].abs().max()) == 0.0
         unused = ~allowed.any(0)

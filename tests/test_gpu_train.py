@@ -1015,19 +1015,7 @@ def test_center2lidar_node_and_unfolding_node():
     assert float((x1.grad - x2.grad).abs().max()) <= 1e-5 * float(x2.grad.abs().max())
 
 
-def _dense_drop_mask(n, nk, p, seed):
-    """keep / scale factors [8, n, nk] of mv2d_dense_attn_* (csrc/dense_attn.hip: murmur3 finaliser of the counter (head n + query) nkp + key)"""
-    nkp = (nk + 31) & ~31
-    pf = np.float32(p)
-    t = float(pf) * 4294967296.0
-    thr = (0xffffffff if t >= 4294967295.0 else int(t)) or 1
-    idx = ((np.arange(8)[:, None, None] * n + np.arange(n)[None, :, None]) * nkp + np.arange(nk)[None, None, :]).astype(np.uint64)
-    with np.errstate(over='ignore'):
-        u = ((idx * np.uint64(0x9E3779B1)) & np.uint64(0xffffffff)).astype(np.uint32) ^ np.uint32(seed & 0xffffffff)
-        u ^= u >> np.uint32(16); u = ((u.astype(np.uint64) * np.uint64(0x85EBCA6B)) & np.uint64(0xffffffff)).astype(np.uint32)
-        u ^= u >> np.uint32(13); u = ((u.astype(np.uint64) * np.uint64(0xC2B2AE35)) & np.uint64(0xffffffff)).astype(np.uint32)
-        u ^= u >> np.uint32(16)
-    return np.where(u >= np.uint32(thr), np.float32(1.0) / (np.float32(1.0) - pf), np.float32(0.0)).astype(np.float64)
+from train_cases import dense_drop_mask as _dense_drop_mask          # noqa: E402  (the numpy restatement of the counter hash lives with the cases)
 
 
 @pytest.mark.parametrize('n,nk,p', [(37, 203, 0.0), (400, 1501, 0.0), (64, 128, 0.25), (100, 4097, 0.1), (16, 31, 0.0)])
@@ -1053,3 +1041,12 @@ def test_dense_block_without_materialised_logits(n, nk, p):
     for got, want, name in ((out, ref, 'out'), (qa.grad, qd.grad, 'dq'), (ka.grad, kd.grad, 'dk'), (va.grad, vd.grad, 'dv')):
         err = float((got.double() - want).abs().max() / want.abs().max())
         assert err < 1e-4, (name, err)
+    # row by row (train_cases.row_err) against the format model of the same operands: every product on bf16 hi + lo pairs, the rest in fp64
+    import train_cases as tc
+    assert tc.DENSE_SEED == 1234                                        # the seed of the run above is the one the model's mask uses
+    ops_cpu = tuple(t.detach().cpu() for t in (q, k, v, go))
+    model, ref64 = (tc.dense_attend(n, nk, p, prod=pr, operands=ops_cpu) for pr in (tc.Bf16x3(), None))
+    for got, name in ((out, 'ctx'), (qa.grad, 'dq'), (ka.grad, 'dk'), (va.grad, 'dv')):
+        yard, w = tc.worst(getattr(model, name), getattr(ref64, name)), tc.worst(got, getattr(ref64, name))
+        print(f'train_ratio test_dense_block_without_materialised_logits n={n} nk={nk} p={p} {name}: largest row error {w:.3e} = {w / yard:.2f} x the format model ({yard:.3e})')
+        assert 0.0 < yard < 2.0 ** -10 and w <= tc.K['dense_fwd' if name == 'ctx' else 'dense_bwd'] * yard, (name, w / yard)
