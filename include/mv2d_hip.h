@@ -485,6 +485,12 @@ int mv2d_xattn_tile_fwd_ordered(const void* Qt, const void* Xk, const void* Xv, 
 int mv2d_xattn_fused_fwd(const float* q, const void* WA_hi, const void* WA_lo, const void* WB_hi, const void* WB_lo, const float* bv, const void* Xk,
                          const void* Xv, const void* Xk_lo, const void* Xv_lo, const int* row_ptr, const int* col_idx, float* ctx, int R, int empty_nan,
                          const int* order, int lo_fmt, void* stream);
+/* The same with the dealing of a batch-sized launch (more blocks of 8 queries than CUs) forced: deal = 0 the library's policy (what
+ * mv2d_xattn_fused_fwd does: 2, sized for several launch sequences in flight; MV2D_XF_DEAL=1 / 2 overrides it for A/B runs), 1 = the block count
+ * rounded up to whole rounds of CUs (blocks of 4 .. 8 queries: the shape before this policy), 2 = ceil(R / 8) blocks of 8.  Launches of up to one round are spread over the CUs whatever deal says.  Results do not depend on it. */
+int mv2d_xattn_fused_fwd_p(const float* q, const void* WA_hi, const void* WA_lo, const void* WB_hi, const void* WB_lo, const float* bv, const void* Xk,
+                           const void* Xv, const void* Xk_lo, const void* Xv_lo, const int* row_ptr, const int* col_idx, float* ctx, int R, int empty_nan,
+                           const int* order, int lo_fmt, int deal, void* stream);
 /* Key tiles SHARED BETWEEN QUERIES (round 6, csrc/xattn_group.hip; the masks of RH/mv2d_t_head.py:79-109 / the duplication of
  * RH/mv2d_s_head.py:184-192 let 2.9-6.2 queries list the same key row).  mv2d_xattn_group_tables (once per frame): the queries of every sample
  * (grp_start [n_samples + 1]; rows behind grp_start[n_samples] are bucket padding and form groups of their own), taken in `order` (a permutation that

@@ -185,7 +185,10 @@ struct AttnOutX3Params {
 
 // RT row tiles (16 rows each) per block share one fetch of the weight fragments.  A block is bound by fetching its 0.5 MB of weights
 // through one CU's L1 (~57 GB/s), whatever the number of rows: with a batch of samples (M > 512) two row tiles per block take the
-// same time on half as many CUs, which the other streams' wide kernels can use.
+// same time on half as many CUs, which the other streams' wide kernels can use.  FOUR row tiles (64 rows per block above 2048 rows: 75 blocks instead of 150
+// at 4800 rows) were measured and not kept: a block takes 1.34 x as long (12.5 -> 16.9 us and 21.7 -> 29.4 us per launch: the matrix pipe starts to count),
+// 0.67 x the CU-time; four streams gain 0.7 %, under three times their own spread, and one stream of 16-sample launches loses 3.9 %
+// (profiles/batch_shapes_kernel_stats.txt).
 __device__ __forceinline__ void split8(const float4& x0, const float4& x1, BFrag& hi, BFrag& lo) {
     uint2 h0, l0, h1, l1;
     split4(x0, h0, l0);

@@ -29,6 +29,20 @@
 #ifndef MV2D_XF_QB_DEFAULT
 #define MV2D_XF_QB_DEFAULT 8
 #endif
+// How the queries of a batch-sized launch (more blocks of QB than one round of CUs) are dealt to blocks:
+//   XF_DEAL_ROUNDS  the block count rounded up to whole rounds of CUs while a block keeps >= QB / 2 queries (4800 queries: 768 blocks of 6-7)
+//   XF_DEAL_FULL    ceil(R / QB) blocks of QB queries (600 blocks of 8): the fewest blocks, i.e. the fewest map phases and the least CU-time
+// The default is XF_DEAL_FULL: the library sizes batch launches for SEVERAL launch sequences in flight.  A block holds a whole CU (132 KB of LDS) and
+// pays both map phases whatever its query count, so what a launch costs the other streams is blocks x time per block.  Measured on an MI355X
+// (profiles/batch_shapes_kernel_stats.txt; 16 cfg2_s samples per launch, R = 4800): the launch takes 104.8 us either way in the four-stream loop and
+// 105.8 / 105.2 us alone on an idle GPU, on 768 / 600 CU slots; four streams complete 10524 -> 10720 samples/s (+1.9 %), one stream is unchanged
+// (6752 -> 6750).  MV2D_XF_DEAL=1 restores whole rounds.  The policy is a function of the row count only: neither a sample's result nor a graph's
+// shape depends on what else runs.
+enum { XF_DEAL_ROUNDS = 1, XF_DEAL_FULL = 2 };
+#ifndef MV2D_XF_DEAL_DEFAULT
+#define MV2D_XF_DEAL_DEFAULT XF_DEAL_FULL
+#endif
+constexpr int XF_DEAL_DEFAULT = MV2D_XF_DEAL_DEFAULT;
 
 #ifdef MV2D_XF_TRACE
 __device__ long long g_xf_trace[32];
@@ -60,9 +74,10 @@ __global__ __launch_bounds__(64 * QB, 2) void xattn_fused_kernel(const float* __
     int* rend = rq + 2 * QB;
     // XCD-chunked block order (block b runs on XCD b % 8): every XCD works through one contiguous range of query slots; optional launch order
     // of the queries (the S path ranks them by the smallest RoI they list, so that matched RoIs share an L2).  Speed only.
-    // The R query slots are dealt EVENLY to nblk >= ceil(R / 8) blocks (the host rounds nblk up to a multiple of the CU count when that leaves >= 4
-    // queries per block: 4800 queries = 600 blocks of 8 are 2.34 rounds of 256 one-block-per-CU slots, and the third round costs nearly a full one;
-    // 768 blocks of 6-7 queries are three full rounds of 0.78 x the work each: 140 -> 112 us per layer).
+    // The R query slots are dealt EVENLY to nblk >= ceil(R / QB) blocks; the host chooses nblk (XF_DEAL_* above: ceil(R / QB) for a batch-sized launch,
+    // up to one block per CU for a small one).  Rounding 600 blocks of 8 up to 768 of 6-7 -- three whole rounds of one block per CU -- was measured at
+    // 140 -> 112 us per layer when that rule was written; on today's kernel both shapes take 105 us (profiles/batch_shapes_kernel_stats.txt), and the
+    // 600 leave 168 CU slots per launch to the other streams.
     const int blk = xcd_chunked(blockIdx.x, nblk);
     const int slot0 = (int)((long long)blk * R / nblk), nq = (int)((long long)(blk + 1) * R / nblk) - slot0;
     if (nq <= 0) return;
@@ -233,9 +248,12 @@ extern "C" int mv2d_xf_trace_read(long long* host, int n) { return hipMemcpyFrom
 #endif
 
 // C-ABI: include/mv2d_hip.h
-extern "C" int mv2d_xattn_fused_fwd(const float* q, const void* WA_hi, const void* WA_lo, const void* WB_hi, const void* WB_lo, const float* bv,
-                                    const void* Xk, const void* Xv, const void* Xk_lo, const void* Xv_lo, const int* row_ptr, const int* col_idx,
-                                    float* ctx, int R, int empty_nan, const int* order, int lo_fmt, void* stream) {
+// deal: the block count of a batch-sized launch (more blocks than one round of CUs) as a launch policy -- 0 = the library's default,
+// 1 = whole rounds (XF_DEAL_ROUNDS), 2 = ceil(R / QB) full blocks (XF_DEAL_FULL).  Which block computes a query changes, how it is computed does not.
+extern "C" int mv2d_xattn_fused_fwd_p(const float* q, const void* WA_hi, const void* WA_lo, const void* WB_hi, const void* WB_lo, const float* bv,
+                                      const void* Xk, const void* Xv, const void* Xk_lo, const void* Xv_lo, const int* row_ptr, const int* col_idx,
+                                      float* ctx, int R, int empty_nan, const int* order, int lo_fmt, int deal, void* stream) {
+    MV2D_CHECK_ARG(deal >= 0 && deal <= 2, "mv2d_xattn_fused_fwd_p: deal is 0 (default), 1 (whole rounds) or 2 (full blocks)");
     MV2D_CHECK_ARG(lo_fmt == 0 || (lo_fmt == 1 && Xk_lo), "mv2d_xattn_fused_fwd: lo_fmt is 0 (key16 lo rows) or 1 (e4m3 lo rows; needs the lo rows)");
     MV2D_CHECK_ARG(q && WA_hi && WA_lo && WB_hi && WB_lo && bv && Xk && Xv && row_ptr && col_idx && ctx && R >= 0, "mv2d_xattn_fused_fwd: bad args");
     MV2D_CHECK_ARG((Xk_lo == nullptr) == (Xv_lo == nullptr), "mv2d_xattn_fused_fwd: Xk_lo and Xv_lo come together");
@@ -254,9 +272,14 @@ extern "C" int mv2d_xattn_fused_fwd(const float* q, const void* WA_hi, const voi
     const int QB = qb_env == 4 || qb_env == 8 ? qb_env : MV2D_XF_QB_DEFAULT;
     const int slots = n_cu * (QB == 4 ? 2 : 1);               // blocks of a round
     int nblk = (R + QB - 1) / QB;
-    if (nblk > slots) {                                       // whole rounds, as long as a block keeps >= QB / 2 queries
-        const int up = (nblk + slots - 1) / slots * slots;
-        if ((long long)up * (QB / 2) <= R) nblk = up;
+    if (nblk > slots) {
+        // a batch-sized launch: the dealing policy (above XF_DEAL_DEFAULT).  MV2D_XF_DEAL=1 / 2 forces it for A/B runs; the entry's argument wins.
+        static const int deal_env = [] { const char* e = getenv("MV2D_XF_DEAL"); return e ? atoi(e) : 0; }();
+        const int policy = deal ? deal : (deal_env == XF_DEAL_ROUNDS || deal_env == XF_DEAL_FULL ? deal_env : XF_DEAL_DEFAULT);
+        if (policy == XF_DEAL_ROUNDS) {                       // whole rounds, as long as a block keeps >= QB / 2 queries
+            const int up = (nblk + slots - 1) / slots * slots;
+            if ((long long)up * (QB / 2) <= R) nblk = up;
+        }                                                     // XF_DEAL_FULL: ceil(R / QB) blocks, dealt evenly: QB - 1 or QB queries each
     } else {
         // a small launch (one sample: 300 queries = 38 blocks of 8 on a 256-CU chip): spread it, down to two queries per block -- the blocks stream
         // the map weights from L2 either way, and the launch is bound by the longest block (26.5 -> ~14 us per layer at R = 300)
@@ -273,4 +296,10 @@ extern "C" int mv2d_xattn_fused_fwd(const float* q, const void* WA_hi, const voi
 #undef MV2D_XF
     MV2D_LAUNCH_CHECK();
     return MV2D_OK;
+}
+
+extern "C" int mv2d_xattn_fused_fwd(const float* q, const void* WA_hi, const void* WA_lo, const void* WB_hi, const void* WB_lo, const float* bv,
+                                    const void* Xk, const void* Xv, const void* Xk_lo, const void* Xv_lo, const int* row_ptr, const int* col_idx,
+                                    float* ctx, int R, int empty_nan, const int* order, int lo_fmt, void* stream) {
+    return mv2d_xattn_fused_fwd_p(q, WA_hi, WA_lo, WB_hi, WB_lo, bv, Xk, Xv, Xk_lo, Xv_lo, row_ptr, col_idx, ctx, R, empty_nan, order, lo_fmt, 0, stream);
 }

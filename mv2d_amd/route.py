@@ -17,7 +17,8 @@ def default_options():
         xattn_waves=int(env('MV2D_XATTN_WAVES', '2')), q_order=True, fold_sa0=True, masked_transpose=True, last_stage_heads=False,
         exact_skip=frozenset({'conv'}), lo8_rows=True, pe_at_positions=env('MV2D_PE_AT_POS', '1') != '0', pe_rows_in_waves=False,
         ablate_zero_lo=frozenset(), keep_sine_rows=False, stop_before_decoder=False, force_nc=None, debug_attn=False,
-        fuse_qg_tail=env('MV2D_QG_TAIL', '1') != '0', pe_cache=env('MV2D_PE_CACHE', '1') != '0', pe_cache_views=env('MV2D_PE_CACHE_VIEWS', '0') == '1')
+        fuse_qg_tail=env('MV2D_QG_TAIL', '1') != '0', pe_cache=env('MV2D_PE_CACHE', '1') != '0', pe_cache_views=env('MV2D_PE_CACHE_VIEWS', '0') == '1',
+        xattn_deal=0)                 # forced block dealing of the one-launch cross attention (0 = the library's policy)
 
 
 OPTIONS = tuple(default_options())
@@ -139,6 +140,11 @@ class Route(NamedTuple):
     # not part of the graph key, only "full launches" / "split launches" is.  This field: the route ALLOWS it -- T path, and the conditions of pe_cache.
     # The S path ignores the option.
     pe_cache_views: bool
+    # option xattn_deal, tests only: the FORCED block dealing of the one-launch cross attention, handed to ops.xattn_fused(deal=...) -- 1 = a launch of
+    # more blocks of 8 queries than CUs is cut into whole rounds of CUs, 2 = into full blocks of 8 (csrc/xattn_fused.hip).  0, the default: the
+    # library's policy, a function of the row count alone.  Which block computes a row changes, the row does not (tests/test_gpu_batch_shapes.py).
+    # Launch-only.
+    xattn_deal: int
 
     @property
     def storage(self):
@@ -180,6 +186,8 @@ def resolve(opts, kind, exact, depth_num, map_dtype=torch.float32, keep_stages=F
     if o.ablate_zero_lo and lo8:
         raise ValueError('ablate_zero_lo works on key16 lo rows: set lo8_rows = False')
     assert not (debug and use_graph), 'debug_attn: eager runs only'
+    if int(o.xattn_deal) not in (0, 1, 2):
+        raise ValueError('mv2d engine: xattn_deal is 0 (the library\'s policy), 1 (whole rounds) or 2 (full blocks)')
     pe_pos = kind == 'S' and exact and bool(o.pe_at_positions)
     pe_opt = lambda key, shipped: (pe_options or {}).get(key, shipped)      # noqa: E731
     pe_cache_ok = (pe_x3 and bool(pe_opt('with_fpe', True)) and not pe_opt('no_sin_enc', False) and not stages and not o.keep_sine_rows
@@ -196,4 +204,5 @@ def resolve(opts, kind, exact, depth_num, map_dtype=torch.float32, keep_stages=F
         masked=bool(o.masked_transpose) and not forked and not o.keep_sine_rows and not stages,
         last_stage_heads=bool(o.last_stage_heads) and not stages, debug_attn=debug, stop_before_decoder=bool(o.stop_before_decoder),
         force_nc=o.force_nc, ablate_zero_lo=frozenset(o.ablate_zero_lo) if exact else frozenset(),
-        qg_tail_fused=bool(o.fuse_qg_tail) and not stages, pe_cache=pe_cache, pe_cache_views=pe_cache_views)
+        qg_tail_fused=bool(o.fuse_qg_tail) and not stages, pe_cache=pe_cache, pe_cache_views=pe_cache_views,
+        xattn_deal=int(o.xattn_deal))
