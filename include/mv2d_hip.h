@@ -491,6 +491,12 @@ int mv2d_xattn_fused_fwd(const float* q, const void* WA_hi, const void* WA_lo, c
 int mv2d_xattn_fused_fwd_p(const float* q, const void* WA_hi, const void* WA_lo, const void* WB_hi, const void* WB_lo, const float* bv, const void* Xk,
                            const void* Xv, const void* Xk_lo, const void* Xv_lo, const int* row_ptr, const int* col_idx, float* ctx, int R, int empty_nan,
                            const int* order, int lo_fmt, int deal, void* stream);
+/* The same with the queries per block forced as well: qb = 0 the library's choice (what mv2d_xattn_fused_fwd_p does: with e4m3 lo rows, 12 for a
+ * batch-sized launch -- more blocks of 8 than CUs -- and 8 otherwise; MV2D_XF_QB overrides it for A/B runs), 4 or 8 on every route, 12 with
+ * e4m3 lo rows only (lo_fmt = 1: 12 KB of LDS per query, three waves per SIMD).  deal counts in blocks of qb.  Results do not depend on it. */
+int mv2d_xattn_fused_fwd_q(const float* q, const void* WA_hi, const void* WA_lo, const void* WB_hi, const void* WB_lo, const float* bv, const void* Xk,
+                           const void* Xv, const void* Xk_lo, const void* Xv_lo, const int* row_ptr, const int* col_idx, float* ctx, int R, int empty_nan,
+                           const int* order, int lo_fmt, int deal, int qb, void* stream);
 /* Key tiles SHARED BETWEEN QUERIES (round 6, csrc/xattn_group.hip; the masks of RH/mv2d_t_head.py:79-109 / the duplication of
  * RH/mv2d_s_head.py:184-192 let 2.9-6.2 queries list the same key row).  mv2d_xattn_group_tables (once per frame): the queries of every sample
  * (grp_start [n_samples + 1]; rows behind grp_start[n_samples] are bucket padding and form groups of their own), taken in `order` (a permutation that

@@ -110,6 +110,7 @@ SIGNATURES = {
     'mv2d_xattn_tile_fwd_ordered': (I, [P, P, P, P, P, P, P, P, P, LL, I, I, I, P, I, P]),
     'mv2d_xattn_fused_fwd': (I, [P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, P, I, P]),
     'mv2d_xattn_fused_fwd_p': (I, [P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, P, I, I, P]),
+    'mv2d_xattn_fused_fwd_q': (I, [P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, P, I, I, I, P]),
     'mv2d_xattn_group_max': (I, [I, I]),
     'mv2d_xattn_group_tables': (I, [P, P, P, P, I, I, I, P, P, P, P, P, P, I, P, P, P]),
     'mv2d_xattn_group_fwd': (I, [P] * 19 + [I, I, P]),

@@ -67,14 +67,21 @@ __device__ __forceinline__ float row16_max(float v) {
 // (round 4: a tile is two dependent round trips, index then rows; the index trip of the next tile runs under the current tile's gather and
 // arithmetic: cfg3_t 94.5 -> 87.3 us per layer).
 // ------------------------------------------------------------------------------------------------
-template <int XLO, bool DBG>
+// LO8B (XLO = 2 only; the fused kernel): the lo key tile in LDS keeps the e4m3 BYTES (16 rows x 32 chunks of 8 B = 4 KB, chunk c of row r at slot
+// c ^ 2 r: the 8-byte fragment reads of a half wave -- 16 rows x 2 chunks -- hit 32 different bank pairs) and compute() widens them with the same
+// lo8_chunk as it reads the fragment: the same conversion of the same bytes, as many per lane and tile, on 12 KB of LDS per wave instead of 16.
+// LO8B is the fused kernel above 8 queries per block: three waves per SIMD, i.e. 168 registers per lane and no scratch.  Same arithmetic in the same
+// order; what also changes is what lives across the tile loop and when the lo value rows are requested (see fresh(), compute()).
+template <int XLO, bool DBG, bool LO8B = false>
 struct XattnWalk {
+    static_assert(!LO8B || XLO == 2, "LO8B: the e4m3 lo rows only");
     typedef std::conditional_t<XLO == 2, u32x2, u32x4> lo_t;      // a lane's piece of a lo row: 16 bytes of key16, 8 of e4m3
     struct KRows { u32x4 hi[8]; lo_t lo[XLO ? 8 : 1]; };          // staging of a tile's key rows
     struct VRows { u32x4 hi[4][2]; lo_t lo[XLO ? 4 : 1][2]; };    // a tile's value rows: they stay in registers
 
     const unsigned short *Xk, *Xv, *Xk_lo, *Xv_lo;
-    int lane, n, g, beg, end;
+    int lane, n, g;
+    int beg, end;
     uint4 *kt, *kt2;
     float* pl;
     float* dbg_logits;
@@ -90,6 +97,23 @@ struct XattnWalk {
         : Xk(Xk_), Xv(Xv_), Xk_lo(Xk_lo_), Xv_lo(Xv_lo_), lane(lane_), n(lane_ & 15), g(lane_ >> 4), beg(beg_), end(end_), kt(kt_), kt2(kt2_), pl(pl_),
           dbg_logits(dbg_logits_), dbg_stride(dbg_stride_) {}
 
+    // LO8B: the lane's constants are made opaque once per use, so that the ~55 LDS / gather addresses
+    // derived from them are recomputed per tile (two VALU operations each) and do not live across the tile loop as registers -- hipcc hoisted them and spilled.
+    __device__ __forceinline__ static int fresh(int x) {
+        if constexpr (LO8B) asm volatile("" : "+v"(x));
+        return x;
+    }
+    // the value of lane `src` (0 .. 63): LO8B spares __shfl's own lane arithmetic and the register it keeps
+    __device__ __forceinline__ static int shfl(int v, int src) {
+        if constexpr (LO8B) return __builtin_amdgcn_ds_bpermute(src << 2, v);
+        else return __shfl(v, src, 64);
+    }
+    __device__ __forceinline__ void relane() {
+        lane = fresh(lane);
+        n = lane & 15;
+        g = lane >> 4;
+    }
+
     __device__ __forceinline__ void reset() {
 #pragma unroll
         for (int i = 0; i < 4; ++i) { m_run[i] = -INFINITY; l_run[i] = 0.f; }
@@ -103,7 +127,7 @@ struct XattnWalk {
     __device__ __forceinline__ void load_v(const unsigned short* V_, int myidx, u32x4 (&dst)[4][2]) const {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const unsigned int vidx = (unsigned int)__shfl(myidx, 4 * g + e, 64);
+            const unsigned int vidx = (unsigned int)shfl(myidx, 4 * g + e);
             const char* vp = reinterpret_cast<const char*>(V_) + ((vidx << 9) + 16u * (unsigned)n);
             dst[e][0] = *reinterpret_cast<const u32x4*>(vp);
             dst[e][1] = *reinterpret_cast<const u32x4*>(vp + 256);
@@ -112,7 +136,7 @@ struct XattnWalk {
     __device__ __forceinline__ void load_k(const unsigned short* K_, int myidx, u32x4 (&dst)[8]) const {
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-            const unsigned int ridx = (unsigned int)__shfl(myidx, 2 * i + (lane >> 5), 64);
+            const unsigned int ridx = (unsigned int)shfl(myidx, 2 * i + (lane >> 5));
             dst[i] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(K_) + ((ridx << 9) + (unsigned)(lane & 31) * 16u));
         }
     }
@@ -127,7 +151,7 @@ struct XattnWalk {
     __device__ __forceinline__ void load_v8(const unsigned short* V_, int myidx, u32x2 (&dst)[4][2]) const {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const unsigned int vidx = (unsigned int)__shfl(myidx, 4 * g + e, 64);
+            const unsigned int vidx = (unsigned int)shfl(myidx, 4 * g + e);
             const char* vp = reinterpret_cast<const char*>(V_) + ((vidx << 8) + 8u * (unsigned)n);
             dst[e][0] = *reinterpret_cast<const u32x2*>(vp);
             dst[e][1] = *reinterpret_cast<const u32x2*>(vp + 128);
@@ -136,7 +160,7 @@ struct XattnWalk {
     __device__ __forceinline__ void load_k8(const unsigned short* K_, int myidx, u32x2 (&dst)[8]) const {
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-            const unsigned int ridx = (unsigned int)__shfl(myidx, 2 * i + (lane >> 5), 64);
+            const unsigned int ridx = (unsigned int)shfl(myidx, 2 * i + (lane >> 5));
             dst[i] = *reinterpret_cast<const u32x2*>(reinterpret_cast<const char*>(K_) + ((ridx << 8) + (unsigned)(lane & 31) * 8u));
         }
     }
@@ -144,19 +168,24 @@ struct XattnWalk {
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             const int rowi = 2 * i + (lane >> 5);
-            tile[rowi * 32 + ((lane & 31) ^ (rowi & 15))] = lo8_chunk(make_uint2(src[i].x, src[i].y));
+            if constexpr (LO8B) reinterpret_cast<u32x2*>(tile)[rowi * 32 + ((lane & 31) ^ (2 * rowi))] = src[i];
+            else tile[rowi * 32 + ((lane & 31) ^ (rowi & 15))] = lo8_chunk(make_uint2(src[i].x, src[i].y));
         }
     }
     // the hi and lo halves of the 16 key rows are requested together (16 loads in flight) ...
-    __device__ __forceinline__ void request_k(int myidx, KRows& k) const {
+    __device__ __forceinline__ void request_k(int myidx, KRows& k) {
+        if constexpr (LO8B) relane();
         load_k(Xk, myidx, k.hi);
         if constexpr (XLO == 1) load_k(Xk_lo, myidx, k.lo);
+        if constexpr (LO8B) relane();
         if constexpr (XLO == 2) load_k8(Xk_lo, myidx, k.lo);
     }
     // ... and go to the LDS tile
-    __device__ __forceinline__ void stage_k(const KRows& k) const {
+    __device__ __forceinline__ void stage_k(const KRows& k) {
+        if constexpr (LO8B) relane();
         store_k(kt, k.hi);
         if constexpr (XLO == 1) store_k(kt2, k.lo);
+        if constexpr (LO8B) relane();
         if constexpr (XLO == 2) store_k8(kt2, k.lo);
     }
     __device__ __forceinline__ void request_v(int myidx, VRows& v) const {
@@ -174,14 +203,19 @@ struct XattnWalk {
     // 66.3 / 68.2 (same box, round 4) -- twice the bytes in flight per wave buy nothing, the kernel sits at what the memory system delivers
     // for 512-byte rows (4-5 TB/s from HBM, 10-12 TB/s where L2 serves the repeats), not at a per-wave latency chain.  The same for the fused
     // kernel with e4m3 lo rows in round 6 (110.6 against 98.6 us per cfg2_s launch: profiles/r06_xattn_fused_lo8_experiments.txt, 1).
-    __device__ __forceinline__ void gather(int myidx, bool with_k, VRows& v) const {
+    __device__ __forceinline__ void gather(int myidx, bool with_k, VRows& v) {
         if constexpr (XLO != 0) {
             if (with_k) {
                 KRows k;
                 request_k(myidx, k);
                 stage_k(k);
             }
-            request_v(myidx, v);
+            if constexpr (LO8B) {
+                relane();
+                load_v(Xv, myidx, v.hi);
+            } else {
+                request_v(myidx, v);
+            }
         } else if (with_k) {
             KRows k;
             request_k(myidx, k);
@@ -194,8 +228,10 @@ struct XattnWalk {
     }
 
     // logits, online softmax and P . V of tile tt: the key tile is in LDS (kt, XLO: kt2), the value rows in registers
-    __device__ __forceinline__ void compute(int tt, const VRows& v) {
+    // (LO8B: gather() has requested the hi value rows only; the lo rows of the tile's keys `myidx` are requested here, behind the logits MFMAs -- 16 registers)
+    __device__ __forceinline__ void compute(int tt, VRows& v, int myidx = 0) {
         const int kbase = beg + 16 * tt;
+        if constexpr (LO8B) relane();
         // ---- logits of the tile: D[row 4g+i][key n] = sum_c Qt[row][c] Xk[key][c]
         f32x4_t sacc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -205,10 +241,17 @@ struct XattnWalk {
             sacc = mfma_k16_16x16x32(qa[s].u, kb.u, sacc);
             if (XLO) {
                 Frag kl, qh;
-                kl.u = kt2[n * 32 + ((4 * s + g) ^ n)];
+                if constexpr (LO8B) kl.u = lo8_chunk(reinterpret_cast<const uint2*>(kt2)[n * 32 + ((4 * s + g) ^ (2 * n))]);
+                else kl.u = kt2[n * 32 + ((4 * s + g) ^ n)];
                 qh.u = n < 8 ? qa[s].u : make_uint4(0u, 0u, 0u, 0u);              // hi rows only
                 sacc = mfma_k16_16x16x32(qh.u, kl.u, sacc);
             }
+        }
+        if constexpr (LO8B) {
+            __builtin_amdgcn_sched_barrier(0);
+            relane();
+            load_v8(Xv_lo, myidx, v.lo);
+            __builtin_amdgcn_sched_barrier(0);
         }
         const bool valid = kbase + n < end;
         float sv[4], p[4], alpha[4];
@@ -282,6 +325,7 @@ struct XattnWalk {
                     zc = mfma_k16_16x16x16(pah, vl, zc);
                 }
                 Z[H * 8 + w] = zc;
+                if constexpr (LO8B) { if (w & 1) __builtin_amdgcn_sched_barrier(0); }
             }
         }
         __builtin_amdgcn_wave_barrier();                                             // before the next tile overwrites kt / pl
@@ -289,6 +333,17 @@ struct XattnWalk {
 
     // ---- after the last tile: l_run = the row sums over the 16 key lanes (the softmax denominators of the wave's share of the row)
     __device__ __forceinline__ void row_sums() {
+        if constexpr (LO8B) {                 // (the same exchanges, addressed from the walk's own lane: __shfl_xor keeps a lane id of its own across the tile loop)
+            relane();
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                float l = l_run[i];
+#pragma unroll
+                for (int m = 1; m < 16; m *= 2) l += __int_as_float(__builtin_amdgcn_ds_bpermute((lane ^ m) << 2, __float_as_int(l)));
+                l_run[i] = l;
+            }
+            return;
+        }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             float l = l_run[i];

@@ -1115,7 +1115,7 @@ class HeadEngine:
                 if rt.grouped:
                     o.xattn_group(ws['q'], mapA, mapB, bv, xk_rows, xv_rows, ws['row_ptr'], ws['grp_tab'], out=ws['ctx'], R=R, **rows)
                 elif rt.xattn_fused:
-                    o.xattn_fused(ws['q'], mapA, mapB, bv, xk_rows, xv_rows, ws['row_ptr'], ws['col_idx'], out=ws['ctx'], R=R, deal=rt.xattn_deal, **rows)
+                    o.xattn_fused(ws['q'], mapA, mapB, bv, xk_rows, xv_rows, ws['row_ptr'], ws['col_idx'], out=ws['ctx'], R=R, deal=rt.xattn_deal, qb=rt.xattn_qb or None, **rows)
                 else:
                     o.xattn_qmap(ws['q'], mapA, ws['Qt'], R=R)
                     tile_attn(i)

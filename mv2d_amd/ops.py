@@ -1060,10 +1060,12 @@ def xattn_tile(Qt, Xk, Xv, row_ptr, col_idx, out=None, R=None, dbg_logits=None, 
     return out
 
 
-def xattn_fused(q, WA, WB, bv, Xk, Xv, row_ptr, col_idx, out=None, R=None, empty_nan=True, Xk_lo=None, Xv_lo=None, order=None, deal=0):
-    """ctx [R,256] fp32 = xattn_ctxmap(xattn_tile(xattn_qmap(q))) in ONE launch (csrc/xattn_fused.hip: blocks of 8 queries, Qt / z stay on chip);
+def xattn_fused(q, WA, WB, bv, Xk, Xv, row_ptr, col_idx, out=None, R=None, empty_nan=True, Xk_lo=None, Xv_lo=None, order=None, deal=0, qb=None):
+    """ctx [R,256] fp32 = xattn_ctxmap(xattn_tile(xattn_qmap(q))) in ONE launch (csrc/xattn_fused.hip: blocks of 8 or 12 queries, Qt / z stay on chip);
     bitwise equal to the three calls with waves=1.  deal: how a launch of more blocks than CUs is cut into blocks -- 0 = the library's policy
-    (full blocks; MV2D_XF_DEAL=1 restores whole rounds), 1 = whole rounds of CUs, 2 = full blocks of 8 (same rows bit for bit)."""
+    (full blocks; MV2D_XF_DEAL=1 restores whole rounds), 1 = whole rounds of CUs, 2 = full blocks (same rows bit for bit).  qb: the queries per
+    block -- None = the library's choice (e4m3 lo rows: 12 for a launch of more blocks of 8 than CUs, else 8), 4 or 8, or with e4m3 lo rows 12
+    (same rows bit for bit)."""
     _req(q, torch.float32, 'q'); _req(bv, torch.float32, 'bv'); _req(row_ptr, torch.int32, 'row_ptr'); _req(col_idx, torch.int32, 'col_idx')
     for t, n_ in ((WA[0], 'WA_hi'), (WA[1], 'WA_lo'), (WB[0], 'WB_hi'), (WB[1], 'WB_lo')):
         _req(t, q16_dtype(), n_)
@@ -1073,9 +1075,9 @@ def xattn_fused(q, WA, WB, bv, Xk, Xv, row_ptr, col_idx, out=None, R=None, empty
     if out is None:
         out = torch.empty((R, 256), device=q.device, dtype=torch.float32)
     _req(out, torch.float32, 'out')
-    check(_lib.load().mv2d_xattn_fused_fwd_p(_p(q), _p(WA[0]), _p(WA[1]), _p(WB[0]), _p(WB[1]), _p(bv), _p(Xk), _p(Xv), _p(Xk_lo), _p(Xv_lo), _p(row_ptr),
-                                             _p(col_idx), _p(out), R, 1 if empty_nan else 0, _p(order), lo_fmt, int(deal), _stream()),
-          'mv2d_xattn_fused_fwd_p')
+    check(_lib.load().mv2d_xattn_fused_fwd_q(_p(q), _p(WA[0]), _p(WA[1]), _p(WB[0]), _p(WB[1]), _p(bv), _p(Xk), _p(Xv), _p(Xk_lo), _p(Xv_lo), _p(row_ptr),
+                                             _p(col_idx), _p(out), R, 1 if empty_nan else 0, _p(order), lo_fmt, int(deal), int(qb or 0), _stream()),
+          'mv2d_xattn_fused_fwd_q')
     return out
 
 

@@ -18,7 +18,8 @@ def default_options():
         exact_skip=frozenset({'conv'}), lo8_rows=True, pe_at_positions=env('MV2D_PE_AT_POS', '1') != '0', pe_rows_in_waves=False,
         ablate_zero_lo=frozenset(), keep_sine_rows=False, stop_before_decoder=False, force_nc=None, debug_attn=False,
         fuse_qg_tail=env('MV2D_QG_TAIL', '1') != '0', pe_cache=env('MV2D_PE_CACHE', '1') != '0', pe_cache_views=env('MV2D_PE_CACHE_VIEWS', '0') == '1',
-        xattn_deal=0)                 # forced block dealing of the one-launch cross attention (0 = the library's policy)
+        xattn_deal=0,                 # forced block dealing of the one-launch cross attention (0 = the library's policy)
+        xattn_qb=0)                   # forced queries per block of the same launch (0 = the library's choice)
 
 
 OPTIONS = tuple(default_options())
@@ -145,6 +146,9 @@ class Route(NamedTuple):
     # library's policy, a function of the row count alone.  Which block computes a row changes, the row does not (tests/test_gpu_batch_shapes.py).
     # Launch-only.
     xattn_deal: int
+    # option xattn_qb, tests only: the FORCED queries per block of the same launch, handed to ops.xattn_fused(qb=...): 4, 8, or with e4m3 lo rows 12.
+    # 0, the default: the library's choice, a function of the row count alone.  Launch-only, and the rows do not depend on it (tests/test_gpu_xattn_fused_qb.py).
+    xattn_qb: int
 
     @property
     def storage(self):
@@ -188,6 +192,8 @@ def resolve(opts, kind, exact, depth_num, map_dtype=torch.float32, keep_stages=F
     assert not (debug and use_graph), 'debug_attn: eager runs only'
     if int(o.xattn_deal) not in (0, 1, 2):
         raise ValueError('mv2d engine: xattn_deal is 0 (the library\'s policy), 1 (whole rounds) or 2 (full blocks)')
+    if int(o.xattn_qb) not in (0, 4, 8, 12):
+        raise ValueError('mv2d engine: xattn_qb is 0 (the library\'s choice), 4, 8 or 12')
     pe_pos = kind == 'S' and exact and bool(o.pe_at_positions)
     pe_opt = lambda key, shipped: (pe_options or {}).get(key, shipped)      # noqa: E731
     pe_cache_ok = (pe_x3 and bool(pe_opt('with_fpe', True)) and not pe_opt('no_sin_enc', False) and not stages and not o.keep_sine_rows
@@ -205,4 +211,4 @@ def resolve(opts, kind, exact, depth_num, map_dtype=torch.float32, keep_stages=F
         last_stage_heads=bool(o.last_stage_heads) and not stages, debug_attn=debug, stop_before_decoder=bool(o.stop_before_decoder),
         force_nc=o.force_nc, ablate_zero_lo=frozenset(o.ablate_zero_lo) if exact else frozenset(),
         qg_tail_fused=bool(o.fuse_qg_tail) and not stages, pe_cache=pe_cache, pe_cache_views=pe_cache_views,
-        xattn_deal=int(o.xattn_deal))
+        xattn_deal=int(o.xattn_deal), xattn_qb=int(o.xattn_qb))
